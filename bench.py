@@ -16,7 +16,14 @@ Prints ONE JSON line on rank 0 with the contract fields plus
 After the W warm-up steps an untimed "settle" phase keeps stepping until the step time is stable (cold-box power
 management; see main()); the timed region is still EXACTLY K steps between barrier + synchronize.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1 without WORLD_SIZE: launches its own N ranks)
+A plain run measures the headline figure only (set-up, warm-up, the K timed steps, the JSON line).  Everything else -- the
+rooflines and their profiler passes, the PCIe-inclusive figures, the CPU baseline, the secondary records (other precisions,
+geometries, exchange schedules, inference) and the exchange's own timings -- runs only under `--full`.
+`--dump-outputs DIR` runs, after the timed steps, one more step of the timed path from the initial weights and writes what it
+computed (dump_outputs()): a step from a fixed state, so that two runs, or two builds, can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                             (N > 1 without WORLD_SIZE: launches its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -65,6 +72,25 @@ def _time_launch(launch, iters):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters
+
+
+DUMP_CAP = 2 << 20     # elements per array written by --dump-outputs; a larger array is written as a fixed sample of this size
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every named tensor as d/<name>.npy, float64 for float64 tensors and float32 otherwise.  A tensor of more
+    than DUMP_CAP elements is flattened and written as a fixed sample (DUMP_CAP indices drawn under seed 0, sorted), so that a
+    dump stays well under 64 MB and two runs of the same arguments write the same arrays (to the rounding of the library's default
+    fp32-atomic sums: ops.set_deterministic)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randint(t.numel(), (DUMP_CAP,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy())
 
 
 def _hw(imsize):
@@ -458,6 +484,8 @@ def inference_record(o):
     per = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(o.steps))
     masks = run.outs[0]
     assert tuple(masks.shape[:2]) == (o.batch, o.T) and bool(torch.isfinite(masks).all())
+    if o.dump_outputs:      # what test() returns for the last timed batch (eval mode: no state carries over from one batch to the next)
+        dump_outputs(o.dump_outputs, dict(zip(("mask_probs", "class_probs", "stop_probs"), run.outs)))
     ms = 1000.0 * dt / o.steps
     out = {"metric": "inference images/sec at %dx%d, T=%d, batch=%d" % (o.imsize, imw, o.T, o.batch), "value": round(o.batch * o.steps / dt, 1),
            "unit": "images/s", "n_gpus": 1, "steps": o.steps, "warmup": o.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
@@ -620,8 +648,9 @@ def check_world(gpus):
 
 
 def self_launch(gpus):
-    """plain `python bench.py --gpus N` (the shape of the driver's N=1 command): become `torch.distributed.run --standalone` with N ranks
-    of this very command line.  Rank 0 of the child job prints the JSON line; the launcher adds nothing to stdout."""
+    """plain `python bench.py --gpus N` (the shape of the driver's N=1 command): run `torch.distributed.run` with N ranks of this very
+    command line as a child process and exit with its status.  Rank 0 of the child job prints the JSON line; the launcher adds nothing
+    to stdout.  (A child, not an exec: this process has already opened the GPU to count the devices.)"""
     ndev = visible_devices()
     if ndev < gpus and os.environ.get("RSIS_SHARE_GPU", "") != "1":
         sys.exit("bench.py: --gpus %d but only %d device(s) visible (one rank per GPU; no N-rank run is faked)" % (gpus, ndev))
@@ -629,7 +658,7 @@ def self_launch(gpus):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     print("[bench] self-launch: %s" % " ".join(cmd), file=sys.stderr, flush=True)
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def exchange_report(a, encoder, decoder, crits, optims, reducer, gstep, seg, batch, t_run, rank_ms, o, fence, note):
@@ -641,6 +670,7 @@ def exchange_report(a, encoder, decoder, crits, optims, reducer, gstep, seg, bat
     drift): step - this = the EXPOSED part of the exchange, (5) per-rank step times."""
     if reducer is None or not getattr(reducer, "active", False):
         return {"mode": "none", "world": 1, "note": "single process, no gradient exchange (RSIS_FORCE_DIST=1 runs the collective path at world 1)"}
+    # (1), (2) and (5) are what the timed run did; (3) and (4) are runs of their own: --full only
     from rsis_amd import comm as _comm
     from rsis_amd.train import EXCHANGE_CUTS, GraphedStep, exchange_plan
     world = dist.get_world_size()
@@ -653,6 +683,9 @@ def exchange_report(a, encoder, decoder, crits, optims, reducer, gstep, seg, bat
            "rccl_direct": dict(_comm.LAST_STATUS),
            "range_bytes": {k: int(sum(b.numel() * b.element_size() for b in v)) for k, v in plan.items()},
            "rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3), "all": [round(v, 3) for v in rank_ms]}}
+    if not o.full:
+        note("exchange: %s" % json.dumps(rep))
+        return rep
     try:
         red = gstep._reduce if gstep is not None else (lambda b, _a=False: dist.all_reduce(b, op=dist.ReduceOp.SUM))
         bufs = [b for k in ("dec", "trunk_hi", "rest") for b in plan[k]]
@@ -734,7 +767,13 @@ def main():
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the gate-kernel roofline leg and print its object (for `rocprofv3 --kernel-trace --stats`: the "
                          "profile then holds exactly the launches the `roofline` figure is computed from)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: rooflines and their profiler passes, "
+                    "PCIe-inclusive figures, CPU baseline, secondary records, the exchange's own timings (the --skip-* options still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, run one more step of the timed path "
+                    "from the initial weights and write what it computed as DIR/<name>.npy")
     o = ap.parse_args()
+    if not o.full:
+        o.skip_cpu = o.skip_roofline = o.skip_traffic = o.skip_secondary = True
     if o.cpu_baseline_only:
         print(json.dumps(cpu_baseline(o.imsize, o.T)))
         return
@@ -748,7 +787,7 @@ def main():
         return
 
     if o.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(o.gpus)              # (does not return: the process becomes the launcher of N ranks)
+        self_launch(o.gpus)              # (does not return: exits with the status of the N-rank job)
 
     from rsis_amd.train import GraphedStep, build_optimizers, init_distributed, runIter
     from rsis_amd.modules import FeatureExtractor, RSIS
@@ -774,6 +813,12 @@ def main():
         for p in list(encoder.parameters()) + list(decoder.parameters()) + list(encoder.buffers()):
             dist.broadcast(p.data, 0)
     enc_opt, dec_opt = build_optimizers(a, encoder, decoder)
+    # --dump-outputs: the initial state, restored for the step whose outputs are written (after the timed steps)
+    initial = None
+    if o.dump_outputs:
+        initial = ({k: v.detach().clone() for k, v in encoder.state_dict().items()}, {k: v.detach().clone() for k, v in decoder.state_dict().items()},
+                   [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.group.state_dict().items()} for opt in (enc_opt, dec_opt)],
+                   torch.get_rng_state(), torch.cuda.get_rng_state())
     force = os.environ.get("RSIS_FORCE_DIST", "") == "1"
     reducer = BucketedAllReduce([dec_opt.group, enc_opt.group], force=force) if (world > 1 or force) else None
     if reducer is not None and reducer.active:
@@ -969,6 +1014,32 @@ def main():
         except Exception as ex:  # noqa: BLE001
             pcie = {"error": repr(ex)}
     exchange = exchange_report(a, encoder, decoder, crits, [enc_opt, dec_opt], reducer, gstep, seg, batch, t_run, rank_ms, o, fence, note)
+    if initial is not None:
+        # --dump-outputs: one more step of the timed path, from the initial state.  (The last TIMED step starts from the end of a chain
+        # of steps whose sums end in fp32 atomics, so its state differs from run to run beyond rounding; a step from a fixed state
+        # does not.)  The project's own reload path: release the captures, load in place, invalidate the packed weights; then one
+        # eager call of GraphedStep -- the runIter call its graph is a capture of -- on the same resident batch.
+        from rsis_amd import ops
+        fence()
+        if gstep is not None:
+            gstep.release()
+        encoder.load_state_dict(initial[0])
+        decoder.load_state_dict(initial[1])
+        for opt, sd in zip((enc_opt, dec_opt), initial[2]):
+            opt.load_state_dict(sd)
+        ops.bump_weight_epoch()
+        torch.set_rng_state(initial[3])
+        torch.cuda.set_rng_state(initial[4])
+        dstep = GraphedStep(a, encoder, decoder, crits, [enc_opt, dec_opt], reducer, warm=1)
+        dlosses, douts, _perms = dstep(batch, t_run)
+        fence()
+        if rank == 0:
+            # what runIter returns to its caller: the four losses and the outputs (raw mask logits, class probabilities).  Not the
+            # updated weights or the trunk's gradients: Adam's first update is +-lr wherever a gradient is near zero, and the backward
+            # through ~100 train-mode BatchNorms amplifies rounding to ~1 %, so those differ between two runs by more than rounding.
+            dump_outputs(o.dump_outputs, {"losses": torch.tensor([float(v) for v in dlosses[:4]], dtype=torch.float64),
+                                          "mask_logits": douts[0], "class_probs": douts[1]})
+            note("--dump-outputs: one step from the initial state written to %s" % o.dump_outputs)
 
     cpu, out, secondary = None, None, None
     if rank == 0:
@@ -993,7 +1064,7 @@ def main():
             for sd, extra, env in (("bf16", [], {}), ("fp32", ["--skip-traffic"], {}),
                                    ("bf16", ["--skip-traffic", "--skip-roofline"], {"RSIS_BF16_STORAGE": "0", "RSIS_DECODER_BLK": "0"})):
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--dtype", sd, "--imsize", "224", "--batch", str(o.batch), "--T",
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--dtype", sd, "--imsize", "224", "--batch", str(o.batch), "--T",
                                         str(o.T), "--steps", str(o.steps), "--warmup", str(o.warmup), "--skip-cpu", "--skip-secondary",
                                         "--kernel-iters", str(o.kernel_iters)] + extra, capture_output=True, text=True, timeout=600,
                                        env=dict(os.environ, **env))
@@ -1007,7 +1078,7 @@ def main():
                 secondary[0]["speedup_over_bf16_operands_on_fp32_activations"] = round(secondary[0]["value"] / secondary[2]["value"], 3)
             # BASELINE configs[4]'s per-GPU workload (Cityscapes geometry 512x1024, T=20, batch 8 per GPU, bf16), same harness, graph replay
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--dtype", "bf16", "--imsize", "512", "--imsize-w", "1024", "--batch", "8", "--T", "20",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--dtype", "bf16", "--imsize", "512", "--imsize-w", "1024", "--batch", "8", "--T", "20",
                                     "--steps", str(max(5, o.steps // 2)), "--warmup", str(o.warmup), "--skip-cpu", "--skip-secondary",
                                     "--kernel-iters", str(max(4, o.kernel_iters // 2))],
                                    capture_output=True, text=True, timeout=900, env=dict(os.environ))
@@ -1020,7 +1091,7 @@ def main():
             # captured all-reduces, 1 / world scaling all run; the wire is a loop-back): what the exchange machinery costs per step
             if os.environ.get("RSIS_FORCE_DIST", "") != "1":
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
                                         "--steps", str(max(10, o.steps // 2)), "--warmup", str(o.warmup), "--skip-cpu", "--skip-secondary", "--skip-roofline"],
                                        capture_output=True, text=True, timeout=600,
                                        env=dict(os.environ, RSIS_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())))
@@ -1032,7 +1103,7 @@ def main():
                 # ... and the CUT schedule (RSIS_EXCHANGE=cuts: graphs A | B1 | B2 | C with torch.distributed collectives between them -- the
                 # fallback whenever the direct communicator is not available) next to it, so that both schedules are driver-timed every round
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
                                         "--steps", str(max(10, o.steps // 2)), "--warmup", str(o.warmup), "--skip-cpu", "--skip-secondary", "--skip-roofline"],
                                        capture_output=True, text=True, timeout=600,
                                        env=dict(os.environ, RSIS_FORCE_DIST="1", RSIS_EXCHANGE="cuts", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())))
@@ -1044,7 +1115,7 @@ def main():
                     secondary.append({"dtype": "fp32", "config": "configs[1] + RSIS_FORCE_DIST=1 + RSIS_EXCHANGE=cuts", "error": repr(ex)})
             # update_encoder off (the reference's training state until -finetune_after epochs: args.py:39-45), headline geometry
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--encoder-frozen", "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--encoder-frozen", "--batch", str(o.batch), "--imsize", str(o.imsize), "--T", str(o.T),
                                     "--steps", str(o.steps), "--warmup", str(o.warmup), "--skip-cpu", "--skip-secondary", "--skip-roofline"],
                                    capture_output=True, text=True, timeout=600, env=dict(os.environ))
                 sj = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1054,7 +1125,7 @@ def main():
             # inference: test() (reference src/test.py:16-50, the caller of src/eval.py:262) at the headline geometry in fp32 and at configs[2]'s in bf16
             for extra in (["--imsize", str(o.imsize), "--dtype", "fp32"], ["--imsize", "224", "--dtype", "bf16"]):
                 try:
-                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--inference", "--batch", str(o.batch), "--T", str(o.T), "--steps",
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--inference", "--batch", str(o.batch), "--T", str(o.T), "--steps",
                                         str(o.steps), "--warmup", str(o.warmup), "--kernel-iters", str(o.kernel_iters)] + extra,
                                        capture_output=True, text=True, timeout=600, env=dict(os.environ))
                     secondary.append(json.loads(r.stdout.strip().splitlines()[-1]))

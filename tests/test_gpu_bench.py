@@ -23,10 +23,11 @@ def _free_port():
 
 
 def _run(extra, env_extra):
+    # (--full: the exchange's own timings -- the collectives alone, the iteration without exchange -- are runs of their own)
     env = dict(os.environ, RSIS_SHARE_GPU="1", RSIS_DIST_BACKEND="gloo", **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3", "--batch", "4",
-           "--T", "3", "--skip-cpu", "--skip-roofline", "--skip-secondary", "--no-settle"] + (extra if "--imsize" in extra else ["--imsize", "128"] + extra)
+           "--T", "3", "--full", "--skip-cpu", "--skip-roofline", "--skip-secondary", "--no-settle"] + (extra if "--imsize" in extra else ["--imsize", "128"] + extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, "bench.py --gpus 2 failed:\n%s\n%s" % (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
