@@ -44,15 +44,25 @@ class GraphedTest(object):
     """test() captured ONCE per input shape as a hipGraph and replayed: the ~560 kernel launches of an inference batch cost the
     host as long in Python (12 ms at batch 32, T = 10) as the GPU needs for them.  The first `warm` calls run eagerly (they load
     code objects and let BatchNorm / packed-weight caches settle), the next one captures; the input is copied into a static buffer
-    and the returned tensors are STATIC -- the next call overwrites them, so consume (or clone) them first.  Weights must not
-    change between calls (the packed copies are part of the captured launches' arguments); a new input shape re-captures."""
+    and the returned tensors are STATIC -- the next call overwrites them, so consume (or clone) them first.  A new input shape re-captures.
+    So does a change of the weights: the packed copies are part of the captured launches' arguments, so the capture records a weights key
+    (the packed-weight epoch, which the optimizer steps and the replays of a captured training step bump, and every parameter's
+    (_version, data_ptr()), which load_state_dict and other in-place writes bump); a call that finds another key runs test() eagerly
+    (which repacks the copies from the live weights) and the next call captures again.  Writes through `.data` bypass `_version`: after
+    one, call ops.bump_weight_epoch()."""
 
     def __init__(self, args, encoder, decoder, return_logits=False, warm=2):
         self.args, self.encoder, self.decoder, self.return_logits, self.warm = args, encoder, decoder, return_logits, warm
         self.graph, self.static_x, self.outs, self.n_eager = None, None, None, 0
+        self.params, self.key = None, None
         self.stream = torch.cuda.Stream()
 
+    def _weights_key(self):
+        return (ops._WEIGHT_EPOCH[0],) + tuple((p._version, p.data_ptr()) for p in self.params)
+
     def __call__(self, x):
+        if self.graph is not None and self._weights_key() != self.key:
+            self.graph, self.static_x, self.outs, self.n_eager = None, None, None, self.warm - 1  # new weights: repack eagerly, capture again
         if self.graph is not None and tuple(x.shape) != tuple(self.static_x.shape):
             self.graph, self.static_x, self.outs, self.n_eager = None, None, None, self.warm      # new shape: capture again
         if self.graph is None:
@@ -61,6 +71,9 @@ class GraphedTest(object):
                 return test(self.args, self.encoder, self.decoder, x, self.return_logits)
             self.static_x = x.clone()
             torch.cuda.synchronize()
+            # (the parameter list is taken once per capture: walking the module tree on every call costs 0.5 ms of host time)
+            self.params = list(self.encoder.parameters()) + list(self.decoder.parameters())
+            self.key = self._weights_key()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
                 self.outs = test(self.args, self.encoder, self.decoder, self.static_x, self.return_logits)

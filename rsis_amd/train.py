@@ -509,6 +509,11 @@ class GraphedStep(object):
         for g in self._groups():
             if self.args.update_encoder or g is not self.optims[0].group:
                 g.note_replay()
+        # the replay changed the weights on the device without touching any packed copy's key: the copies of the captured repack_all()
+        # job table are current, every other one (the direct twins the Winograd convs serve no-grad calls from, created by the first
+        # validation pass after the capture) would serve the old weights to the next eager call.  Host-only; that call repacks each copy
+        # in place (same buffers: the captured addresses and the job table stay valid).
+        ops.bump_weight_epoch()
         for m in self._bns:                        # HipBatchNorm2d counts its training calls on the host
             m._nbt_pending += 1
         return self.result
