@@ -16,10 +16,16 @@ grouped launch), but leaves the backward to autograd: one node per cell, run one
     the (B, T, N) layout train.py:118 stacks them into, the sum over t of d(gates) for the time-invariant skip term
     (rsis_sum_leading), the time-batched weight gradients of the recurrent channels (as decoder_fused does).
 
+The schedule is written once, in _DecoderSeqFn.  How the recurrence is stored is a layout object the node asks for buffers and
+launches, picked per call by blk_supported():
+
+  * _Nchw: fp32 NCHW (-dtype fp32, and -dtype bf16 under RSIS_DECODER_BLK=0);
+  * _Blk: channel-blocked bf16 [B][C/8][H][W][8] for hidden states, saved gates, up-sampled inputs, the hoisted gate terms and
+    their gradients (-dtype bf16); the cell state and its gradient stay fp32 NCHW in both.
+
 Arithmetic and kernels per cell are those of the per-step path (tests/test_gpu_modules.py compares them); only the launch
 schedule differs.  The per-timestep `RSIS.forward` stays for callers that thread the state themselves.
 """
-import ctypes
 import os
 
 import torch
@@ -94,29 +100,28 @@ def supported_for_input(decoder, skip_channels, B, H, W, T):
     return supported(decoder, probes, T) and blk_supported(decoder, probes)
 
 
+# RSIS_DECODER_BLK=0: keep fp32 NCHW storage in the decoder under -dtype bf16 (bf16 operands only, the round-3 path)
+BLK_ENABLED = [os.environ.get("RSIS_DECODER_BLK", "1") != "0"]
+
+
+def blk_supported(decoder, skip_feats):
+    """the decoder's storage half of `-dtype bf16`: every tensor of the recurrence as channel-blocked bf16 (csrc/conv_blk_dec.hip,
+    blk_dec.hip) -- needs bf16 cells, whole 8-channel cells at every level and the 8-channel conv_out (hidden_size % 128 == 0)"""
+    if not BLK_ENABLED[0]:
+        return False
+    hs = [c.hidden_size for c in decoder.clstm_list]
+    if not all(getattr(c, "dtype", ops.DTYPE_F32) == ops.DTYPE_BF16 for c in decoder.clstm_list):
+        return False
+    if any(h % 8 for h in hs) or any(_chan(f) % 8 for f in skip_feats) or hs[-1] != 8:
+        return False
+    return (2 * skip_feats[-1].shape[3]) % 4 == 0
+
+
 class _Level(object):
     __slots__ = ("cell", "hid", "c_up", "c_skip", "H", "W", "hoist", "dyn", "G", "Hs", "Cs", "ACT", "UP", "KEY", "SIDE", "ARG", "skip")
 
 
-def _conv_out_seq_ok(Cin, W):
-    return Cin in (4, 8, 16) and W % 4 == 0
-
-
 UPCONV = [os.environ.get("RSIS_UPCONV", "1") != "0"]       # the last level's upsample + conv_out as one op per direction (upconv_out.hip)
-
-
-def _upconv_ok(L, last, H5, W5):
-    return UPCONV[0] and L.rsis_upconv_out_supported(last.hid, last.H, last.W, H5, W5) == 1
-
-
-def _upconv_bwd(L, d_masks, last, blk, co_w, dW, db, dside, T, B, H5, W5, DH_last):
-    """the backward of the fused tail: DH_last <- the gradient of the last level's hidden states through conv_out and the upsample (plus
-    the side max-pool gradient at its arg-max pixel); dW / db accumulate (fixed-order sums of per-block partials)"""
-    nb = L.rsis_upconv_out_bwd_blocks(T, B, last.H, last.W)
-    partial = torch.empty(nb * 80, dtype=torch.float32, device=d_masks.device)
-    check(L.rsis_upconv_out_bwd(ptr(d_masks), ptr(last.Hs), 1 if blk else 0, ptr(co_w.detach()), ptr(DH_last), ptr(dW) if dW is not None else None,
-                                ptr(db) if db is not None else None, ptr(dside), ptr(last.ARG), ptr(partial), T, B, last.hid, last.H, last.W, H5, W5,
-                                stream()), "rsis_upconv_out_bwd")
 
 
 def _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, probs_tb, dp_tb, ds_tb, dsides, hb):
@@ -134,140 +139,361 @@ def _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, probs_tb, dp_tb, ds_tb,
         check(rc, "rsis_heads_bwd(all steps)")
 
 
-def _heads_all_steps(L, levels, hs, n, rows, Wc, bc, Ws, bs, ncls, probs_tb, stop_tb):
-    """the class / stop heads (model.py:169-182) of ALL timesteps in one launch: every (t, b) row is independent, the per-level key /
-    feature / arg-max arrays are [T][B][hid] contiguous, i.e. T * B rows; the launch decodes the pooled keys (writes SIDE / ARG)"""
-    check(L.rsis_heads_fwd_keys(ptr_array([v.KEY for v in levels]), ptr_array([v.SIDE for v in levels]), ptr_array([v.ARG for v in levels]),
-                                int_array(hs), n, rows, ptr(Wc), ptr(bc), ncls, ptr(Ws), ptr(bs), ptr(probs_tb), ptr(stop_tb), stream()),
-          "rsis_heads_fwd_keys(all steps)")
+def _per_level(buf, hs, T, B):
+    """views [T][B][hid] of one flat buffer, level after level"""
+    return [v.view(T, B, h) for v, h in zip(buf.split([T * B * h for h in hs]), hs)]
 
 
-class _DecoderSeqFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, decoder, T, keep, *tensors):
-        L = lib()
-        n = len(decoder.clstm_list)
-        feats = [t if t.is_contiguous() else t.contiguous() for t in tensors[:n]]
-        params = tensors[n:]
-        gates_w = [params[2 * i] for i in range(n)]
-        gates_b = [params[2 * i + 1] for i in range(n)]
-        co_w, co_b, Wc, bc, Ws, bs = params[2 * n:2 * n + 6]
-        _lib.require_cuda_f32(*feats, *params)
-        need_grad = bool(keep) and any(ctx.needs_input_grad)     # (grad mode is off inside forward: the caller says whether a backward may follow)
-        dev = feats[0].device
-        B = feats[0].shape[0]
-        hs = [c.hidden_size for c in decoder.clstm_list]
-        tot = sum(hs)
-        f32 = dict(dtype=torch.float32, device=dev)
-        # one zeroed key buffer for the side max-pools of the whole sequence (rsis_lstm_job.side_key), decoded by the heads launches
-        KEY = torch.zeros(T * B * tot, dtype=torch.int64, device=dev)
-        SIDE = torch.empty(T * B * tot, **f32)
-        ARG = torch.empty(T * B * tot, dtype=torch.int32, device=dev)
-        levels, off = [], 0
-        for i, cell in enumerate(decoder.clstm_list):
-            lv = _Level()
-            lv.cell, lv.hid, lv.c_up, lv.c_skip = cell, hs[i], (0 if i == 0 else hs[i - 1]), feats[i].shape[1]
-            lv.H, lv.W = feats[i].shape[2], feats[i].shape[3]
-            lv.hoist, lv.dyn = decoder_fused._packs(cell, lv.c_up, lv.c_skip)
-            # G_i = W[:, skip channels] * skip_i + b, once per iteration (the skip features do not depend on t)
-            wp = lv.hoist.fwd(gates_w[i], gates_b[i])
-            lv.G = torch.empty((B, 4 * lv.hid, lv.H, lv.W), **f32)
-            check(L.rsis_conv2d_fwd(ptr_array([feats[i]]), int_array([lv.c_skip]), 1, B, lv.H, lv.W, ptr(wp), 4 * lv.hid, 3, 1, 1,
-                                    ptr(lv.hoist.bias_p), None, ptr(lv.G), lv.H, lv.W, ops.FORCE_TILE[0] + (100 if need_grad else 0), lv.hoist.dtype,
-                                    stream()),
-                  "rsis_conv2d_fwd(hoist)")
-            lv.Hs = torch.empty((T, B, lv.hid, lv.H, lv.W), **f32)
-            lv.Cs = torch.empty((T, B, lv.hid, lv.H, lv.W), **f32)
-            lv.ACT = torch.empty((T, B, 4 * lv.hid, lv.H, lv.W), **f32) if need_grad else None
-            lv.UP = torch.empty((T, B, lv.c_up, lv.H, lv.W), **f32) if lv.c_up > 0 else None
-            m = T * B * lv.hid
-            lv.KEY, lv.SIDE, lv.ARG = KEY[off:off + m].view(T, B, lv.hid), SIDE[off:off + m].view(T, B, lv.hid), ARG[off:off + m].view(T, B, lv.hid)
-            off += m
-            levels.append(lv)
-        last = levels[-1]
+def _diagonal(d, n, T):
+    """the cells (level i, step t) with i + t == d: independent of each other in either direction"""
+    return [(i, d - i) for i in range(n) if 0 <= d - i < T]
+
+
+def _gate_srcs(lv, t):
+    """the sources of cell (lv, t)'s gate conv besides the hoisted skip term, in packing order: up(h[i-1][t]), h[i][t-1]"""
+    return ([lv.UP[t]] if lv.c_up > 0 else []) + ([lv.Hs[t - 1]] if t > 0 else [])
+
+
+class _Layout(object):
+    """How the node stores the recurrence and which kernels it launches on it.  The node asks a layout for the tensors of that storage
+    (`empty`) and for the launches that differ between formats; everything else -- the diagonals, the heads, the fused upconv tail, the
+    cell state and its gradient (always fp32 NCHW), the parameter-gradient targets -- is the node's."""
+
+    def __init__(self, L, T, B, dev):
+        self.L, self.T, self.B, self.dev = L, T, B, dev
+
+
+class _Nchw(_Layout):
+    """fp32 NCHW storage: -dtype fp32, and -dtype bf16 under RSIS_DECODER_BLK=0 (bf16 operands, the round-3 path).  The hoisted skip
+    terms, the inter-level upsamples and their transposes and the skip data gradients go out one launch per cell or level."""
+    blk = 0                 # the storage flag of rsis_upconv_out_*
+    by_level = True         # the per-level tail of the backward runs one level at a time
+
+    def empty(self, lead, C, H, W):
+        return torch.empty(lead + (C, H, W), dtype=torch.float32, device=self.dev)
+
+    def to_nchw(self, x):
+        return x
+    from_nchw = to_nchw
+
+    def hoist(self, levels, feats, gates_w, gates_b, need_grad):
+        """G_i = W[:, skip channels] * skip_i + b, one launch per level (on a tile of its own when a backward may follow)"""
+        _lib.require_cuda_f32(*feats)
+        for lv, f, w, b in zip(levels, feats, gates_w, gates_b):
+            lv.skip = f
+            wp = lv.hoist.fwd(w, b)
+            check(self.L.rsis_conv2d_fwd(ptr_array([f]), int_array([lv.c_skip]), 1, self.B, lv.H, lv.W, ptr(wp), 4 * lv.hid, 3, 1, 1,
+                                         ptr(lv.hoist.bias_p), None, ptr(lv.G), lv.H, lv.W, ops.FORCE_TILE[0] + (100 if need_grad else 0),
+                                         lv.hoist.dtype, stream()), "rsis_conv2d_fwd(hoist)")
+
+    def gates(self, levels, cells, wps):
+        jobs = (_lib.LstmJob * len(cells))()
+        for j, (i, t) in zip(jobs, cells):
+            lv = levels[i]
+            srcs = _gate_srcs(lv, t)
+            j.nsrc = len(srcs)
+            for k, s in enumerate(srcs):
+                j.src[k], j.Csrc[k] = s.data_ptr(), s.shape[1]
+            (j.B, j.H, j.W, j.Wp, j.bias_packed, j.addend, j.c_prev, j.h_out, j.c_out, j.act_out, j.hid, j.ks, j.pad, j.tile, j.dtype,
+             j.side_key) = (self.B, lv.H, lv.W, wps[i].data_ptr(), None, lv.G.data_ptr(), lv.Cs[t - 1].data_ptr() if t > 0 else None,
+                            lv.Hs[t].data_ptr(), lv.Cs[t].data_ptr(), lv.ACT[t].data_ptr() if lv.ACT is not None else None, lv.hid, 3, 1,
+                            ops.FORCE_TILE[0], lv.dyn.dtype, lv.KEY[t].data_ptr())
+        check(self.L.rsis_convlstm_fwd_batch(jobs, len(cells), stream()), "rsis_convlstm_fwd_batch")
+
+    def up(self, levels, cells):
+        for i, t in cells:
+            if i + 1 < len(levels):
+                lv, nx = levels[i], levels[i + 1]
+                if (nx.H, nx.W) == (lv.H, lv.W):          # align-corners resize to the same size is the identity (ops.upsample_bilinear_ac)
+                    nx.UP[t].copy_(lv.Hs[t])
+                else:
+                    check(self.L.rsis_upsample_bilinear_ac_fwd(ptr(lv.Hs[t]), ptr(nx.UP[t]), self.B * lv.hid, lv.H, lv.W, nx.H, nx.W, stream()),
+                          "rsis_upsample_fwd")
+
+    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads):
+        """the x2 upsample of the last level over all steps, heads() (the launch of the class / stop heads, which each layout issues
+        where it always has), then conv_out: stacked over T where rsis_conv_out_seq_* covers the shape (3 launches instead of 3 T),
+        per step otherwise"""
+        L, T, B = self.L, self.T, self.B
         H5, W5 = 2 * last.H, 2 * last.W
-        upc = _upconv_ok(L, last, H5, W5)
-        UP5 = None if upc else torch.empty((T, B, last.hid, H5, W5), **f32)            # model.py:163-164, all timesteps
-        ncls = Wc.shape[0]
-        probs_tb = torch.empty((T, B, ncls), **f32)
-        stop_tb = torch.empty((T, B, 1), **f32)
-        wps = [lv.dyn.fwd(gates_w[i]) for i, lv in enumerate(levels)]
-        Wc_d, bc_d, Ws_d, bs_d = Wc.detach(), bc.detach(), Ws.detach(), bs.detach()
-
-        for d in range(T + n - 1):
-            cells = [(i, d - i) for i in range(n) if 0 <= d - i < T]
-            jobs = (_lib.LstmJob * len(cells))()
-            for j, (i, t) in zip(jobs, cells):
-                lv = levels[i]
-                srcs = ([lv.UP[t]] if lv.c_up > 0 else []) + ([lv.Hs[t - 1]] if t > 0 else [])
-                j.nsrc = len(srcs)
-                for k, s in enumerate(srcs):
-                    j.src[k], j.Csrc[k] = s.data_ptr(), s.shape[1]
-                (j.B, j.H, j.W, j.Wp, j.bias_packed, j.addend, j.c_prev, j.h_out, j.c_out, j.act_out, j.hid, j.ks, j.pad, j.tile, j.dtype,
-                 j.side_key) = (B, lv.H, lv.W, wps[i].data_ptr(), None, lv.G.data_ptr(), lv.Cs[t - 1].data_ptr() if t > 0 else None,
-                                lv.Hs[t].data_ptr(), lv.Cs[t].data_ptr(), lv.ACT[t].data_ptr() if lv.ACT is not None else None, lv.hid, 3, 1,
-                                ops.FORCE_TILE[0], lv.dyn.dtype, lv.KEY[t].data_ptr())
-            check(L.rsis_convlstm_fwd_batch(jobs, len(cells), stream()), "rsis_convlstm_fwd_batch")
-            for i, t in cells:
-                lv = levels[i]
-                if i + 1 < n:
-                    nx = levels[i + 1]
-                    if (nx.H, nx.W) == (lv.H, lv.W):          # align-corners resize to the same size is the identity (ops.upsample_bilinear_ac)
-                        nx.UP[t].copy_(lv.Hs[t])
-                    else:
-                        check(L.rsis_upsample_bilinear_ac_fwd(ptr(lv.Hs[t]), ptr(nx.UP[t]), B * lv.hid, lv.H, lv.W, nx.H, nx.W, stream()),
-                              "rsis_upsample_fwd")
-                # (the x2 upsample of the last level, model.py:163-164, feeds conv_out only, and the heads only the losses: both run once
-                #  over all T steps after the loop)
-        if not upc:
-            check(L.rsis_upsample_bilinear_ac_fwd(ptr(last.Hs), ptr(UP5), T * B * last.hid, last.H, last.W, H5, W5, stream()), "rsis_upsample_fwd(all steps)")
-        _heads_all_steps(L, levels, hs, n, T * B, Wc_d, bc_d, Ws_d, bs_d, ncls, probs_tb, stop_tb)
-        # conv_out (model.py:167) on every timestep at once, logits straight into (B, T, N)
-        out_masks = torch.empty((B, T, H5 * W5), **f32)
-        co_pack = decoder.conv_out._pack
-        co_wp = None if upc else co_pack.fwd(co_w)
-        seq_ok = _conv_out_seq_ok(last.hid, W5)
-        if upc:       # upsample + conv_out in one pass, the upsampled tensor never formed
-            check(L.rsis_upconv_out_fwd(ptr(last.Hs), 0, ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), T, B, last.hid, last.H, last.W, H5, W5,
-                                        stream()), "rsis_upconv_out_fwd")
-        elif seq_ok:
+        check(L.rsis_upsample_bilinear_ac_fwd(ptr(last.Hs), ptr(UP5), T * B * last.hid, last.H, last.W, H5, W5, stream()), "rsis_upsample_fwd(all steps)")
+        heads()
+        co_pack = conv_out._pack
+        co_wp = co_pack.fwd(co_w)
+        self.seq_ok = last.hid in (4, 8, 16) and W5 % 4 == 0
+        if self.seq_ok:
             check(L.rsis_conv_out_seq_fwd(ptr(UP5), ptr(co_wp), ptr(co_b.detach()), ptr(out_masks), T, B, last.hid, H5, W5, stream()),
                   "rsis_conv_out_seq_fwd")
         else:
-            tmp = torch.empty((B, 1, H5, W5), **f32)
+            tmp = torch.empty((B, 1, H5, W5), dtype=torch.float32, device=self.dev)
             for t in range(T):
                 check(L.rsis_conv2d_fwd(ptr_array([UP5[t]]), int_array([last.hid]), 1, B, H5, W5, ptr(co_wp), 1, 3, 1, 1, ptr(co_b.detach()), None,
                                         ptr(tmp), H5, W5, ops.FORCE_TILE[0], co_pack.dtype, stream()), "rsis_conv2d_fwd(conv_out)")
                 out_masks[:, t].copy_(tmp.view(B, -1))
+
+    def tail_bwd(self, d_masks, last, UP5, dUP5, conv_out, co_w, dW, db):
+        """conv_out's data gradient into dUP5; its weight / bias gradients into the buffers dW() / db() return (None: not wanted)"""
+        L, T, B = self.L, self.T, self.B
+        H5, W5 = 2 * last.H, 2 * last.W
+        co_pack = conv_out._pack
+        co_wd = co_pack.dgrad(co_w)
+        dW = dW() if dW else None
+        db = db() if db else None
+        if self.seq_ok:
+            check(L.rsis_conv_out_seq_dgrad(ptr(d_masks), ptr(co_wd), ptr(dUP5), T, B, last.hid, H5, W5, stream()), "rsis_conv_out_seq_dgrad")
+            if dW is not None:
+                check(L.rsis_conv_out_seq_wgrad(ptr(d_masks), ptr(UP5), ptr(dW), ptr(db), T, B, last.hid, H5, W5, stream()), "rsis_conv_out_seq_wgrad")
+            elif db is not None:
+                db += d_masks.sum()
+            return
+        for t in range(T):
+            dy = d_masks[:, t].contiguous().view(B, 1, H5, W5)
+            check(L.rsis_conv2d_dgrad(ptr(dy), B, 1, H5, W5, ptr(co_wd), co_pack.cin, 3, 1, 1, ptr_array([dUP5[t]]), int_array([last.hid]), 1,
+                                      H5, W5, None, ops.FORCE_TILE[0], co_pack.dtype, stream()), "rsis_conv2d_dgrad(conv_out)")
+            if dW is not None:
+                check(L.rsis_conv2d_wgrad(ptr(dy), ptr(UP5[t]), ptr(dW), B, last.hid, H5, W5, 1, H5, W5, 3, 1, 1, last.hid, 0, 0, co_pack.dtype,
+                                          stream()), "rsis_conv2d_wgrad(conv_out)")
+            if db is not None:
+                check(L.rsis_bias_grad(ptr(dy), ptr(db), B, 1, H5 * W5, 0, stream()), "rsis_bias_grad(conv_out)")
+
+    def up5_bwd(self, dUP5, dside, last, DH_last):
+        check(self.L.rsis_upsample_maxpool_bwd(ptr(dUP5), ptr(dside), ptr(last.ARG), ptr(DH_last), self.T * self.B * last.hid, last.H, last.W,
+                                               2 * last.H, 2 * last.W, stream()), "rsis_upsample_maxpool_bwd(all steps)")
+
+    def up_bwd(self, levels, cells, DUP, DH, dsides):
+        B = self.B
+        for i, t in cells:
+            if i + 1 < len(levels):
+                lv, nx = levels[i], levels[i + 1]
+                if (nx.H, nx.W) == (lv.H, lv.W):
+                    DH[i].copy_(DUP[i + 1])
+                    check(self.L.rsis_global_maxpool_bwd_add(ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(DH[i]), B * lv.hid, lv.H * lv.W, stream()),
+                          "rsis_global_maxpool_bwd_add")
+                else:
+                    check(self.L.rsis_upsample_maxpool_bwd(ptr(DUP[i + 1]), ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(DH[i]), B * lv.hid, lv.H, lv.W,
+                                                           nx.H, nx.W, stream()), "rsis_upsample_maxpool_bwd")
+
+    def lstm_bwd(self, jobs):
+        """the pointwise LSTM backward of one diagonal, jobs (dh, dh2, dc_next, act, c_prev, c, da, dc_prev): one grouped launch"""
+        lb = (_lib.LstmBwdJob * len(jobs))()
+        for j, job in zip(lb, jobs):
+            j.dh, j.dh2, j.dc_next, j.act, j.c_prev, j.c, j.da, j.dc_prev = [ptr(x) for x in job]
+            dh = job[0]
+            j.B, j.hid, j.HW = dh.shape[0], dh.shape[1], dh.shape[2] * dh.shape[3]
+        check(self.L.rsis_convlstm_bwd_gates_batch(lb, len(jobs), stream()), "rsis_convlstm_bwd_gates_batch")
+
+    def dgrad(self, jobs):
+        """the gate convs' data gradients of one diagonal, jobs (dy, packed weights, packed input channels, dtype, [dx, ...]): one
+        grouped launch"""
+        if not jobs:
+            return
+        dg = (_lib.DgradJob * len(jobs))()
+        for j, (dy, wd, cin, dtype, dxs) in zip(dg, jobs):
+            B, Cout, H, W = dy.shape
+            (j.dy, j.B, j.Cout, j.Hy, j.Wy, j.Wd, j.Cin_packed, j.ks, j.stride, j.pad, j.ndst, j.Hx, j.Wx, j.addend, j.tile, j.dtype) = (
+                ptr(dy), B, Cout, H, W, ptr(wd), cin, 3, 1, 1, len(dxs), H, W, None, ops.FORCE_TILE[0], dtype)
+            for k, x in enumerate(dxs):
+                j.dx[k], j.Cdx[k] = x.data_ptr(), x.shape[1]
+        check(self.L.rsis_conv2d_dgrad_batch(dg, len(jobs), stream()), "rsis_conv2d_dgrad_batch")
+
+    def sum_t(self, DA, dG):
+        check(self.L.rsis_sum_leading(ptr(DA), ptr(dG), self.T, dG.numel(), stream()), "rsis_sum_leading")
+
+    def skip_dgrad(self, jobs):
+        """dgrad() of the hoisted skip terms: one launch per level"""
+        for dy, wd, cin, dtype, (dx,) in jobs:
+            B, Cout, H, W = dy.shape
+            check(self.L.rsis_conv2d_dgrad(ptr(dy), B, Cout, H, W, ptr(wd), cin, 3, 1, 1, ptr_array([dx]), int_array([dx.shape[1]]), 1, H, W, None,
+                                           ops.FORCE_TILE[0], dtype, stream()), "rsis_conv2d_dgrad(hoist)")
+
+    def bias_grad(self, dG, db, lv):
+        check(self.L.rsis_bias_grad(ptr(dG), ptr(db), self.B, 4 * lv.hid, lv.H * lv.W, lv.hid, stream()), "rsis_bias_grad(hoist)")
+
+    def wgrad_formats(self, lv):
+        """(dtype of the skip term's weight gradient, dtype of the recurrent channels' time-batched ones, source [T][B] -> their rows).
+        bf16 rows that are not a multiple of 4 pixels (the 7 / 14-pixel levels of a 224 x 224 input) go through channel-blocked bf16
+        copies of the (small) stacks and the whole-cell loader, see decoder_fused._StepFn.backward"""
+        if lv.dyn.dtype == ops.DTYPE_BF16 and decoder_fused._BLK_WGRAD[0] and lv.W % 4 != 0 and lv.hid % 8 == 0 and lv.c_up % 8 == 0:
+            return lv.hoist.dtype, ops.DTYPE_BF16_BLK, lambda x: ops.blk_from_nchw(x.flatten(0, 1))
+        return lv.hoist.dtype, lv.dyn.dtype, lambda x: x.flatten(0, 1)
+
+
+class _Blk(_Layout):
+    """channel-blocked bf16 storage [B][C/8][H][W][8] (csrc/conv_blk_dec.hip, blk_dec.hip) of hidden states, saved gates, up-sampled
+    inputs, the hoisted gate terms and every gradient of them.  Per diagonal ONE grouped launch per kind of work (gate convs, upsamples;
+    backward: upsample transposes, pointwise LSTM backward, data gradients); the hoisted skip terms and their data gradients of all
+    levels in one launch each."""
+    blk = 1
+    by_level = False        # the per-level tail of the backward runs each of its steps over all levels
+
+    def empty(self, lead, C, H, W):
+        return torch.empty(lead + (C // 8, H, W, 8), dtype=torch.bfloat16, device=self.dev)
+
+    def to_nchw(self, x):
+        return ops.blk_to_nchw(x)
+
+    def from_nchw(self, x):
+        return ops.blk_from_nchw(x)
+
+    def hoist(self, levels, feats, gates_w, gates_b, need_grad):
+        jobs = []
+        for lv, f, w, b in zip(levels, feats, gates_w, gates_b):
+            lv.skip = f if _is_blk(f) else ops.blk_from_nchw(f)
+            jobs.append(ops.blk_conv_job([lv.skip], lv.hoist.fwd(w, b), 4 * lv.hid, bias=lv.hoist.bias_p, dsts=[lv.G]))
+        ops.blk_conv3x3_batch(jobs)
+
+    def gates(self, levels, cells, wps):
+        jobs = []
+        for i, t in cells:
+            lv = levels[i]
+            jobs.append(ops.blk_conv_job(_gate_srcs(lv, t), wps[i], 4 * lv.hid, addend=lv.G, hid=lv.hid, c_prev=lv.Cs[t - 1] if t > 0 else None,
+                                         c_out=lv.Cs[t], h_out=lv.Hs[t], act_out=lv.ACT[t] if lv.ACT is not None else None, side_key=lv.KEY[t],
+                                         shape=(self.B, lv.H, lv.W)))
+        ops.blk_conv3x3_batch(jobs)
+
+    def up(self, levels, cells):
+        ups = [ops.blk_resize_job(levels[i].Hs[t], levels[i + 1].UP[t]) for i, t in cells if i + 1 < len(levels)]
+        if ups:
+            ops.blk_upsample_fwd_batch(ups)
+
+    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads):
+        """heads(), then the x2 upsample of the last level and conv_out, each over all steps at once"""
+        heads()
+        ops.blk_upsample_fwd_batch([ops.blk_resize_job(last.Hs.flatten(0, 1), UP5.flatten(0, 1))])
+        check(self.L.rsis_blk_conv_out_seq_fwd(ptr(UP5), ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), self.T, self.B, 2 * last.H,
+                                               2 * last.W, stream()), "rsis_blk_conv_out_seq_fwd")
+
+    def tail_bwd(self, d_masks, last, UP5, dUP5, conv_out, co_w, dW, db):
+        L, T, B = self.L, self.T, self.B
+        H5, W5 = 2 * last.H, 2 * last.W
+        check(L.rsis_blk_conv_out_seq_dgrad(ptr(d_masks), ptr(co_w.detach()), ptr(dUP5), T, B, H5, W5, stream()), "rsis_blk_conv_out_seq_dgrad")
+        if dW or db:
+            dW = dW() if dW else torch.zeros_like(co_w)
+            db = db() if db else None
+            check(L.rsis_blk_conv_out_seq_wgrad(ptr(d_masks), ptr(UP5), ptr(dW), ptr(db), T, B, H5, W5, stream()), "rsis_blk_conv_out_seq_wgrad")
+
+    def up5_bwd(self, dUP5, dside, last, DH_last):
+        ops.blk_upsample_bwd_batch([ops.blk_resize_job(dUP5.flatten(0, 1), DH_last.flatten(0, 1), dside, last.ARG, backward=True)])
+
+    def up_bwd(self, levels, cells, DUP, DH, dsides):
+        ups = [ops.blk_resize_job(DUP[i + 1], DH[i], dsides[i][t], levels[i].ARG[t], backward=True) for i, t in cells if i + 1 < len(levels)]
+        if ups:
+            ops.blk_upsample_bwd_batch(ups)
+
+    def lstm_bwd(self, jobs):
+        ops.blk_lstm_bwd_batch([ops.blk_lstm_bwd_job(*job) for job in jobs])
+
+    def dgrad(self, jobs):
+        if jobs:
+            ops.blk_conv3x3_batch([ops.blk_conv_job([dy], wd, sum(x.shape[1] for x in dxs) * 8, cpack=cin, dsts=dxs) for dy, wd, cin, _dt, dxs in jobs])
+
+    def sum_t(self, DA, dG):
+        check(self.L.rsis_blk_sum_leading(ptr(DA), ptr(dG), self.T, dG.numel() // 8, stream()), "rsis_blk_sum_leading")
+
+    skip_dgrad = dgrad      # (the skip data gradients of all levels: one grouped launch)
+
+    def bias_grad(self, dG, db, lv):
+        check(self.L.rsis_blk_bias_grad(ptr(dG), ptr(db), self.B, 4 * lv.hid, lv.H * lv.W, lv.hid, stream()), "rsis_blk_bias_grad")
+
+    def wgrad_formats(self, lv):
+        return ops.DTYPE_BF16_BLK, ops.DTYPE_BF16_BLK, lambda x: x.flatten(0, 1)
+
+
+class _DecoderSeqFn(torch.autograd.Function):
+    """the schedule of the module docstring, on the storage of `layout` (_Nchw or _Blk)"""
+
+    @staticmethod
+    def forward(ctx, layout, decoder, T, keep, want_hidden, *tensors):
+        L = lib()
+        n = len(decoder.clstm_list)
+        feats = [t.contiguous() for t in tensors[:n]]      # fp32 NCHW, or already blk (the encoder's blk skip path)
+        params = tensors[n:]
+        gates_w, gates_b = params[0:2 * n:2], params[1:2 * n:2]
+        co_w, co_b, Wc, bc, Ws, bs = params[2 * n:2 * n + 6]
+        _lib.require_cuda_f32(*params)
+        need_grad = bool(keep) and any(ctx.needs_input_grad)     # (grad mode is off inside forward: the caller says whether a backward may follow)
+        dev = feats[0].device
+        B = feats[0].shape[0]
+        lay = layout(L, T, B, dev)
+        hs = [c.hidden_size for c in decoder.clstm_list]
+        tot = sum(hs)
+        f32 = dict(dtype=torch.float32, device=dev)
+        # one zeroed key buffer for the side max-pools of the whole sequence (rsis_lstm_job.side_key), decoded by the heads launch
+        KEY = torch.zeros(T * B * tot, dtype=torch.int64, device=dev)
+        SIDE = torch.empty(T * B * tot, **f32)
+        ARG = torch.empty(T * B * tot, dtype=torch.int32, device=dev)
+        levels = []
+        for i, cell in enumerate(decoder.clstm_list):
+            lv = _Level()
+            lv.cell, lv.hid, lv.c_up, lv.c_skip = cell, hs[i], (0 if i == 0 else hs[i - 1]), _chan(feats[i])
+            lv.H, lv.W = feats[i].shape[2], feats[i].shape[3]
+            lv.hoist, lv.dyn = decoder_fused._packs(cell, lv.c_up, lv.c_skip)
+            lv.G = lay.empty((B,), 4 * lv.hid, lv.H, lv.W)
+            lv.Hs = lay.empty((T, B), lv.hid, lv.H, lv.W)
+            lv.Cs = torch.empty((T, B, lv.hid, lv.H, lv.W), **f32)
+            lv.ACT = lay.empty((T, B), 4 * lv.hid, lv.H, lv.W) if need_grad else None
+            lv.UP = lay.empty((T, B), lv.c_up, lv.H, lv.W) if lv.c_up > 0 else None
+            levels.append(lv)
+        for lv, key, side, arg in zip(levels, _per_level(KEY, hs, T, B), _per_level(SIDE, hs, T, B), _per_level(ARG, hs, T, B)):
+            lv.KEY, lv.SIDE, lv.ARG = key, side, arg
+        # G_i = W[:, skip channels] * skip_i + b, once per iteration (the skip features do not depend on t)
+        lay.hoist(levels, feats, gates_w, gates_b, need_grad)
+        last = levels[-1]
+        H5, W5 = 2 * last.H, 2 * last.W
+        upc = UPCONV[0] and L.rsis_upconv_out_supported(last.hid, last.H, last.W, H5, W5) == 1
+        UP5 = None if upc else lay.empty((T, B), last.hid, H5, W5)            # model.py:163-164, all timesteps
+        probs_tb = torch.empty((T, B, Wc.shape[0]), **f32)
+        stop_tb = torch.empty((T, B, 1), **f32)
+        wps = [lv.dyn.fwd(w) for lv, w in zip(levels, gates_w)]
+        for d in range(T + n - 1):
+            cells = _diagonal(d, n, T)
+            lay.gates(levels, cells, wps)
+            lay.up(levels, cells)
+            # (the x2 upsample of the last level, model.py:163-164, feeds conv_out only, and the heads only the losses: both run once
+            #  over all T steps after the loop)
+
+        def heads():
+            """the class / stop heads (model.py:169-182) of ALL timesteps in one launch: every (t, b) row is independent, the per-level
+            key / feature / arg-max arrays are [T][B][hid] contiguous, i.e. T * B rows; the launch decodes the pooled keys (writes SIDE / ARG)"""
+            check(L.rsis_heads_fwd_keys(ptr_array([v.KEY for v in levels]), ptr_array([v.SIDE for v in levels]), ptr_array([v.ARG for v in levels]),
+                                        int_array(hs), n, T * B, ptr(Wc.detach()), ptr(bc.detach()), Wc.shape[0], ptr(Ws.detach()), ptr(bs.detach()),
+                                        ptr(probs_tb), ptr(stop_tb), stream()), "rsis_heads_fwd_keys(all steps)")
+        # conv_out (model.py:167) on every timestep at once, logits straight into (B, T, N)
+        out_masks = torch.empty((B, T, H5 * W5), **f32)
+        if upc:       # upsample + conv_out in one pass, the upsampled tensor never formed (nor rounded to bf16)
+            heads()
+            check(L.rsis_upconv_out_fwd(ptr(last.Hs), lay.blk, ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), T, B, last.hid, last.H, last.W,
+                                        H5, W5, stream()), "rsis_upconv_out_fwd")
+        else:
+            lay.tail(last, UP5, decoder.conv_out, co_w, co_b, out_masks, heads)
         out_probs = probs_tb.transpose(0, 1).contiguous()            # (B, T, C)   train.py:119
         out_stops = stop_tb.transpose(0, 1).contiguous()             # (B, T, 1)   train.py:120
         hidden = []
-        for lv in levels:
-            hidden += [lv.Hs[T - 1], lv.Cs[T - 1]]
+        if want_hidden:
+            for lv in levels:
+                hidden += [lay.to_nchw(lv.Hs[T - 1]), lv.Cs[T - 1]]
         if RECORD[0]:
             LAST["arg"] = [lv.ARG.clone() for lv in levels]
         ctx.set_materialize_grads(False)
         if need_grad:
-            ctx.decoder, ctx.T, ctx.levels, ctx.seq_ok, ctx.upc = decoder, T, levels, seq_ok, upc
-            ctx.UP5, ctx.probs_tb, ctx.feats = UP5, probs_tb, feats
-            ctx.params = params
+            ctx.lay, ctx.decoder, ctx.T, ctx.levels, ctx.upc = lay, decoder, T, levels, upc
+            ctx.UP5, ctx.probs_tb, ctx.feats, ctx.params = UP5, probs_tb, feats, params
         else:
             for lv in levels:
-                lv.G = lv.ACT = lv.UP = None
+                lv.G = lv.ACT = lv.UP = lv.skip = None
         return (out_masks, out_probs, out_stops) + tuple(hidden)
 
     @staticmethod
     def backward(ctx, d_masks, d_probs, d_stops, *d_hidden):
         L = lib()
-        decoder, T, levels = ctx.decoder, ctx.T, ctx.levels
+        lay, decoder, T, levels = ctx.lay, ctx.decoder, ctx.T, ctx.levels
         n = len(levels)
         feats, params = ctx.feats, ctx.params
-        gates_w = [params[2 * i] for i in range(n)]
-        gates_b = [params[2 * i + 1] for i in range(n)]
+        gates_w = params[0:2 * n:2]
         co_w, co_b, Wc, bc, Ws, bs = params[2 * n:2 * n + 6]
-        need = ctx.needs_input_grad            # (decoder, T, keep, feats..., params...)
-        need_feat = [need[3 + i] for i in range(n)]
-        need_par = [need[3 + n + k] for k in range(len(params))]
+        need = ctx.needs_input_grad            # (layout, decoder, T, keep, want_hidden, feats..., params...)
+        need_feat = [need[5 + i] for i in range(n)]
+        need_par = [need[5 + n + k] for k in range(len(params))]
         dev = feats[0].device
         B = feats[0].shape[0]
         hs = [lv.hid for lv in levels]
@@ -287,49 +513,21 @@ class _DecoderSeqFn(torch.autograd.Function):
             grads_par[k] = g
             return g, False
 
-        # ---- conv_out: data gradient of all T steps in one launch, weight + bias gradient in another ----
+        # ---- conv_out: data gradient of all T steps, weight + bias gradient ----
         upc = ctx.upc
         dUP5 = None if upc else torch.empty_like(UP5)
-        co_pack = decoder.conv_out._pack
+        kw, kb = 2 * n, 2 * n + 1
         have_masks = d_masks is not None       # (no gradient on the logits: conv_out's parameters get none either, as on the unfused path)
         if upc:         # (the whole tail runs below, once the side gradients of the heads are known)
-            d_masks = torch.zeros((B, T, H5 * W5), **f32) if d_masks is None else (d_masks if d_masks.is_contiguous() else d_masks.contiguous())
+            d_masks = torch.zeros((B, T, H5 * W5), **f32) if d_masks is None else d_masks.contiguous()
         elif d_masks is None:
             dUP5.zero_()
         else:
-            d_masks = d_masks if d_masks.is_contiguous() else d_masks.contiguous()
-            co_wd = co_pack.dgrad(co_w)
-            kw, kb = 2 * n, 2 * n + 1
-            dW = db = None
-            if need_par[kw]:
-                dW, _ = target(kw)
-            if need_par[kb]:
-                db, _ = target(kb)
-            if ctx.seq_ok:
-                check(L.rsis_conv_out_seq_dgrad(ptr(d_masks), ptr(co_wd), ptr(dUP5), T, B, last.hid, H5, W5, stream()), "rsis_conv_out_seq_dgrad")
-                if dW is not None:
-                    check(L.rsis_conv_out_seq_wgrad(ptr(d_masks), ptr(UP5), ptr(dW), ptr(db), T, B, last.hid, H5, W5, stream()),
-                          "rsis_conv_out_seq_wgrad")
-                elif db is not None:
-                    db += d_masks.sum()
-            else:
-                for t in range(T):
-                    dy = d_masks[:, t].contiguous().view(B, 1, H5, W5)
-                    check(L.rsis_conv2d_dgrad(ptr(dy), B, 1, H5, W5, ptr(co_wd), co_pack.cin, 3, 1, 1, ptr_array([dUP5[t]]), int_array([last.hid]), 1,
-                                              H5, W5, None, ops.FORCE_TILE[0], co_pack.dtype, stream()), "rsis_conv2d_dgrad(conv_out)")
-                    if dW is not None:
-                        check(L.rsis_conv2d_wgrad(ptr(dy), ptr(UP5[t]), ptr(dW), B, last.hid, H5, W5, 1, H5, W5, 3, 1, 1, last.hid, 0, 0,
-                                                  co_pack.dtype, stream()), "rsis_conv2d_wgrad(conv_out)")
-                    if db is not None:
-                        check(L.rsis_bias_grad(ptr(dy), ptr(db), B, 1, H5 * W5, 0, stream()), "rsis_bias_grad(conv_out)")
-        # ---- heads: per timestep (the parameter gradients accumulate over t) ----
-        tot = sum(hs)
-        DSIDE = torch.empty(T * B * tot, **f32)
-        dsides, off = [], 0
-        for lv in levels:
-            m = T * B * lv.hid
-            dsides.append(DSIDE[off:off + m].view(T, B, lv.hid))
-            off += m
+            lay.tail_bwd(d_masks.contiguous(), last, UP5, dUP5, decoder.conv_out, co_w, (lambda: target(kw)[0]) if need_par[kw] else None,
+                         (lambda: target(kb)[0]) if need_par[kb] else None)
+        # ---- heads: all timesteps (the parameter gradients accumulate over t) ----
+        DSIDE = torch.empty(T * B * sum(hs), **f32)
+        dsides = _per_level(DSIDE, hs, T, B)
         if d_probs is None and d_stops is None:
             DSIDE.zero_()
         else:
@@ -339,363 +537,86 @@ class _DecoderSeqFn(torch.autograd.Function):
             _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, ctx.probs_tb, dp_tb, ds_tb, dsides, hb)
         # ---- reverse wavefront ----
         DA = [torch.empty_like(lv.ACT) for lv in levels]
-        DH = [torch.empty((B, lv.hid, lv.H, lv.W), **f32) for lv in levels]                  # gradient of h[i][t] from above (upsample + pool)
-        DHP = [torch.empty((B, lv.hid, lv.H, lv.W), **f32) for lv in levels]                 # ... through the recurrence, from step t + 1
+        DH = [lay.empty((B,), lv.hid, lv.H, lv.W) for lv in levels]                  # gradient of h[i][t] from above (upsample + pool)
+        DHP = [lay.empty((B,), lv.hid, lv.H, lv.W) for lv in levels]                 # ... through the recurrence, from step t + 1
         DC = [[torch.empty((B, lv.hid, lv.H, lv.W), **f32) for _ in range(2)] for lv in levels]
-        DUP = [torch.empty((B, lv.c_up, lv.H, lv.W), **f32) if lv.c_up > 0 else None for lv in levels]
+        DUP = [lay.empty((B,), lv.c_up, lv.H, lv.W) if lv.c_up > 0 else None for lv in levels]
         dpk = [decoder_fused.dyn_dgrad_pack(lv.cell, lv.c_up, lv.c_skip, lv.H, lv.W) for lv in levels]
-        wds = [dpk[i].dgrad(gates_w[i]) for i, lv in enumerate(levels)]
+        wds = [pk.dgrad(w) for pk, w in zip(dpk, gates_w)]
+        # gradients a caller put on the returned final state (none in runIter: train.py never reads it)
+        d_hidden = d_hidden or (None,) * (2 * n)
+        dhf = [lay.from_nchw(g.contiguous()) if g is not None else None for g in d_hidden[0::2]]
+        dcf = [g.contiguous() if g is not None else None for g in d_hidden[1::2]]
         # the last level's hidden states receive their gradient from conv_out only (no level above): all T steps in one launch
-        DH_last = torch.empty((T, B, last.hid, last.H, last.W), **f32)
-        if upc:
-            kw, kb = 2 * n, 2 * n + 1
-            _upconv_bwd(L, d_masks, last, False, co_w, target(kw)[0] if need_par[kw] and have_masks else None,
-                        target(kb)[0] if need_par[kb] and have_masks else None, dsides[n - 1],
-                        T, B, H5, W5, DH_last)
+        DH_last = lay.empty((T, B), last.hid, last.H, last.W)
+        if upc:         # through conv_out and the upsample (plus the side max-pool gradient at its arg-max pixel); dW / db accumulate
+            dW = target(kw)[0] if need_par[kw] and have_masks else None        # (fixed-order sums of per-block partials)
+            db = target(kb)[0] if need_par[kb] and have_masks else None
+            partial = torch.empty(L.rsis_upconv_out_bwd_blocks(T, B, last.H, last.W) * 80, **f32)
+            check(L.rsis_upconv_out_bwd(ptr(d_masks), ptr(last.Hs), lay.blk, ptr(co_w.detach()), ptr(DH_last), ptr(dW), ptr(db), ptr(dsides[n - 1]),
+                                        ptr(last.ARG), ptr(partial), T, B, last.hid, last.H, last.W, H5, W5, stream()), "rsis_upconv_out_bwd")
         else:
-            check(L.rsis_upsample_maxpool_bwd(ptr(dUP5), ptr(dsides[n - 1]), ptr(last.ARG), ptr(DH_last), T * B * last.hid, last.H, last.W, H5, W5,
-                                              stream()), "rsis_upsample_maxpool_bwd(all steps)")
+            lay.up5_bwd(dUP5, dsides[n - 1], last, DH_last)
         for d in range(T + n - 2, -1, -1):
-            cells = [(i, d - i) for i in range(n) if 0 <= d - i < T]
-            for i, t in cells:          # gradient reaching h[i][t] through its upsample into the next level and its side max-pool
-                lv = levels[i]
-                if i + 1 == n:
-                    continue
-                nx = levels[i + 1]
-                dy, Ho, Wo = DUP[i + 1], nx.H, nx.W
-                if (Ho, Wo) == (lv.H, lv.W):
-                    DH[i].copy_(dy)
-                    check(L.rsis_global_maxpool_bwd_add(ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(DH[i]), B * lv.hid, lv.H * lv.W, stream()),
-                          "rsis_global_maxpool_bwd_add")
-                else:
-                    check(L.rsis_upsample_maxpool_bwd(ptr(dy), ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(DH[i]), B * lv.hid, lv.H, lv.W, Ho, Wo,
-                                                      stream()), "rsis_upsample_maxpool_bwd")
-            # clstm.py:47-58 backwards: d(gates), dc_{t-1} of the diagonal's cells -- ONE grouped launch
-            lb = (_lib.LstmBwdJob * len(cells))()
-            keep = []
-            for j, (i, t) in zip(lb, cells):
-                lv = levels[i]
-                if t == T - 1:      # gradients a caller put on the returned final state (none in runIter: train.py never reads it)
-                    dh2 = d_hidden[2 * i].contiguous() if d_hidden[2 * i] is not None else None
-                    dcn = d_hidden[2 * i + 1].contiguous() if d_hidden[2 * i + 1] is not None else None
-                    keep += [dh2, dcn]
-                else:
-                    dh2, dcn = DHP[i], DC[i][(t + 1) & 1]
-                dh = DH_last[t] if i + 1 == n else DH[i]
-                (j.dh, j.dh2, j.dc_next, j.act, j.c_prev, j.c, j.da, j.dc_prev, j.B, j.hid, j.HW) = (
-                    ptr(dh), ptr(dh2), ptr(dcn), ptr(lv.ACT[t]), ptr(lv.Cs[t - 1]) if t > 0 else None, ptr(lv.Cs[t]), ptr(DA[i][t]),
-                    ptr(DC[i][t & 1]) if t > 0 else None, B, lv.hid, lv.H * lv.W)
-            check(L.rsis_convlstm_bwd_gates_batch(lb, len(cells), stream()), "rsis_convlstm_bwd_gates_batch")
-            # data gradients of the gate convs: d(up[i][t]) for the level below, dh[i][t-1] through the recurrence -- ONE grouped launch
-            dgc = [(i, t) for i, t in cells if levels[i].c_up > 0 or t > 0]
-            if dgc:
-                dg = (_lib.DgradJob * len(dgc))()
-                for j, (i, t) in zip(dg, dgc):
-                    lv = levels[i]
-                    dxs = ([DUP[i]] if lv.c_up > 0 else []) + ([DHP[i]] if t > 0 else [])
-                    (j.dy, j.B, j.Cout, j.Hy, j.Wy, j.Wd, j.Cin_packed, j.ks, j.stride, j.pad, j.ndst, j.Hx, j.Wx, j.addend, j.tile, j.dtype) = (
-                        ptr(DA[i][t]), B, 4 * lv.hid, lv.H, lv.W, ptr(wds[i]), lv.dyn.cin, 3, 1, 1, len(dxs), lv.H, lv.W, None, ops.FORCE_TILE[0],
-                        dpk[i].dtype)
-                    for k, x in enumerate(dxs):
-                        j.dx[k], j.Cdx[k] = x.data_ptr(), x.shape[1]
-                check(L.rsis_conv2d_dgrad_batch(dg, len(dgc), stream()), "rsis_conv2d_dgrad_batch")
-        # ---- per level, once: the time-invariant skip term and the time-batched weight gradients ----
-        dfeats = [None] * n
-        for i, lv in enumerate(levels):
-            kw, kb = 2 * i, 2 * i + 1
-            hid, H, W = lv.hid, lv.H, lv.W
-            if T == 1:
-                dG = DA[i][0]
-            else:
-                dG = torch.empty_like(lv.G)
-                check(L.rsis_sum_leading(ptr(DA[i]), ptr(dG), T, dG.numel(), stream()), "rsis_sum_leading")
-            if need_feat[i]:
-                dfeats[i] = torch.empty_like(feats[i])
-                check(L.rsis_conv2d_dgrad(ptr(dG), B, 4 * hid, H, W, ptr(lv.hoist.dgrad(gates_w[i])), lv.hoist.cin, 3, 1, 1, ptr_array([dfeats[i]]),
-                                          int_array([lv.c_skip]), 1, H, W, None, ops.FORCE_TILE[0], lv.hoist.dtype, stream()), "rsis_conv2d_dgrad(hoist)")
-            if need_par[kb]:
-                db, _ = target(kb)
-                check(L.rsis_bias_grad(ptr(dG), ptr(db), B, 4 * hid, H * W, hid, stream()), "rsis_bias_grad(hoist)")
-            if need_par[kw]:
-                dW, direct = target(kw)
-                Ctot = gates_w[i].shape[1]
-                h_off = lv.c_up + lv.c_skip
-                ops.wgrad_launch(L, dG, feats[i], dW, B, lv.c_skip, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up, hid, lv.hoist.dtype,
-                                 "rsis_conv2d_wgrad(hoist)", direct)
-                dt = lv.dyn.dtype
-                # bf16, rows that are not a multiple of 4 pixels (the 7 / 14-pixel levels of a 224 x 224 input): channel-blocked bf16 copies
-                # of the (small) stacks and the whole-cell loader, see decoder_fused._StepFn.backward
-                as_blk = (dt == ops.DTYPE_BF16 and decoder_fused._BLK_WGRAD[0] and W % 4 != 0 and hid % 8 == 0 and lv.c_up % 8 == 0)
-                if as_blk:
-                    da_b = ops.blk_from_nchw(DA[i].view(T * B, 4 * hid, H, W))
-                    if lv.c_up > 0:
-                        ops.wgrad_launch(L, da_b, ops.blk_from_nchw(lv.UP.view(T * B, lv.c_up, H, W)), dW, T * B, lv.c_up, H, W, 4 * hid, H, W, 3, 1, 1,
-                                         Ctot, 0, hid, ops.DTYPE_BF16_BLK, "rsis_conv2d_wgrad(batched up, blk)", direct)
-                    if T > 1:
-                        ops.wgrad_launch(L, da_b[B:], ops.blk_from_nchw(lv.Hs[:T - 1].reshape((T - 1) * B, hid, H, W)), dW, (T - 1) * B, hid, H, W,
-                                         4 * hid, H, W, 3, 1, 1, Ctot, h_off, hid, ops.DTYPE_BF16_BLK, "rsis_conv2d_wgrad(batched h, blk)", direct)
-                else:
-                    if lv.c_up > 0:
-                        ops.wgrad_launch(L, DA[i], lv.UP, dW, T * B, lv.c_up, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, 0, hid, dt,
-                                         "rsis_conv2d_wgrad(batched up)", direct)
-                    if T > 1:
-                        ops.wgrad_launch(L, DA[i][1], lv.Hs, dW, (T - 1) * B, hid, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, h_off, hid, dt,
-                                         "rsis_conv2d_wgrad(batched h)", direct)
-        for lv in levels:
-            lv.G = lv.Hs = lv.Cs = lv.ACT = lv.UP = None
-        ctx.levels = ctx.UP5 = ctx.feats = ctx.params = ctx.decoder = None
-        return (None, None, None) + tuple(dfeats) + tuple(grads_par)
-
-
-# RSIS_DECODER_BLK=0: keep fp32 NCHW storage in the decoder under -dtype bf16 (bf16 operands only, the round-3 path)
-BLK_ENABLED = [os.environ.get("RSIS_DECODER_BLK", "1") != "0"]
-
-
-def blk_supported(decoder, skip_feats):
-    """the decoder's storage half of `-dtype bf16`: every tensor of the recurrence as channel-blocked bf16 (csrc/conv_blk_dec.hip,
-    blk_dec.hip) -- needs bf16 cells, whole 8-channel cells at every level and the 8-channel conv_out (hidden_size % 128 == 0)"""
-    if not BLK_ENABLED[0]:
-        return False
-    hs = [c.hidden_size for c in decoder.clstm_list]
-    if not all(getattr(c, "dtype", ops.DTYPE_F32) == ops.DTYPE_BF16 for c in decoder.clstm_list):
-        return False
-    if any(h % 8 for h in hs) or any(_chan(f) % 8 for f in skip_feats) or hs[-1] != 8:
-        return False
-    return (2 * skip_feats[-1].shape[3]) % 4 == 0
-
-
-class _DecoderSeqBlkFn(torch.autograd.Function):
-    """_DecoderSeqFn with every tensor of the recurrence stored channel-blocked bf16: hidden states, saved gates, up-sampled inputs,
-    the hoisted gate terms and every gradient of them; the cell state and its gradient stay fp32.  Per diagonal ONE grouped launch
-    per kind of work (gate convs, upsamples; backward: upsample transposes, pointwise LSTM backward, data gradients)."""
-
-    @staticmethod
-    def forward(ctx, decoder, T, keep, want_hidden, *tensors):
-        L = lib()
-        n = len(decoder.clstm_list)
-        feats = [t if t.is_contiguous() else t.contiguous() for t in tensors[:n]]      # fp32 NCHW, or already blk (the encoder's blk skip path)
-        params = tensors[n:]
-        gates_w = [params[2 * i] for i in range(n)]
-        gates_b = [params[2 * i + 1] for i in range(n)]
-        co_w, co_b, Wc, bc, Ws, bs = params[2 * n:2 * n + 6]
-        _lib.require_cuda_f32(*[f for f in feats if not _is_blk(f)], *params)
-        need_grad = bool(keep) and any(ctx.needs_input_grad)
-        dev = feats[0].device
-        B = feats[0].shape[0]
-        hs = [c.hidden_size for c in decoder.clstm_list]
-        tot = sum(hs)
-        f32 = dict(dtype=torch.float32, device=dev)
-        b16 = dict(dtype=torch.bfloat16, device=dev)
-        KEY = torch.zeros(T * B * tot, dtype=torch.int64, device=dev)
-        SIDE = torch.empty(T * B * tot, **f32)
-        ARG = torch.empty(T * B * tot, dtype=torch.int32, device=dev)
-        levels, off, hoist_jobs = [], 0, []
-        for i, cell in enumerate(decoder.clstm_list):
-            lv = _Level()
-            lv.cell, lv.hid, lv.c_up, lv.c_skip = cell, hs[i], (0 if i == 0 else hs[i - 1]), _chan(feats[i])
-            lv.H, lv.W = feats[i].shape[2], feats[i].shape[3]
-            lv.hoist, lv.dyn = decoder_fused._packs(cell, lv.c_up, lv.c_skip)
-            lv.skip = feats[i] if _is_blk(feats[i]) else ops.blk_from_nchw(feats[i])
-            lv.G = torch.empty((B, 4 * lv.hid // 8, lv.H, lv.W, 8), **b16)
-            hoist_jobs.append(ops.blk_conv_job([lv.skip], lv.hoist.fwd(gates_w[i], gates_b[i]), 4 * lv.hid, bias=lv.hoist.bias_p, dsts=[lv.G]))
-            lv.Hs = torch.empty((T, B, lv.hid // 8, lv.H, lv.W, 8), **b16)
-            lv.Cs = torch.empty((T, B, lv.hid, lv.H, lv.W), **f32)
-            lv.ACT = torch.empty((T, B, 4 * lv.hid // 8, lv.H, lv.W, 8), **b16) if need_grad else None
-            lv.UP = torch.empty((T, B, lv.c_up // 8, lv.H, lv.W, 8), **b16) if lv.c_up > 0 else None
-            m = T * B * lv.hid
-            lv.KEY, lv.SIDE, lv.ARG = KEY[off:off + m].view(T, B, lv.hid), SIDE[off:off + m].view(T, B, lv.hid), ARG[off:off + m].view(T, B, lv.hid)
-            off += m
-            levels.append(lv)
-        ops.blk_conv3x3_batch(hoist_jobs)          # G_i = W[:, skip channels] * skip_i + b of all five levels: one grouped launch
-        last = levels[-1]
-        H5, W5 = 2 * last.H, 2 * last.W
-        upc = _upconv_ok(L, last, H5, W5)
-        UP5 = None if upc else torch.empty((T, B, 1, H5, W5, 8), **b16)
-        ncls = Wc.shape[0]
-        probs_tb = torch.empty((T, B, ncls), **f32)
-        stop_tb = torch.empty((T, B, 1), **f32)
-        wps = [lv.dyn.fwd(gates_w[i]) for i, lv in enumerate(levels)]
-        Wc_d, bc_d, Ws_d, bs_d = Wc.detach(), bc.detach(), Ws.detach(), bs.detach()
-        for d in range(T + n - 1):
-            cells = [(i, d - i) for i in range(n) if 0 <= d - i < T]
-            jobs, ups = [], []
+            cells = _diagonal(d, n, T)
+            # gradient reaching h[i][t] through its upsample into the next level and its side max-pool
+            lay.up_bwd(levels, cells, DUP, DH, dsides)
+            lstm, dg = [], []
             for i, t in cells:
                 lv = levels[i]
-                srcs = ([lv.UP[t]] if lv.c_up > 0 else []) + ([lv.Hs[t - 1]] if t > 0 else [])
-                jobs.append(ops.blk_conv_job(srcs, wps[i], 4 * lv.hid, addend=lv.G, hid=lv.hid, c_prev=lv.Cs[t - 1] if t > 0 else None, c_out=lv.Cs[t],
-                                             h_out=lv.Hs[t], act_out=lv.ACT[t] if lv.ACT is not None else None, side_key=lv.KEY[t],
-                                             shape=(B, lv.H, lv.W)))
-                if i + 1 < n:        # (the last level's x2 upsample feeds conv_out only: all T steps in one launch after the loop)
-                    ups.append(ops.blk_resize_job(lv.Hs[t], levels[i + 1].UP[t]))
-            ops.blk_conv3x3_batch(jobs)
-            if ups:
-                ops.blk_upsample_fwd_batch(ups)
-        _heads_all_steps(L, levels, hs, n, T * B, Wc_d, bc_d, Ws_d, bs_d, ncls, probs_tb, stop_tb)
-        out_masks = torch.empty((B, T, H5 * W5), **f32)
-        if upc:       # upsample + conv_out in one pass, the upsampled tensor never formed (nor rounded to bf16)
-            check(L.rsis_upconv_out_fwd(ptr(last.Hs), 1, ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), T, B, last.hid, last.H, last.W, H5, W5,
-                                        stream()), "rsis_upconv_out_fwd")
-        else:
-            ops.blk_upsample_fwd_batch([ops.blk_resize_job(last.Hs.view(T * B, last.hid // 8, last.H, last.W, 8), UP5.view(T * B, 1, H5, W5, 8))])
-            check(L.rsis_blk_conv_out_seq_fwd(ptr(UP5), ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), T, B, H5, W5, stream()),
-                  "rsis_blk_conv_out_seq_fwd")
-        out_probs = probs_tb.transpose(0, 1).contiguous()
-        out_stops = stop_tb.transpose(0, 1).contiguous()
-        hidden = []
-        if want_hidden:
-            for lv in levels:
-                hidden += [ops.blk_to_nchw(lv.Hs[T - 1]), lv.Cs[T - 1]]
-        if RECORD[0]:
-            LAST["arg"] = [lv.ARG.clone() for lv in levels]
-        ctx.set_materialize_grads(False)
-        if need_grad:
-            ctx.decoder, ctx.T, ctx.levels = decoder, T, levels
-            ctx.UP5, ctx.probs_tb, ctx.feats, ctx.params, ctx.upc = UP5, probs_tb, feats, params, upc
-        else:
-            for lv in levels:
-                lv.G = lv.ACT = lv.UP = lv.skip = None
-        return (out_masks, out_probs, out_stops) + tuple(hidden)
-
-    @staticmethod
-    def backward(ctx, d_masks, d_probs, d_stops, *d_hidden):
-        L = lib()
-        decoder, T, levels = ctx.decoder, ctx.T, ctx.levels
-        n = len(levels)
-        feats, params = ctx.feats, ctx.params
-        gates_w = [params[2 * i] for i in range(n)]
-        co_w, co_b, Wc, bc, Ws, bs = params[2 * n:2 * n + 6]
-        need = ctx.needs_input_grad            # (decoder, T, keep, want_hidden, feats..., params...)
-        need_feat = [need[4 + i] for i in range(n)]
-        need_par = [need[4 + n + k] for k in range(len(params))]
-        dev = feats[0].device
-        B = feats[0].shape[0]
-        hs = [lv.hid for lv in levels]
-        f32 = dict(dtype=torch.float32, device=dev)
-        b16 = dict(dtype=torch.bfloat16, device=dev)
-        last = levels[-1]
-        H5, W5 = 2 * last.H, 2 * last.W
-        UP5 = ctx.UP5
-        grads_par = [None] * len(params)
-
-        def target(k):
-            p = params[k]
-            t = ops._direct_target(p)
-            if t is not None:
-                return t, True
-            g = torch.zeros_like(p)
-            grads_par[k] = g
-            return g, False
-
-        upc = ctx.upc
-        dUP5 = None if upc else torch.empty_like(UP5)
-        kw, kb = 2 * n, 2 * n + 1
-        have_masks = d_masks is not None       # (no gradient on the logits: conv_out's parameters get none either, as on the unfused path)
-        if upc:         # (the whole tail runs below, once the side gradients of the heads are known)
-            d_masks = torch.zeros((B, T, H5 * W5), **f32) if d_masks is None else (d_masks if d_masks.is_contiguous() else d_masks.contiguous())
-        elif d_masks is None:
-            dUP5.zero_()
-        else:
-            d_masks = d_masks if d_masks.is_contiguous() else d_masks.contiguous()
-            check(L.rsis_blk_conv_out_seq_dgrad(ptr(d_masks), ptr(co_w.detach()), ptr(dUP5), T, B, H5, W5, stream()), "rsis_blk_conv_out_seq_dgrad")
-            if need_par[kw] or need_par[kb]:
-                dW = target(kw)[0] if need_par[kw] else torch.zeros_like(co_w)
-                db = target(kb)[0] if need_par[kb] else None
-                check(L.rsis_blk_conv_out_seq_wgrad(ptr(d_masks), ptr(UP5), ptr(dW), ptr(db), T, B, H5, W5, stream()), "rsis_blk_conv_out_seq_wgrad")
-        tot = sum(hs)
-        DSIDE = torch.empty(T * B * tot, **f32)
-        dsides, off = [], 0
-        for lv in levels:
-            m = T * B * lv.hid
-            dsides.append(DSIDE[off:off + m].view(T, B, lv.hid))
-            off += m
-        if d_probs is None and d_stops is None:
-            DSIDE.zero_()
-        else:
-            dp_tb = d_probs.transpose(0, 1).contiguous() if d_probs is not None else None
-            ds_tb = d_stops.transpose(0, 1).contiguous() if d_stops is not None else None
-            hb = [target(2 * n + 2 + k)[0] if need_par[2 * n + 2 + k] else None for k in range(4)]
-            _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, ctx.probs_tb, dp_tb, ds_tb, dsides, hb)
-        DA = [torch.empty_like(lv.ACT) for lv in levels]
-        DH = [torch.empty((B, lv.hid // 8, lv.H, lv.W, 8), **b16) for lv in levels]
-        DHP = [torch.empty((B, lv.hid // 8, lv.H, lv.W, 8), **b16) for lv in levels]
-        DC = [[torch.empty((B, lv.hid, lv.H, lv.W), **f32) for _ in range(2)] for lv in levels]
-        DUP = [torch.empty((B, lv.c_up // 8, lv.H, lv.W, 8), **b16) if lv.c_up > 0 else None for lv in levels]
-        wds = [lv.dyn.dgrad(gates_w[i]) for i, lv in enumerate(levels)]
-        dhf = [ops.blk_from_nchw(d_hidden[2 * i].contiguous()) if (len(d_hidden) > 2 * i and d_hidden[2 * i] is not None) else None for i in range(n)]
-        dcf = [d_hidden[2 * i + 1].contiguous() if (len(d_hidden) > 2 * i + 1 and d_hidden[2 * i + 1] is not None) else None for i in range(n)]
-        # the last level's hidden states receive their gradient from conv_out only: all T steps in one launch
-        DH_last = torch.empty((T, B, last.hid // 8, last.H, last.W, 8), **b16)
-        if upc:
-            _upconv_bwd(L, d_masks, last, True, co_w, target(kw)[0] if need_par[kw] and have_masks else None,
-                        target(kb)[0] if need_par[kb] and have_masks else None, dsides[n - 1],
-                        T, B, H5, W5, DH_last)
-        else:
-            ops.blk_upsample_bwd_batch([ops.blk_resize_job(dUP5.view(T * B, 1, H5, W5, 8), DH_last.view(T * B, last.hid // 8, last.H, last.W, 8),
-                                                            dsides[n - 1], last.ARG, backward=True)])
-        for d in range(T + n - 2, -1, -1):
-            cells = [(i, d - i) for i in range(n) if 0 <= d - i < T]
-            ups, lbs, dgs = [], [], []
-            for i, t in cells:
-                lv = levels[i]
-                if i + 1 < n:
-                    ups.append(ops.blk_resize_job(DUP[i + 1], DH[i], dsides[i][t], lv.ARG[t], backward=True))
-                dh = DH[i] if i + 1 < n else DH_last[t]
                 dh2, dcn = (dhf[i], dcf[i]) if t == T - 1 else (DHP[i], DC[i][(t + 1) & 1])
-                lbs.append(ops.blk_lstm_bwd_job(dh, dh2, dcn, lv.ACT[t], lv.Cs[t - 1] if t > 0 else None, lv.Cs[t], DA[i][t],
-                                                DC[i][t & 1] if t > 0 else None))
+                lstm.append((DH[i] if i + 1 < n else DH_last[t], dh2, dcn, lv.ACT[t], lv.Cs[t - 1] if t > 0 else None, lv.Cs[t], DA[i][t],
+                             DC[i][t & 1] if t > 0 else None))
                 dxs = ([DUP[i]] if lv.c_up > 0 else []) + ([DHP[i]] if t > 0 else [])
                 if dxs:
-                    dgs.append(ops.blk_conv_job([DA[i][t]], wds[i], sum(x.shape[1] for x in dxs) * 8, cpack=lv.dyn.cin, dsts=dxs))
-            if ups:
-                ops.blk_upsample_bwd_batch(ups)
-            ops.blk_lstm_bwd_batch(lbs)
-            if dgs:
-                ops.blk_conv3x3_batch(dgs)
-        dfeats = [None] * n
-        dG, dskip_jobs = [], []
-        for i, lv in enumerate(levels):
-            if T == 1:
-                dG.append(DA[i][0])
-            else:
-                g = torch.empty_like(lv.G)
-                check(L.rsis_blk_sum_leading(ptr(DA[i]), ptr(g), T, g.numel() // 8, stream()), "rsis_blk_sum_leading")
-                dG.append(g)
-        dskips = [None] * n
-        for i, lv in enumerate(levels):
-            if need_feat[i]:
-                dskips[i] = torch.empty_like(lv.skip)
-                dskip_jobs.append(ops.blk_conv_job([dG[i]], lv.hoist.dgrad(gates_w[i]), lv.c_skip, cpack=lv.hoist.cin, dsts=[dskips[i]]))
-        if dskip_jobs:
-            ops.blk_conv3x3_batch(dskip_jobs)       # the data gradients of the five skip terms: one grouped launch
-        for i, lv in enumerate(levels):
-            kw, kb = 2 * i, 2 * i + 1
-            hid, H, W = lv.hid, lv.H, lv.W
-            if dskips[i] is not None:
-                dfeats[i] = dskips[i] if _is_blk(feats[i]) else ops.blk_to_nchw(dskips[i])
-            if need_par[kb]:
-                db, _ = target(kb)
-                check(L.rsis_blk_bias_grad(ptr(dG[i]), ptr(db), B, 4 * hid, H * W, hid, stream()), "rsis_blk_bias_grad")
-            if need_par[kw]:
-                dW, direct = target(kw)
-                Ctot = gates_w[i].shape[1]
-                h_off = lv.c_up + lv.c_skip
-                blk = ops.DTYPE_BF16_BLK
-                ops.wgrad_launch(L, dG[i], lv.skip, dW, B, lv.c_skip, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up, hid, blk, "rsis_conv2d_wgrad(hoist, blk)",
-                                 direct)
-                if lv.c_up > 0:
-                    ops.wgrad_launch(L, DA[i], lv.UP, dW, T * B, lv.c_up, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, 0, hid, blk,
-                                     "rsis_conv2d_wgrad(batched up, blk)", direct)
-                if T > 1:
-                    ops.wgrad_launch(L, DA[i][1], lv.Hs, dW, (T - 1) * B, hid, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, h_off, hid, blk,
-                                     "rsis_conv2d_wgrad(batched h, blk)", direct)
+                    dg.append((DA[i][t], wds[i], lv.dyn.cin, dpk[i].dtype, dxs))
+            # clstm.py:47-58 backwards: d(gates), dc_{t-1} of the diagonal's cells -- ONE grouped launch
+            lay.lstm_bwd(lstm)
+            # data gradients of the gate convs: d(up[i][t]) for the level below, dh[i][t-1] through the recurrence -- ONE grouped launch
+            lay.dgrad(dg)
+        # ---- per level, once: the time-invariant skip term and the time-batched weight gradients ----
+        dG, dskip, dfeats = [None] * n, [None] * n, [None] * n
+        for grp in ([[i] for i in range(n)] if lay.by_level else [range(n)]):
+            for i in grp:
+                if T == 1:
+                    dG[i] = DA[i][0]
+                else:
+                    dG[i] = torch.empty_like(levels[i].G)
+                    lay.sum_t(DA[i], dG[i])
+                if need_feat[i]:
+                    dskip[i] = torch.empty_like(levels[i].skip)
+            lay.skip_dgrad([(dG[i], levels[i].hoist.dgrad(gates_w[i]), levels[i].hoist.cin, levels[i].hoist.dtype, [dskip[i]]) for i in grp
+                            if need_feat[i]])
+            for i in grp:
+                lv = levels[i]
+                kw, kb = 2 * i, 2 * i + 1
+                hid, H, W = lv.hid, lv.H, lv.W
+                if need_feat[i]:
+                    dfeats[i] = dskip[i] if _is_blk(feats[i]) else lay.to_nchw(dskip[i])
+                if need_par[kb]:
+                    lay.bias_grad(dG[i], target(kb)[0], lv)
+                if need_par[kw]:
+                    dW, direct = target(kw)
+                    Ctot = gates_w[i].shape[1]
+                    dt_skip, dt, rows = lay.wgrad_formats(lv)
+                    ops.wgrad_launch(L, dG[i], lv.skip, dW, B, lv.c_skip, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up, hid, dt_skip,
+                                     "rsis_conv2d_wgrad(hoist)", direct)
+                    da = rows(DA[i])
+                    if lv.c_up > 0:
+                        ops.wgrad_launch(L, da, rows(lv.UP), dW, T * B, lv.c_up, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, 0, hid, dt,
+                                         "rsis_conv2d_wgrad(batched up)", direct)
+                    if T > 1:
+                        ops.wgrad_launch(L, da[B:], rows(lv.Hs[:T - 1]), dW, (T - 1) * B, hid, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up + lv.c_skip,
+                                         hid, dt, "rsis_conv2d_wgrad(batched h)", direct)
         for lv in levels:
             lv.G = lv.Hs = lv.Cs = lv.ACT = lv.UP = lv.skip = None
-        ctx.levels = ctx.UP5 = ctx.feats = ctx.params = ctx.decoder = None
-        return (None, None, None, None) + tuple(dfeats) + tuple(grads_par)
+        ctx.lay = ctx.levels = ctx.UP5 = ctx.feats = ctx.params = ctx.decoder = None
+        return (None, None, None, None, None) + tuple(dfeats) + tuple(grads_par)
 
 
 def decoder_sequence_stacked(decoder, skip_feats, T, want_hidden=True):
-    """(out_masks (B, T, H*W) logits, class_probs (B, T, C), stop logits (B, T, 1), hidden_list, (H, W) of the masks)"""
+    """(out_masks (B, T, H*W) logits, class_probs (B, T, C), stop logits (B, T, 1), hidden_list (None unless want_hidden), (H, W) of the
+    masks)"""
     n = len(decoder.clstm_list)
     params = []
     for c in decoder.clstm_list:
@@ -703,10 +624,8 @@ def decoder_sequence_stacked(decoder, skip_feats, T, want_hidden=True):
     params += [decoder.conv_out.weight, decoder.conv_out.bias, decoder.fc_class.weight, decoder.fc_class.bias, decoder.fc_stop.weight,
                decoder.fc_stop.bias]
     keep = torch.is_grad_enabled() and (any(f.requires_grad for f in skip_feats) or any(p.requires_grad for p in params))
-    if blk_supported(decoder, skip_feats):
-        res = _DecoderSeqBlkFn.apply(decoder, int(T), keep, bool(want_hidden), *skip_feats, *params)
-    else:
-        res = _DecoderSeqFn.apply(decoder, int(T), keep, *skip_feats, *params)
+    layout = _Blk if blk_supported(decoder, skip_feats) else _Nchw
+    res = _DecoderSeqFn.apply(layout, decoder, int(T), keep, bool(want_hidden), *skip_feats, *params)
     out_masks, out_probs, out_stops = res[:3]
     hidden = [[res[3 + 2 * i], res[4 + 2 * i]] for i in range(n)] if len(res) > 3 else None
     size = (2 * skip_feats[-1].shape[2], 2 * skip_feats[-1].shape[3])

@@ -248,8 +248,8 @@ def test_blk_conv_out_over_all_timesteps(shape):
 
 @pytest.mark.parametrize("geom", ["224", "odd"])
 def test_blk_decoder_sequence_against_the_fp32_storage_decoder_and_float64(geom):
-    """The whole T-step decoder on blk storage (decoder_seq._DecoderSeqBlkFn) against (a) the same bf16-operand kernels on fp32 NCHW
-    storage (RSIS_DECODER_BLK=0, decoder_seq._DecoderSeqFn) and (b) the float64 oracle decoder on the same weights.  Bars stated before
+    """The whole T-step decoder on blk storage (decoder_seq._DecoderSeqFn, _Blk layout) against (a) the same bf16-operand kernels on
+    fp32 NCHW storage (RSIS_DECODER_BLK=0, the _Nchw layout) and (b) the float64 oracle decoder on the same weights.  Bars stated before
     measuring: blk storage adds ONE bf16 rounding to tensors the fp32-storage path already rounds when it stages them (h, up(h)) and
     rounds three it keeps in fp32 (the hoisted gate term, the saved gates, the gate gradients): outputs within 2 % of max |reference|
     of the fp32-storage path, every gradient within 6 % relative L2 of it -- and no farther from float64 than 1.5 x the fp32-storage
