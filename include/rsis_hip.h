@@ -264,6 +264,17 @@ int rsis_maxpool3x3s2_bwd(const float* dy, const unsigned char* argmax, float* d
 int rsis_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, float gscale, const int* step_dev, void* stream);
 
+/* ---- the other two rules of utils/utils.py:78-87 (-optim / -optim_cnn sgd, rmsprop) on a flat parameter range, with the same
+ * gradient handling as rsis_adam_step: d = g * gscale + weight_decay * p.  Parameters without a gradient are the caller's to skip
+ * (no range covers them).  n == 0 is a no-op.
+ * torch.optim.SGD(momentum), dampening 0, no Nesterov: buf = momentum * buf + d; p -= lr * buf.  A zero-filled buf gives torch's first
+ * step (buf = d), so no step count is kept; momentum 0 is plain SGD (p -= lr * d). ---- */
+int rsis_sgd_step(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay, float gscale,
+                  void* stream);
+/* ---- torch.optim.RMSprop, no momentum, not centred: sq = alpha * sq + (1 - alpha) * d * d; p -= lr * d / (sqrt(sq) + eps). ---- */
+int rsis_rmsprop_step(float* p, const float* g, float* sq, long n, float lr, float alpha, float eps, float weight_decay, float gscale,
+                      void* stream);
+
 /* ---- Hungarian matching of predictions to ground-truth slots (hungarian.py:91-125, munkres.Munkres().compute per
  * sample): scores[B][G][T] fp32 (rows = GT slots, columns = predictions, T <= G <= 64) -> perm[B][G] int64 with
  * perm[b][t] = GT slot of prediction t for t < T and 0 elsewhere.  Minimum total cost; runs on the device so the training

@@ -62,6 +62,7 @@ int rsis_l_subsample(const float*, float*, long, int, int, int, int, int, hipStr
 int rsis_l_maxpool_bwd(const float*, const unsigned char*, float*, long, int, int, int, int, int, hipStream_t);
 int rsis_l_channel_sum(const float*, float*, int, int, int, int, hipStream_t);
 int rsis_l_adam(float*, const float*, float*, float*, long, float, float, float, float, float, int, float, const int*, hipStream_t);
+int rsis_l_flat_rule(int, float*, const float*, float*, long, float, float, float, float, float, hipStream_t);
 int rsis_l_assign(const float*, long long*, int, int, int, hipStream_t);
 int rsis_l_gmax_bwd_add(const float*, const int*, float*, long, int, hipStream_t);
 int rsis_l_pack_batch(const rsis_pack_job*, int, int, hipStream_t);
@@ -757,6 +758,18 @@ int rsis_adam_step(float* p, const float* g, float* m, float* v, long n, float l
   if (!p || !g || !m || !v || n < 0 || (!step_dev && step < 1)) return RSIS_ERR_ARG;
   if (n == 0) return RSIS_OK;
   return rsis_l_adam(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step_dev ? 1 : step, gscale, step_dev, (hipStream_t)stream);
+}
+int rsis_sgd_step(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay, float gscale,
+                  void* stream) {
+  if (!p || !g || !buf || n < 0) return RSIS_ERR_ARG;
+  if (n == 0) return RSIS_OK;
+  return rsis_l_flat_rule(0, p, g, buf, n, lr, momentum, 0.f, weight_decay, gscale, (hipStream_t)stream);
+}
+int rsis_rmsprop_step(float* p, const float* g, float* sq, long n, float lr, float alpha, float eps, float weight_decay, float gscale,
+                      void* stream) {
+  if (!p || !g || !sq || n < 0) return RSIS_ERR_ARG;
+  if (n == 0) return RSIS_OK;
+  return rsis_l_flat_rule(1, p, g, sq, n, lr, alpha, eps, weight_decay, gscale, (hipStream_t)stream);
 }
 
 int rsis_assign_min_cost(const float* scores, long long* perm, int B, int G, int T, void* stream) {

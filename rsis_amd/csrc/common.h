@@ -31,6 +31,13 @@ int rsis_zero_async(void* p, size_t bytes, hipStream_t st);
 // reduced address, no same-address atomics from more than one contributor) -- bit-reproducible run to run, slower.
 int rsis_deterministic();
 
+// grid of the grid-stride elementwise kernels (256 threads per block): one thread per item up to 16 blocks per CU
+static inline int ew_grid(long total) {
+  long g = (total + 255) / 256;
+  if (g > 256 * 16) g = 256 * 16;
+  if (g < 1) g = 1;
+  return (int)g;
+}
 static inline int rsis_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int rsis_roundup(int a, int b) { return ((a + b - 1) / b) * b; }
 

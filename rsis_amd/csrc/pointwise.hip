@@ -986,12 +986,6 @@ int rsis_zero_async(void* p, size_t bytes, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // launchers (called from api.hip)
 // ------------------------------------------------------------------------------------------------
-static inline int ew_grid(long total) {
-  long g = (total + 255) / 256;
-  if (g > 256 * 16) g = 256 * 16;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 // register-resident single-launch BatchNorm: float4-able planes, the whole channel (B*HW values) in one block's registers, and
 // enough channels to fill the chip (RSIS_BN_FUSED=0 forces the split kernels)
 static inline bool bn_fused_ok(int C, int HW, long N) {

@@ -784,6 +784,32 @@ def adam_step_flat(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, gscale
         bump_weight_epoch()
 
 
+def _require_flat(what, *ts):
+    """equal-length contiguous ranges: the kernel walks all of them with the first one's length"""
+    require_cuda_f32(*ts)
+    if any(t.numel() != ts[0].numel() or not t.is_contiguous() for t in ts):
+        raise ValueError("%s: the parameter, gradient and state ranges must be contiguous and of one length" % what)
+
+
+def sgd_step_flat(p, g, buf, lr, momentum, weight_decay, gscale=1.0, bump=True):
+    """torch.optim.SGD(momentum) step on flat fp32 buffers (in place; bumps the packed-weight epoch).  buf: the momentum buffer,
+    zero before the first step of its parameters."""
+    _require_flat("sgd_step_flat", p, g, buf)
+    check(lib().rsis_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), float(lr), float(momentum), float(weight_decay), float(gscale),
+                              stream()), "rsis_sgd_step")
+    if bump:
+        bump_weight_epoch()
+
+
+def rmsprop_step_flat(p, g, sq, lr, alpha, eps, weight_decay, gscale=1.0, bump=True):
+    """torch.optim.RMSprop step on flat fp32 buffers (in place; bumps the packed-weight epoch).  sq: the square average."""
+    _require_flat("rmsprop_step_flat", p, g, sq)
+    check(lib().rsis_rmsprop_step(ptr(p), ptr(g), ptr(sq), p.numel(), float(lr), float(alpha), float(eps), float(weight_decay),
+                                  float(gscale), stream()), "rsis_rmsprop_step")
+    if bump:
+        bump_weight_epoch()
+
+
 def assign_min_cost(scores):
     """Device-side Hungarian matching (reference hungarian.py:91-125): scores (B, G, T) fp32, rows = GT slots, columns =
     predictions -> perm (B, G) int64, perm[b, t] = GT slot matched to prediction t (0 in the unassigned tail)."""

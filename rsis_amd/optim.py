@@ -1,9 +1,9 @@
 """Flat-buffer optimizer + bucketed gradient all-reduce for one-process-per-GPU data parallelism.
 
-Replaces the reference's two torch.optim.Adam instances (utils/utils.py:83-84, train.py:239-240,185-187) and its
+Replaces the reference's two torch.optim optimizers (Adam, SGD or RMSprop: utils/utils.py:78-87, train.py:239-240,185-187) and its
 single-process nn.DataParallel replication (train.py:269-274).  Parameters of a group are re-homed as views of ONE
-flat fp32 buffer (so are their grads): the Adam step is a single fused HIP kernel over the flat range
-(rsis_adam_step), and the data-parallel gradient exchange is a handful of large RCCL all-reduces over xGMI, one per
+flat fp32 buffer (so are their grads): the optimizer step is a single fused HIP kernel over the flat range
+(rsis_adam_step, rsis_sgd_step, rsis_rmsprop_step), and the data-parallel gradient exchange is a handful of large RCCL all-reduces over xGMI, one per
 bucket, launched from autograd hooks as soon as a bucket's gradients are final (decoder + skip bucket first -- it
 overlaps the whole encoder backward).
 """
@@ -15,13 +15,13 @@ import torch.distributed as dist
 from . import ops
 
 
-class FlatGroup(object):
-    """A parameter group living in one flat buffer. `params` keep their identity (module attributes still work).
+class FlatParams(object):
+    """Parameters re-homed as views of ONE flat fp32 buffer (their grads as views of a second one), and the per-parameter bookkeeping
+    every optimizer rule shares.  `params` keep their identity (module attributes still work).
 
-    torch.optim.Adam semantics per PARAMETER (the reference's optimizer, utils/utils.py:83-84): a parameter that has never
-    received a gradient (`p.grad is None` there) is skipped entirely -- no weight decay, no moment update, no step count --
-    and its bias correction starts at step 1 when its first gradient arrives.  Here every `.grad` is a view of the flat
-    gradient buffer, so "has a gradient" is tracked explicitly: parameters listed in `lazy` start inactive and are switched on
+    torch.optim semantics per PARAMETER (the reference's optimizers, utils/utils.py:78-87): a parameter that has never received a
+    gradient (`p.grad is None` there) is skipped entirely -- no weight decay, no state update.  Here every `.grad` is a view of the
+    flat gradient buffer, so "has a gradient" is tracked explicitly: parameters listed in `lazy` start inactive and are switched on
     by `mark_has_grad` (train.runIter does it for fc_class / fc_stop when their loss is enabled, train.py:173-176); once active
     a parameter stays active, as a zero-filled `.grad` does in the reference.  Consecutive parameters with the same state are
     stepped by one kernel launch.
@@ -30,15 +30,13 @@ class FlatGroup(object):
     SURVEY.md Appendix C), i.e. it applies 1/3/4 identical updates per step; pass utils.base_param_multiplicity(...) to reproduce
     that as a per-range learning-rate multiplier (first-order identical; off by default)."""
 
-    def __init__(self, params, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, name="group", lazy=(), lr_mult=None):
+    def __init__(self, params, name="group", lazy=(), lr_mult=None):
         self.params = [p for p in params if p.requires_grad]
-        self.lr, self.weight_decay, self.betas, self.eps, self.name = lr, weight_decay, betas, eps, name
+        self.name = name
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device if self.params else torch.device("cpu")
         self.flat_p = torch.empty(n, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.offsets = []
         off = 0
         with torch.no_grad():
@@ -51,21 +49,38 @@ class FlatGroup(object):
                 off += k
         lazy_ids = set(id(p) for p in lazy)
         self.active = [id(p) not in lazy_ids for p in self.params]
-        self.steps = [0] * len(self.params)                 # torch.optim.Adam's per-parameter state['step']
         self.mult = [float(lr_mult.get(p, 1.0)) if lr_mult else 1.0 for p in self.params]
         self._index = {id(p): i for i, p in enumerate(self.params)}
         self._ranges = None
-        self._dev = None          # (ranges, int32 device counters) while captured graphs own the step counts
-        self._dev_users = 0       # live captures sharing those counters (train.GraphedStep instances)
-        ops.bump_weight_epoch()
 
-    # ---- torch.optim.Adam's "skip parameters without a gradient" ----
+    # ---- torch.optim's "skip parameters without a gradient" ----
     def mark_has_grad(self, params):
         for p in params:
             i = self._index.get(id(p))
             if i is not None and not self.active[i]:
                 self.active[i] = True
                 self._ranges = None
+
+    def zero_grad(self):
+        self.flat_g.zero_()
+        for p, (off, k) in zip(self.params, self.offsets):  # re-attach (a caller may have set .grad = None)
+            if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * off:
+                p.grad = self.flat_g[off:off + k].view_as(p)
+
+
+class FlatGroup(FlatParams):
+    """torch.optim.Adam over FlatParams (the reference's default rule, utils/utils.py:83-84): both moments, and a per-parameter step
+    count whose bias correction starts at step 1 when the parameter's first gradient arrives."""
+
+    def __init__(self, params, lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, name="group", lazy=(), lr_mult=None):
+        FlatParams.__init__(self, params, name, lazy=lazy, lr_mult=lr_mult)
+        self.lr, self.weight_decay, self.betas, self.eps = lr, weight_decay, betas, eps
+        self.exp_avg = torch.zeros_like(self.flat_p)
+        self.exp_avg_sq = torch.zeros_like(self.flat_p)
+        self.steps = [0] * len(self.params)                 # torch.optim.Adam's per-parameter state['step']
+        self._dev = None          # (ranges, int32 device counters) while captured graphs own the step counts
+        self._dev_users = 0       # live captures sharing those counters (train.GraphedStep instances)
+        ops.bump_weight_epoch()
 
     @property
     def step_count(self):
@@ -94,12 +109,6 @@ class FlatGroup(object):
                     out.append((off, k, self.steps[i], self.mult[i], [i]))
             self._ranges = out
         return self._ranges
-
-    def zero_grad(self):
-        self.flat_g.zero_()
-        for p, (off, k) in zip(self.params, self.offsets):  # re-attach (a caller may have set .grad = None)
-            if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * off:
-                p.grad = self.flat_g[off:off + k].view_as(p)
 
     def step(self, gscale=1.0):
         if not self.flat_p.is_cuda:
@@ -158,6 +167,9 @@ class FlatGroup(object):
     def load_state_dict(self, sd):
         if "param_groups" in sd:
             return self._load_torch_adam(sd)
+        if sd.get("optim", "adam") != "adam":   # a FlatRuleGroup's dict (another rule: -optim sgd / rmsprop)
+            print("FlatGroup(%s): optimizer state of rule %r, not adam; moments restart at zero" % (self.name, sd["optim"]))
+            return False
         if self._dev is not None:
             raise RuntimeError("FlatGroup.load_state_dict: leave graph mode first (end_graph)")
         if "steps" in sd and len(sd["steps"]) == len(self.steps):
@@ -178,7 +190,7 @@ class FlatGroup(object):
         times) the moments restart at zero."""
         ids = [i for g in sd.get("param_groups", []) for i in g["params"]]
         st = sd.get("state", {})
-        ok = len(ids) == len(self.params) and all(i not in st or tuple(st[i]["exp_avg"].shape) == tuple(p.shape)
+        ok = len(ids) == len(self.params) and all(i not in st or ("exp_avg" in st[i] and tuple(st[i]["exp_avg"].shape) == tuple(p.shape))
                                                   for i, p in zip(ids, self.params))
         if not ok or not st:
             if st:
@@ -196,12 +208,127 @@ class FlatGroup(object):
         return True
 
 
-class FlatAdam(object):
-    """torch.optim.Adam semantics (incl. L2 weight decay, parameters without a gradient skipped) over a FlatGroup;
-    `.step()` / `.zero_grad()` / state_dict."""
+class FlatRuleGroup(FlatParams):
+    """torch.optim.SGD(momentum) (rule "sgd") or torch.optim.RMSprop (rule "rmsprop") over FlatParams: the other two rules of the
+    reference's get_optimizer (utils/utils.py:78-87; -optim / -optim_cnn).  ONE state buffer (`buf`: the momentum buffer or the square
+    average; Adam's two moments are not allocated) and no step count: a zero buffer is what torch starts a parameter from (SGD's
+    first step buf = d equals momentum * 0 + d), so a parameter's first gradient needs no bookkeeping.
+    SGD: dampening 0, no Nesterov.  RMSprop: alpha, eps, no momentum, not centred (the reference sets none of these)."""
 
-    def __init__(self, params, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, name="adam", lazy=(), lr_mult=None):
-        self.group = FlatGroup(list(params), lr, weight_decay, betas, eps, name, lazy=lazy, lr_mult=lr_mult)
+    BUFFERS = {"sgd": "momentum_buffer", "rmsprop": "square_avg"}
+
+    def __init__(self, rule, params, lr, weight_decay=0.0, momentum=0.9, alpha=0.99, eps=1e-8, name="group", lazy=(), lr_mult=None):
+        if rule not in self.BUFFERS:
+            raise ValueError("FlatRuleGroup: rule %r (sgd or rmsprop)" % (rule,))
+        FlatParams.__init__(self, params, name, lazy=lazy, lr_mult=lr_mult)
+        self.rule, self.lr, self.weight_decay = rule, lr, weight_decay
+        self.hyper = {"momentum": float(momentum)} if rule == "sgd" else {"alpha": float(alpha), "eps": float(eps)}
+        self.buf = torch.zeros_like(self.flat_p)
+        self._frozen = None       # the launch ranges while captured graphs are alive
+        self._frozen_users = 0
+        ops.bump_weight_epoch()
+
+    @property
+    def buffer_name(self):
+        return self.BUFFERS[self.rule]
+
+    def ranges(self):
+        """[(offset, numel, lr multiplier, [param indices])] of the ACTIVE parameters, consecutive ones with equal multipliers merged"""
+        if self._ranges is None:
+            out = []
+            for i, (off, k) in enumerate(self.offsets):
+                if not self.active[i]:
+                    continue
+                if out and out[-1][0] + out[-1][1] == off and out[-1][2] == self.mult[i]:
+                    last = out[-1]
+                    out[-1] = (last[0], last[1] + k, last[2], last[3] + [i])
+                else:
+                    out.append((off, k, self.mult[i], [i]))
+            self._ranges = out
+        return self._ranges
+
+    def step(self, gscale=1.0):
+        if not self.flat_p.is_cuda:
+            raise RuntimeError("FlatRuleGroup.step: the fused %s step runs on the GPU only" % self.rule)
+        for off, n, mult, _idx in (self._frozen if self._frozen is not None else self.ranges()):
+            p, g, b = self.flat_p[off:off + n], self.flat_g[off:off + n], self.buf[off:off + n]
+            if self.rule == "sgd":
+                ops.sgd_step_flat(p, g, b, self.lr * mult, self.hyper["momentum"], self.weight_decay, gscale, bump=False)
+            else:
+                ops.rmsprop_step_flat(p, g, b, self.lr * mult, self.hyper["alpha"], self.hyper["eps"], self.weight_decay, gscale,
+                                      bump=False)
+        ops.bump_weight_epoch()
+
+    # ---- hipGraph support (train.GraphedStep): no count lives on the host, so a capture only freezes the launch ranges ----
+    def begin_graph(self):
+        ranges = [tuple(r) for r in self.ranges()]
+        if self._frozen is not None and self._frozen != ranges:
+            raise RuntimeError("FlatRuleGroup.begin_graph: the active parameter set changed while a capture is alive (release it first)")
+        self._frozen = ranges
+        self._frozen_users += 1
+
+    def note_replay(self):
+        """(nothing on the host mirrors a replay)"""
+
+    def end_graph(self):
+        self._frozen_users = max(0, self._frozen_users - 1)
+        if self._frozen_users == 0:
+            self._frozen = None
+
+    def state_dict(self):
+        sd = {"optim": self.rule, "active": list(self.active), self.buffer_name: self.buf, "lr": self.lr,
+              "weight_decay": self.weight_decay}
+        sd.update(self.hyper)
+        return sd
+
+    def load_state_dict(self, sd):
+        """this group's own state_dict (same rule), or a torch.optim.SGD / RMSprop state_dict (_load_torch).  Anything else (another
+        rule, another parameter list) leaves the state at zero and returns False."""
+        if self._frozen is not None:
+            raise RuntimeError("FlatRuleGroup.load_state_dict: leave graph mode first (end_graph)")
+        if "param_groups" in sd:
+            return self._load_torch(sd)
+        key = self.buffer_name
+        if (sd.get("optim") != self.rule or key not in sd or len(sd.get("active", ())) != len(self.active)
+                or sd[key].numel() != self.buf.numel()):
+            print("FlatRuleGroup(%s): optimizer state is not %s state of this parameter list; %s restarts at zero"
+                  % (self.name, self.rule, key))
+            return False
+        self.active = [bool(v) for v in sd["active"]]
+        self._ranges = None
+        self.buf.copy_(sd[key].reshape(-1))
+        return True
+
+    def _load_torch(self, sd):
+        """torch.optim.SGD / RMSprop state_dict: per-parameter buffers in param_groups order, adopted under the rule of
+        FlatGroup._load_torch_adam (one to one, a parameter without an entry had no gradient yet: inactive, zero buffer)"""
+        key = self.buffer_name
+        ids = [i for g in sd.get("param_groups", []) for i in g["params"]]
+        st = sd.get("state", {})
+        ok = len(ids) == len(self.params) and all(i not in st or (st[i].get(key) is not None and tuple(st[i][key].shape) == tuple(p.shape))
+                                                  for i, p in zip(ids, self.params))
+        if not ok or not st:
+            if st:
+                print("FlatRuleGroup(%s): optimizer state does not match the parameter list; %s restarts at zero" % (self.name, key))
+            return False
+        for k, (i, (off, n)) in enumerate(zip(ids, self.offsets)):
+            if i in st:
+                self.buf[off:off + n].copy_(st[i][key].reshape(-1))
+                self.active[k] = True
+            else:
+                self.buf[off:off + n].zero_()
+                self.active[k] = False
+        self._ranges = None
+        return True
+
+
+class FlatOptimizer(object):
+    """What train.py drives: `.group` (a FlatParams: flat_p / flat_g / offsets, and begin_graph / end_graph / note_replay for
+    train.GraphedStep), `.gscale` (the gradient scale of the next step: 1 / world after a SUM all-reduce), `.step()` / `.zero_grad()`
+    / `mark_has_grad` / state_dict."""
+
+    def __init__(self, group):
+        self.group = group
         self.gscale = 1.0
 
     def zero_grad(self):
@@ -218,6 +345,29 @@ class FlatAdam(object):
 
     def load_state_dict(self, sd):
         return self.group.load_state_dict(sd)
+
+
+class FlatAdam(FlatOptimizer):
+    """torch.optim.Adam semantics (incl. L2 weight decay, parameters without a gradient skipped) over a FlatGroup"""
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, name="adam", lazy=(), lr_mult=None):
+        FlatOptimizer.__init__(self, FlatGroup(list(params), lr, weight_decay, betas, eps, name, lazy=lazy, lr_mult=lr_mult))
+
+
+class FlatSGD(FlatOptimizer):
+    """torch.optim.SGD(lr, momentum, weight_decay) semantics (dampening 0, no Nesterov; parameters without a gradient skipped)"""
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.0, momentum=0.9, name="sgd", lazy=(), lr_mult=None):
+        FlatOptimizer.__init__(self, FlatRuleGroup("sgd", list(params), lr, weight_decay, momentum=momentum, name=name, lazy=lazy,
+                                                   lr_mult=lr_mult))
+
+
+class FlatRMSprop(FlatOptimizer):
+    """torch.optim.RMSprop(lr, alpha, eps, weight_decay) semantics (no momentum, not centred; parameters without a gradient skipped)"""
+
+    def __init__(self, params, lr=1e-2, weight_decay=0.0, alpha=0.99, eps=1e-8, name="rmsprop", lazy=(), lr_mult=None):
+        FlatOptimizer.__init__(self, FlatRuleGroup("rmsprop", list(params), lr, weight_decay, alpha=alpha, eps=eps, name=name,
+                                                   lazy=lazy, lr_mult=lr_mult))
 
 
 class BucketedAllReduce(object):

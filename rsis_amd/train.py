@@ -25,7 +25,7 @@ import torch.distributed as dist
 from . import ops
 from .args import get_parser
 from .modules.model import RSIS, FeatureExtractor
-from .optim import BucketedAllReduce, FlatAdam
+from .optim import BucketedAllReduce, FlatAdam, FlatOptimizer, FlatRMSprop, FlatSGD
 from .synthetic import SyntheticLoader
 from .utils.hungarian import match_indices, softIoU_matrix
 from .utils.objectives import MaskedBCELoss, MaskedNLLLoss, softIoULoss
@@ -225,11 +225,11 @@ def runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits
     if train:
         if reducer is not None:
             reducer.reset()
-        # FlatAdam keeps every .grad as a zeroed view of one flat buffer: let the wgrad kernels accumulate into it directly
-        direct = isinstance(enc_opt, FlatAdam) and isinstance(dec_opt, FlatAdam)
-        if isinstance(dec_opt, FlatAdam):
-            # torch.optim.Adam skips parameters whose grad is None: the heads get their first gradient when their loss is
-            # switched on (train.py:173-176); until then they are not touched (no weight decay, no moments, no step count)
+        # a FlatOptimizer keeps every .grad as a zeroed view of one flat buffer: let the wgrad kernels accumulate into it directly
+        direct = isinstance(enc_opt, FlatOptimizer) and isinstance(dec_opt, FlatOptimizer)
+        if isinstance(dec_opt, FlatOptimizer):
+            # torch.optim skips parameters whose grad is None: the heads get their first gradient when their loss is switched on
+            # (train.py:173-176); until then they are not touched (no weight decay, no optimizer state, no step count)
             if args.use_class_loss:
                 dec_opt.mark_has_grad(decoder.fc_class.parameters())
             if args.use_stop_loss:
@@ -303,20 +303,36 @@ def init_distributed():
     return rank, local_rank, world
 
 
+def _flat_optimizer(rule, params, lr, weight_decay, momentum, name, lazy=(), lr_mult=None):
+    """utils/utils.py:78-87 get_optimizer on the fused flat HIP steps.  SGD takes -momentum (the reference passes none: torch's
+    0.9 there, which is also -momentum's default); RMSprop takes torch's defaults (alpha 0.99, eps 1e-8)."""
+    if rule == "adam":
+        return FlatAdam(params, lr=lr, weight_decay=weight_decay, name=name, lazy=lazy, lr_mult=lr_mult)
+    if rule == "sgd":
+        return FlatSGD(params, lr=lr, weight_decay=weight_decay, momentum=momentum, name=name, lazy=lazy, lr_mult=lr_mult)
+    if rule == "rmsprop":
+        return FlatRMSprop(params, lr=lr, weight_decay=weight_decay, name=name, lazy=lazy, lr_mult=lr_mult)
+    raise Exception("optimizer %r: adam, sgd or rmsprop" % (rule,))
+
+
 def build_optimizers(args, encoder, decoder):
-    """train.py:236-240: dec_opt = decoder + skip convs/BNs (lr), enc_opt = trunk (lr_cnn).  Fused flat Adam.
+    """train.py:236-240: dec_opt = decoder + skip convs/BNs (-optim, lr), enc_opt = trunk (-optim_cnn, lr_cnn).  Fused flat steps.
     The reference's get_base_params yields trunk tensors 1-4 times, i.e. an effective 1x/3x/4x
     lr_cnn; `--enc_lr_quirk` reproduces it as a per-tensor learning-rate multiplier, the default steps each tensor once."""
-    if args.optim != "adam" or args.optim_cnn != "adam":
-        raise Exception("only -optim adam / -optim_cnn adam run on the fused HIP optimizer")
+    quirk = getattr(args, "enc_lr_quirk", False)
+    if quirk and args.optim_cnn != "adam":
+        # (the multiplier stands in for repeated ADAM updates of one tensor; repeated momentum / RMSprop updates compound differently)
+        raise Exception("--enc_lr_quirk reproduces repeated Adam updates only: it cannot be combined with -optim_cnn %s"
+                        % args.optim_cnn)
+    momentum = getattr(args, "momentum", 0.9)
     decoder_params = list(decoder.parameters()) + list(get_skip_params(encoder))
-    # fc_class / fc_stop receive no gradient until their loss is enabled: torch.optim.Adam leaves such parameters alone
+    # fc_class / fc_stop receive no gradient until their loss is enabled: torch.optim leaves such parameters alone
     lazy = [] if args.use_class_loss else list(decoder.fc_class.parameters())
     lazy += [] if args.use_stop_loss else list(decoder.fc_stop.parameters())
-    dec_opt = FlatAdam(decoder_params, lr=args.lr, weight_decay=args.weight_decay, name="dec", lazy=lazy)
-    mult = base_param_multiplicity(encoder) if getattr(args, "enc_lr_quirk", False) else None
-    enc_opt = FlatAdam(list(get_base_params(args, encoder)), lr=args.lr_cnn, weight_decay=args.weight_decay_cnn, name="enc",
-                       lr_mult=mult)
+    dec_opt = _flat_optimizer(args.optim, decoder_params, args.lr, args.weight_decay, momentum, "dec", lazy=lazy)
+    mult = base_param_multiplicity(encoder) if quirk else None
+    enc_opt = _flat_optimizer(args.optim_cnn, list(get_base_params(args, encoder)), args.lr_cnn, args.weight_decay_cnn, momentum, "enc",
+                              lr_mult=mult)
     return enc_opt, dec_opt
 
 
@@ -352,9 +368,9 @@ class StagedExchange(object):
 def exchange_plan(encoder, optims, cuts, update_encoder=True):
     """flat-gradient ranges that are final after each stage of a split backward (encoder.split_backward = cuts):
     {"dec": [...], "trunk_hi": [...], "rest": [...]} -- "dec" when BPTT and the skip convs are done, "trunk_hi" when trunk layers
-    4-3 are, "rest" at the end.  optims = [enc_opt, dec_opt] (FlatAdam).  update_encoder False (every rank has the same args): the
+    4-3 are, "rest" at the end.  optims = [enc_opt, dec_opt] (FlatOptimizer).  update_encoder False (every rank has the same args): the
     trunk's gradients are neither computed (FeatureExtractor.trunk_grad) nor applied (train.py:186-187), so its 178 MB do not travel."""
-    groups = [o.group for o in optims if isinstance(o, FlatAdam)]
+    groups = [o.group for o in optims if isinstance(o, FlatOptimizer)]
     enc_g = optims[0].group
     dec = [g.flat_g for g in groups if g is not enc_g]
     from .modules import model as _model
@@ -433,7 +449,7 @@ class GraphedStep(object):
                        between=between)
 
     def _groups(self):
-        return [o.group for o in self.optims if isinstance(o, FlatAdam)]
+        return [o.group for o in self.optims if isinstance(o, FlatOptimizer)]
 
     def _reduce(self, buf, async_op=False):
         """SUM all-reduce of (a range of) a flat gradient buffer, issued from the current stream (RCCL runs it on its own stream
@@ -686,9 +702,11 @@ def trainIters(args):
         pickle.dump(args, open(os.path.join(model_dir, "args.pkl"), "wb"))   # train.py:234
     enc_opt, dec_opt = build_optimizers(args, encoder, decoder)
     if (resuming or args.transfer) and enc_opt_dict is not None:
-        # own format or the reference's torch.optim.Adam state_dict ('state' / 'param_groups'); load_state_dict dispatches
+        # own format or the reference's torch.optim state_dict ('state' / 'param_groups'); load_state_dict dispatches
         ok_e = enc_opt.load_state_dict(enc_opt_dict)
-        new_head = args.transfer and "exp_avg" in dec_opt_dict and dec_opt_dict["exp_avg"].numel() != dec_opt.group.exp_avg.numel()
+        # (a new classification head changes the decoder group's flat size: its saved state cannot line up)
+        saved = next((dec_opt_dict[k] for k in ("exp_avg", "momentum_buffer", "square_avg") if k in dec_opt_dict), None)
+        new_head = args.transfer and saved is not None and saved.numel() != dec_opt.group.flat_p.numel()
         ok_d = False if new_head else dec_opt.load_state_dict(dec_opt_dict)
         if rank == 0 and not (ok_e and ok_d):
             print("optimizer state: %s restored, %s restart from zero moments"
