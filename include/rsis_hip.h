@@ -384,6 +384,42 @@ int rsis_rle_to_string(const unsigned int* counts, int m, char* out, int cap);
 int rsis_largest_component(const unsigned char* mask, unsigned char* out, int* labels, int* counts, int* best, int n, int h, int w,
                            void* stream);
 
+/* ---- COCO 'segm' evaluation on bit-packed masks (cocoeval.py:164-191 computeIoU, :236-314 evaluateImg of the reference's modified
+ * pycocotools; IoU semantics of maskApi.c:77-96 rleIou).  A mask of `len` elements is `stride` >= ceil(len / 64) 64-bit words, element e
+ * = bit e % 64 of word e / 64, every bit past len zero.  The grouped launches read their job tables (int64, 8 entries per job) from
+ * DEVICE memory; a job whose offsets do not fit the stated buffer lengths is skipped.  All results are integers or one IEEE float64
+ * division of integers: nothing depends on the order of execution.
+ * rsis_mask_pack_bits: masks[n][len] uint8 (zero / non-zero; the layout rsis_mask_resize_threshold writes) -> bits[n][stride],
+ *   area[n] = set elements.
+ * rsis_rle_to_bits: n masks from run counts (rsis_rle_encode's, or rsis_rle_from_string's): desc[k] = {first count, number of counts,
+ *   first word, words} indexes counts[counts_len] / bits[bits_len]; ends[counts_len] is workspace.  sum(counts of k) must not exceed
+ *   64 * words.
+ * rsis_mask_intersect_blocks / _batch: jobs[j] = {dt_off, gt_off, D, G, stride, out_off, block_begin, 0}: D detection and G ground-truth
+ *   masks of `stride` words (even, as are the offsets: 16-byte cells) at bits + dt_off / gt_off; inter[out_off + d * G + g] = number of
+ *   elements set in both.  Job j owns blocks [block_begin_j, block_begin_j + rsis_mask_intersect_blocks(D, G, stride)); inter[inter_len]
+ *   is zeroed by the call.
+ * rsis_coco_iou_batch: cells[c] = {dt_begin, D, gt_begin, G, inter_off, inter_ld, iou_off, 0}:
+ *   ious[iou_off + d * G + g] = i / (gt_crowd ? dt_marea : dt_marea + gt_marea - i), 0 for i = 0, with
+ *   i = inter[inter_off + dt_row[dt_begin + d] * inter_ld + gt_col[gt_begin + g]].
+ * rsis_coco_match_batch: cells[c] = {iou_off, D, G, dt_begin, gt_begin, dt_out, gt_out, area range}: greedy matching of D detections (in
+ *   score order) against G ground truths in ignored-last order (gperm[gt_begin + g] = column of the IoU matrix, gflag = ignore |
+ *   iscrowd << 1), for T <= 64 thresholds thrs[T]: dtm / dti[(dt_out + d) * T + t] = position of the matched ground truth + 1 (0: none) /
+ *   ignore flag (an unmatched detection: dt_area outside arng[range]), gtm[(gt_out + g) * T + t] = position of the detection + 1.
+ * rsis_rle_from_string: HOST function, inverse of rsis_rle_to_string: returns the number of counts, negated when cap is too small. */
+int rsis_mask_pack_bits(const unsigned char* masks, int n, long len, unsigned long long* bits, long stride, unsigned int* area, void* stream);
+int rsis_rle_to_bits(const unsigned int* counts, long counts_len, const long long* desc, int n, unsigned int* ends, unsigned long long* bits,
+                     long bits_len, unsigned int* area, void* stream);
+long rsis_mask_intersect_blocks(long D, long G, long stride);
+int rsis_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks,
+                              unsigned int* inter, long inter_len, void* stream);
+int rsis_coco_iou_batch(const long long* cells, int ncells, const unsigned int* inter, long inter_len, const int* dt_row,
+                        const unsigned int* dt_marea, long ndt, const int* gt_col, const unsigned int* gt_marea, const int* gt_crowd, long ngt,
+                        double* ious, long ious_len, void* stream);
+int rsis_coco_match_batch(const long long* cells, int ncells, const double* ious, long ious_len, const int* gperm, const int* gflag, long ngt,
+                          const double* dt_area, long ndt, const double* arng, int nrng, const double* thrs, int T, int* dtm, int* dti,
+                          long dt_out_len, int* gtm, long gt_out_len, void* stream);
+int rsis_rle_from_string(const char* s, unsigned int* counts, int cap);
+
 /* ---- channel-blocked bf16 activations: the storage half of the bf16 path (BASELINE.json configs[2..4]) --------------------------
  * A logical [B][C][H][W] tensor stored as bf16 [B][C/8][H][W][8] ("blk": the 8 channels of a pixel are one 16-byte cell, C % 8 == 0).
  * The reference has no counterpart (fp32 NCHW throughout); these entry points serve the ResNet-101 trunk of

@@ -157,6 +157,13 @@ SIGNATURES = {
     "rsis_rle_encode": (_i, [_vp, _i, _l, _vp, _i, _vp, _vp]),
     "rsis_largest_component": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rsis_rle_to_string": (_i, [_vp, _i, ctypes.c_char_p, _i]),
+    "rsis_mask_pack_bits": (_i, [_vp, _i, _l, _vp, _l, _vp, _vp]),
+    "rsis_rle_to_bits": (_i, [_vp, _l, _vp, _i, _vp, _vp, _l, _vp, _vp]),
+    "rsis_mask_intersect_blocks": (_l, [_l, _l, _l]),
+    "rsis_mask_intersect_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp]),
+    "rsis_coco_iou_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp]),
+    "rsis_coco_match_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _i, _vp, _i, _vp, _vp, _l, _vp, _l, _vp]),
+    "rsis_rle_from_string": (_i, [ctypes.c_char_p, _vp, _i]),
     "rsis_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "rsis_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _vp]),
     "rsis_rmsprop_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp]),

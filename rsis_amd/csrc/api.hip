@@ -73,6 +73,15 @@ int rsis_l_mask_resize_threshold(const float*, int, int, int, const unsigned cha
 int rsis_l_rle_encode(const unsigned char*, int, long, unsigned int*, int, int*, hipStream_t);
 int rsis_l_rle_to_string(const unsigned int*, int, char*, int);
 int rsis_l_largest_component(const unsigned char*, unsigned char*, int*, int*, int*, int, int, int, hipStream_t);
+int rsis_l_mask_pack_bits(const unsigned char*, int, long, unsigned long long*, long, unsigned int*, hipStream_t);
+int rsis_l_rle_to_bits(const unsigned int*, long, const long long*, int, unsigned int*, unsigned long long*, long, unsigned int*, hipStream_t);
+long rsis_l_mask_intersect_blocks(long, long, long);
+int rsis_l_mask_intersect_batch(const unsigned long long*, long, const long long*, int, int, unsigned int*, long, hipStream_t);
+int rsis_l_coco_iou_batch(const long long*, int, const unsigned int*, long, const int*, const unsigned int*, long, const int*, const unsigned int*,
+                          const int*, long, double*, long, hipStream_t);
+int rsis_l_coco_match_batch(const long long*, int, const double*, long, const int*, const int*, long, const double*, long, const double*, int,
+                            const double*, int, int*, int*, long, int*, long, hipStream_t);
+int rsis_l_rle_from_string(const char*, unsigned int*, int);
 int rsis_l_heads_fwd(const float* const*, const int*, int, int, const float*, const float*, int, const float*, const float*, float*, float*,
                      hipStream_t, const unsigned long long* const* keys = nullptr, float* const* side_out = nullptr, int* const* arg_out = nullptr);
 int rsis_l_heads_bwd(const float* const*, const int*, int, int, const float*, int, const float*, const float*, const float*, const float*,
@@ -805,6 +814,56 @@ int rsis_rle_encode(const unsigned char* masks, int n, long len, unsigned int* c
 int rsis_rle_to_string(const unsigned int* counts, int m, char* out, int cap) {
   if (!counts || !out || m < 0 || cap < 1) return -1;
   return rsis_l_rle_to_string(counts, m, out, cap);
+}
+
+int rsis_mask_pack_bits(const unsigned char* masks, int n, long len, unsigned long long* bits, long stride, unsigned int* area, void* stream) {
+  if (!masks || !bits || !area || n < 1 || n > 65535 || len < 1 || len >= (1L << 32) || stride < (len + 63) / 64) return RSIS_ERR_ARG;
+  return rsis_l_mask_pack_bits(masks, n, len, bits, stride, area, (hipStream_t)stream);
+}
+
+int rsis_rle_to_bits(const unsigned int* counts, long counts_len, const long long* desc, int n, unsigned int* ends, unsigned long long* bits,
+                     long bits_len, unsigned int* area, void* stream) {
+  if (!counts || !desc || !ends || !bits || !area || n < 1 || counts_len < 1 || bits_len < 1) return RSIS_ERR_ARG;
+  return rsis_l_rle_to_bits(counts, counts_len, desc, n, ends, bits, bits_len, area, (hipStream_t)stream);
+}
+
+long rsis_mask_intersect_blocks(long D, long G, long stride) {
+  if (D < 1 || G < 1 || stride < 1) return 0;
+  return rsis_l_mask_intersect_blocks(D, G, stride);
+}
+
+int rsis_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks,
+                              unsigned int* inter, long inter_len, void* stream) {
+  if (!bits || !jobs || !inter || njobs < 1 || total_blocks < 1 || bits_len < 1 || inter_len < 1) return RSIS_ERR_ARG;
+  return rsis_l_mask_intersect_batch(bits, bits_len, jobs, njobs, total_blocks, inter, inter_len, (hipStream_t)stream);
+}
+
+int rsis_coco_iou_batch(const long long* cells, int ncells, const unsigned int* inter, long inter_len, const int* dt_row,
+                        const unsigned int* dt_marea, long ndt, const int* gt_col, const unsigned int* gt_marea, const int* gt_crowd, long ngt,
+                        double* ious, long ious_len, void* stream) {
+  if (!cells || !inter || !dt_row || !dt_marea || !gt_col || !gt_marea || !gt_crowd || !ious || ncells < 1 || inter_len < 1 || ndt < 1 ||
+      ngt < 1 || ious_len < 1)
+    return RSIS_ERR_ARG;
+  return rsis_l_coco_iou_batch(cells, ncells, inter, inter_len, dt_row, dt_marea, ndt, gt_col, gt_marea, gt_crowd, ngt, ious, ious_len,
+                               (hipStream_t)stream);
+}
+
+int rsis_coco_match_batch(const long long* cells, int ncells, const double* ious, long ious_len, const int* gperm, const int* gflag, long ngt,
+                          const double* dt_area, long ndt, const double* arng, int nrng, const double* thrs, int T, int* dtm, int* dti,
+                          long dt_out_len, int* gtm, long gt_out_len, void* stream) {
+  if (!cells || ncells < 1 || !arng || nrng < 1 || !thrs || T < 1 || T > 64 || ious_len < 0 || ngt < 0 || ndt < 0 || dt_out_len < 0 ||
+      gt_out_len < 0)
+    return RSIS_ERR_ARG;
+  if ((ious_len > 0 && !ious) || (ngt > 0 && (!gperm || !gflag)) || (ndt > 0 && !dt_area) || (dt_out_len > 0 && (!dtm || !dti)) ||
+      (gt_out_len > 0 && !gtm))
+    return RSIS_ERR_ARG;
+  return rsis_l_coco_match_batch(cells, ncells, ious, ious_len, gperm, gflag, ngt, dt_area, ndt, arng, nrng, thrs, T, dtm, dti, dt_out_len, gtm,
+                                 gt_out_len, (hipStream_t)stream);
+}
+
+int rsis_rle_from_string(const char* s, unsigned int* counts, int cap) {
+  if (!s || cap < 0 || (cap > 0 && !counts)) return 0;
+  return rsis_l_rle_from_string(s, counts, cap);
 }
 
 int rsis_heads_fwd(const float* const* side, const int* Cside, int nside, int B, const float* Wc, const float* bc, int ncls,

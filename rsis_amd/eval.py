@@ -7,8 +7,13 @@ eval.py:129-142) with the reference's thresholds (-stop_th, -class_th, -mask_th,
     python -m rsis_amd.eval --synthetic -model_name <name> -batch_size 32 -maxseqlen 10 [-eval_split test]
 
 writes <models_root>/<model_name>/<model_name>_<eval_split>_predictions.json (list of {image_id, category_id, category_name,
-segmentation: COCO RLE, score}).  Not built (out of scope): the dataset readers (so only `--synthetic`
-inputs are wired), pycocotools' COCOeval AP computation, the matplotlib display path.
+segmentation: COCO RLE, score}) and then, unless --no_run_coco_eval, evaluates them as eval.py:375-398 does (COCOeval 'segm' with
+maxDets = [1, -max_dets, 100], useCats = not --ignore_cats, all classes together, then one by one with --all_classes), on the
+device (rsis_amd/cocoeval.py): the thresholded masks are bit-packed where they lie, one row per predicted MASK (the C - 1 records
+of a mask share it), the ground truth comes from the loader's targets.  The 13 stats are printed in the reference's format and
+written to <model_name>_<eval_split>_cocoeval.json.  `-cat_id` is parsed and has no effect, as in the reference (eval.py:381-385
+overwrites it).  Not built (out of scope): the dataset readers (so only `--synthetic` inputs are wired; a
+ground-truth FILE is evaluated with `python -m rsis_amd.cocoeval`), the matplotlib display path.
 """
 import json
 import os
@@ -18,6 +23,7 @@ import numpy as np
 import torch
 
 from .args import get_parser
+from .cocoeval import COCOEvalDevice, run_reference_protocol
 from .eval_post import encode_masks, resize_mask  # noqa: F401  (resize_mask: reference signature, eval.py:96-127)
 from .modules.model import RSIS, FeatureExtractor
 from .synthetic import SyntheticLoader
@@ -70,7 +76,8 @@ class Evaluate(object):
         """eval.py:254-345: one record per (instance, class) with score = class probability * objectness"""
         args = self.args
         predictions, shown, acc = [], [], 0
-        for inputs, _y_mask, _y_class, _sw_mask, _sw_class in self.loader:
+        coco = self.coco = None if getattr(args, "no_run_coco_eval", False) else COCOEvalDevice()
+        for inputs, y_mask, y_class, sw_mask, _sw_class in self.loader:
             x = inputs
             out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)       # eval.py:262
             scores = out_scores.cpu().numpy()
@@ -80,7 +87,8 @@ class Evaluate(object):
             for s in range(out_masks.shape[0]):
                 sample_idx = self.sample_list[s + acc]
                 # all T masks of the image in one launch each: resample + threshold + area, then run-length encoding
-                segs, areas, raws = encode_masks(out_masks[s], h, w, args.mask_th, None)
+                segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, None, want_bits=True)
+                rows, cats, recscores = [], [], []                  # of the records that reach the predictions file
                 for i in range(out_masks.shape[1]):
                     objectness = float(stops[s][i][0])
                     if objectness < args.stop_th:                  # eval.py:303-304
@@ -96,6 +104,21 @@ class Evaluate(object):
                             shown.append(create_annotation(args, sample_idx, _jsonable(raws[i]), cls_id, score, self.class_names,
                                                            is_valid))
                         predictions.append(ann)
+                        rows.append(i)
+                        cats.append(cls_id)
+                        recscores.append(score)
+                if coco is not None:
+                    # ground truth of the image from the loader's targets, in the detections' (column-major) element order
+                    n_gt = int((sw_mask[s] > 0).sum())
+                    gt_m = (y_mask[s, :n_gt].reshape(n_gt, h, w).transpose(1, 2) > 0.5).to(torch.uint8).reshape(n_gt, h * w)
+                    if n_gt:
+                        coco.add_gt_masks(sample_idx, gt_m, [int(c) for c in y_class[s, :n_gt].cpu()])
+                    if rows:
+                        kept = sorted(set(rows))                     # only the masks that have records go into the pool
+                        sel = torch.as_tensor(kept, device=bits[0].device)
+                        pos = {r: j for j, r in enumerate(kept)}
+                        coco.add_dt_masks(sample_idx, None, cats, recscores, rows=[pos[r] for r in rows],
+                                          bits=(bits[0][sel], bits[1][sel], bits[2]))
             acc += out_masks.shape[0]
         return predictions, shown
 
@@ -108,6 +131,21 @@ class Evaluate(object):
             json.dump(predictions, f)
         print("%d prediction records (%d above -class_th for display) from %d images -> %s" %
               (len(predictions), len(shown), len(self.sample_list), path))
+        if self.coco is not None:                                    # eval.py:375-398
+            args = self.args
+            cat_ids = list(range(1, len(self.class_names)))
+            res = run_reference_protocol(self.coco, self.sample_list, cat_ids, args.max_dets, args.use_cats, args.all_classes,
+                                         self.class_names)
+            p = self.coco.params
+            res["params"] = {"maxDets": [int(v) for v in p.maxDets], "useCats": int(bool(args.use_cats)), "catIds": cat_ids,
+                             "iouThrs": [float(v) for v in p.iouThrs], "recThrs": [float(v) for v in p.recThrs],
+                             "areaRng": [[float(v) for v in r] for r in p.areaRng], "areaRngLbl": list(p.areaRngLbl),
+                             "images": len(self.sample_list)}
+            epath = os.path.join(out_dir, "%s_%s_cocoeval.json" % (self.args.model_name, self.split))
+            with open(epath, "w") as f:
+                json.dump(res, f)
+            print("COCO segm evaluation -> %s" % epath)
+            self.coco_stats = res
         return predictions
 
 

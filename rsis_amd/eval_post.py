@@ -12,10 +12,11 @@ import torch
 from ._lib import check, lib, ptr, stream
 
 
-def encode_masks(prob, height, width, th, ignore=None, want_raw=True):
+def encode_masks(prob, height, width, th, ignore=None, want_raw=True, want_bits=False):
     """prob: (n, Hm, Wm) CUDA fp32 mask probabilities of one image -> (segs, areas, raws):
     segs / raws: lists of n COCO RLE dicts {'size': [height, width], 'counts': bytes} (raws: before the ignore mask; None when
-    want_raw is False), areas: (n,) int64 numpy array of the set-pixel counts of segs."""
+    want_raw is False), areas: (n,) int64 numpy array of the set-pixel counts of segs.  With want_bits a fourth value follows: the
+    thresholded masks of segs bit-packed on the device, (words, areas, height * width) as rsis_amd.cocoeval takes them."""
     L = lib()
     prob = prob.detach()
     if not prob.is_cuda or prob.dtype != torch.float32:
@@ -36,6 +37,10 @@ def encode_masks(prob, height, width, th, ignore=None, want_raw=True):
     raws = None
     if want_raw:
         raws = _rle_dicts(L, raw, n, hw, height, width) if raw is not None else [dict(d) for d in segs]
+    if want_bits:
+        from .cocoeval import pack_bits
+        words, barea = pack_bits(seg)
+        return segs, area.cpu().numpy().astype(np.int64), raws, (words, barea, hw)
     return segs, area.cpu().numpy().astype(np.int64), raws
 
 
