@@ -420,6 +420,29 @@ int rsis_coco_match_batch(const long long* cells, int ncells, const double* ious
                           long dt_out_len, int* gtm, long gt_out_len, void* stream);
 int rsis_rle_from_string(const char* s, unsigned int* counts, int cap);
 
+/* ---- CVPPP leaf segmentation measures of N pairs of 8-bit label images (result `in`, ground truth `gt`, equal pixel counts per pair;
+ * the challenge's Matlab scripts, reference src/CVPPP/, restated; rsis_amd/cvppp_eval.py states the definitions).  The images of a call
+ * lie in ONE byte pool (16-byte aligned base; a pair may start at any offset).  Both launches read the same job table from DEVICE
+ * memory, int64, 8 entries per pair: jobs[p] = {in_off, gt_off, npix, table_off, block_begin, 0, 0, 0}: the images are pool + in_off /
+ * gt_off, npix bytes each (1 <= npix < 2^32); the pair's table is counts + table_off (a multiple of 4), 65536 uint32 that no other pair
+ * shares; pair p owns blocks [block_begin_p, block_begin_p + rsis_label_contingency_blocks(npix_p)) of the contingency launch,
+ * total_blocks = their sum.  A pair whose offsets do not fit pool_len / counts_len is skipped by both launches (its table and its
+ * scores stay zero).  All results are integers or float64 operations on integers in a fixed order: they do not depend on the schedule
+ * and are the same bits from run to run.
+ * rsis_label_contingency_batch: counts[table_off + i * 256 + j] = number of pixels with in == i and gt == j (the marginals follow from
+ *   them); counts[counts_len] is zeroed by the call.  Every pixel is read once; counts are merged in registers and in a block-private
+ *   64 x 64 LDS window (labels 0 .. 63) before one integer atomic per non-zero cell and block, labels outside the window add per run.
+ * rsis_label_scores_batch: scores[p][6] (zeroed by the call) = {SymmetricBestDice, FgBgDice, AbsDiffFGLabels, DiffFGLabels,
+ *   BestDice(in, gt), BestDice(gt, in)} with n_i / m_j the marginals, lo / hi the smallest / largest value present in an image,
+ *   Dice(i, j) = 2 o_ij / (n_i + m_j) (0 / 0 counts as 0), BestDice(in, gt) = sum over EVERY i in lo_in .. hi_in, ascending, of
+ *   max_{j in lo_gt .. hi_gt} Dice(i, j), divided by hi_in - lo_in + 1; SymmetricBestDice the smaller of the two; FgBgDice =
+ *   2 |F_in and F_gt| / (|F_in| + |F_gt|), F_a = {a > lo_a}, NaN when both images are constant; DiffFGLabels = (hi_in - lo_in) -
+ *   (hi_gt - lo_gt). */
+long rsis_label_contingency_blocks(long npix);
+int rsis_label_contingency_batch(const unsigned char* pool, long pool_len, const long long* jobs, int njobs, int total_blocks,
+                                 unsigned int* counts, long counts_len, void* stream);
+int rsis_label_scores_batch(const unsigned int* counts, long counts_len, const long long* jobs, int njobs, double* scores, void* stream);
+
 /* ---- channel-blocked bf16 activations: the storage half of the bf16 path (BASELINE.json configs[2..4]) --------------------------
  * A logical [B][C][H][W] tensor stored as bf16 [B][C/8][H][W][8] ("blk": the 8 channels of a pixel are one 16-byte cell, C % 8 == 0).
  * The reference has no counterpart (fp32 NCHW throughout); these entry points serve the ResNet-101 trunk of

@@ -164,6 +164,9 @@ SIGNATURES = {
     "rsis_coco_iou_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_coco_match_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _i, _vp, _i, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_rle_from_string": (_i, [ctypes.c_char_p, _vp, _i]),
+    "rsis_label_contingency_blocks": (_l, [_l]),
+    "rsis_label_contingency_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp]),
+    "rsis_label_scores_batch": (_i, [_vp, _l, _vp, _i, _vp, _vp]),
     "rsis_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "rsis_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _vp]),
     "rsis_rmsprop_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp]),

@@ -82,6 +82,9 @@ int rsis_l_coco_iou_batch(const long long*, int, const unsigned int*, long, cons
 int rsis_l_coco_match_batch(const long long*, int, const double*, long, const int*, const int*, long, const double*, long, const double*, int,
                             const double*, int, int*, int*, long, int*, long, hipStream_t);
 int rsis_l_rle_from_string(const char*, unsigned int*, int);
+long rsis_l_label_contingency_blocks(long);
+int rsis_l_label_contingency_batch(const unsigned char*, long, const long long*, int, int, unsigned int*, long, hipStream_t);
+int rsis_l_label_scores_batch(const unsigned int*, long, const long long*, int, double*, hipStream_t);
 int rsis_l_heads_fwd(const float* const*, const int*, int, int, const float*, const float*, int, const float*, const float*, float*, float*,
                      hipStream_t, const unsigned long long* const* keys = nullptr, float* const* side_out = nullptr, int* const* arg_out = nullptr);
 int rsis_l_heads_bwd(const float* const*, const int*, int, int, const float*, int, const float*, const float*, const float*, const float*,
@@ -864,6 +867,24 @@ int rsis_coco_match_batch(const long long* cells, int ncells, const double* ious
 int rsis_rle_from_string(const char* s, unsigned int* counts, int cap) {
   if (!s || cap < 0 || (cap > 0 && !counts)) return 0;
   return rsis_l_rle_from_string(s, counts, cap);
+}
+
+long rsis_label_contingency_blocks(long npix) {
+  if (npix < 1 || npix >= (1L << 32)) return 0;
+  return rsis_l_label_contingency_blocks(npix);
+}
+
+int rsis_label_contingency_batch(const unsigned char* pool, long pool_len, const long long* jobs, int njobs, int total_blocks,
+                                 unsigned int* counts, long counts_len, void* stream) {
+  if (!pool || ((uintptr_t)pool & 15) || !jobs || !counts || ((uintptr_t)counts & 15) || njobs < 1 || total_blocks < 1 || pool_len < 1 ||
+      counts_len < 65536)
+    return RSIS_ERR_ARG;
+  return rsis_l_label_contingency_batch(pool, pool_len, jobs, njobs, total_blocks, counts, counts_len, (hipStream_t)stream);
+}
+
+int rsis_label_scores_batch(const unsigned int* counts, long counts_len, const long long* jobs, int njobs, double* scores, void* stream) {
+  if (!counts || ((uintptr_t)counts & 15) || !jobs || !scores || njobs < 1 || counts_len < 65536) return RSIS_ERR_ARG;
+  return rsis_l_label_scores_batch(counts, counts_len, jobs, njobs, scores, (hipStream_t)stream);
 }
 
 int rsis_heads_fwd(const float* const* side, const int* Cside, int nside, int B, const float* Wc, const float* bc, int ncls,

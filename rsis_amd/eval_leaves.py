@@ -6,7 +6,10 @@ checkpoint -> `test()` over the -eval_split of the leaves directory -> one 8-bit
            -maxseqlen 16 -gt_maxseqlen 16 -imsize 256 --resize [-dtype bf16]
 
 The label image itself is `rsis_amd.eval_post.leaves_label_image` (the reference's per-mask bytescale + bilinear resize + threshold,
-later timesteps overwriting earlier ones).  Deviations from the reference script, all deliberate:
+later timesteps overwriting earlier ones).  When the split has ground truth (train / val) the files just written are then scored with the
+challenge's measures on the device (`rsis_amd.cvppp_eval`: SymmetricBestDice, FgBgDice, |DiC|, DiC; the reference ran the Matlab scripts
+of src/CVPPP by hand) and `<model_name>_A1_results.csv` appears next to the A1 folder.
+Deviations from the reference script, all deliberate:
   * the last, short batch is evaluated sample by sample that exist (the reference indexes `range(batch_size)` past it and raises);
   * `-eval_split test` reads `-leaves_test_dir` and needs no ground truth (as the reference);
   * no matplotlib display path.
@@ -56,11 +59,26 @@ class Evaluate(object):
         print("%d label images -> %s" % (len(written), results_dir))
         return written
 
+    def score(self, written):
+        """the CVPPP measures of the label images `create_figures` returned against the split's ground truth: prints the summary rows,
+        writes <model_name>_A1_results.csv next to the A1 folder and returns (plant numbers, (N, 6) scores); None for a split without
+        ground truth (-eval_split test)"""
+        from . import cvppp_eval
+        if not self.dataset.gt_files:
+            print("split %r has no ground truth: nothing to score" % self.split)
+            return None
+        numbers, scores = cvppp_eval.evaluate_files(written, self.dataset.gt_files)
+        cvppp_eval.print_summary(scores)
+        out = os.path.join(self.args.models_root, self.args.model_name, self.args.model_name + "_results")
+        print("%d images -> %s" % (len(numbers), cvppp_eval.write_result_table(out, self.args.model_name, numbers, scores)))
+        return numbers, scores
+
 
 if __name__ == "__main__":
     a = get_parser().parse_args()
     torch.manual_seed(a.seed)
     if not a.use_gpu or not torch.cuda.is_available():
         raise SystemExit("rsis_amd.eval_leaves needs the GPU: the HIP library is the only compute path")
-    Evaluate(a).create_figures()
+    ev = Evaluate(a)
+    ev.score(ev.create_figures())
     sys.exit(0)
