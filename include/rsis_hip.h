@@ -443,6 +443,28 @@ int rsis_label_contingency_batch(const unsigned char* pool, long pool_len, const
                                  unsigned int* counts, long counts_len, void* stream);
 int rsis_label_scores_batch(const unsigned int* counts, long counts_len, const long long* jobs, int njobs, double* scores, void* stream);
 
+/* ---- Cityscapes instance-level evaluation: joint pixel counts of P binary masks against one 16-bit instance-id image, for all images of
+ * a call (rsis_amd/cityscapes_eval.py states the measure; matching and AP are host float64).  The id images lie in ONE pool (16-byte
+ * aligned base, pool_len BYTES, a multiple of 16; an image may start at any even byte).  Both launches read one job table from DEVICE
+ * memory, int64, 16 entries per image: jobs[j] = {gt_off (bytes), npix, lut_off, bits_off, stride, P, S, counts_off, block_begin,
+ * presence_block_begin, 0 ..}: 1 <= npix < 2^32 ids at pool + gt_off; flags + lut_off / lut + lut_off are the image's 65536 presence
+ * bytes / id -> slot entries; its P >= 0 masks are bits + bits_off + p * stride (64-bit words, stride >= ceil(npix / 64), the layout of
+ * rsis_mask_pack_bits; bits may be NULL with bits_len 0 when no image has a mask); its table is counts + counts_off, (P + 1) * S uint32
+ * that no other image shares, 1 <= S <= 65535.  Image j owns blocks [block_begin_j, block_begin_j + rsis_inst_overlap_blocks(npix_j,
+ * P_j)) of the overlap launch and [presence_block_begin_j, + rsis_inst_overlap_blocks(npix_j, 0)) of the presence launch; total_blocks
+ * = their sum.  An image whose entries do not fit the stated buffer lengths is skipped (its flags / table stay zero).  Integer atomics
+ * only: the results do not depend on the schedule.
+ * rsis_inst_presence_batch: flags[lut_off + v] = 1 for every value v that occurs in the image; flags[flags_len] is zeroed by the call.
+ * rsis_inst_overlap_batch: counts[counts_off + p * S + s] = #{i : bit i of mask p set and lut[gt[i]] == s} for p < P, and row p = P the
+ *   histogram #{i : lut[gt[i]] == s}; a pixel whose lut entry is >= S is not counted; counts[counts_len] is zeroed by the call.  gt is
+ *   read once per group of 64 masks; counts are merged in registers and in a block-private LDS window (64 masks + histogram) x 64 slots
+ *   before one atomic per non-zero cell and block, slots outside the window add per run. */
+long rsis_inst_overlap_blocks(long npix, long P);
+int rsis_inst_presence_batch(const void* pool, long pool_len, const long long* jobs, int njobs, int total_blocks, unsigned char* flags,
+                             long flags_len, void* stream);
+int rsis_inst_overlap_batch(const void* pool, long pool_len, const long long* jobs, int njobs, int total_blocks, const unsigned short* lut,
+                            long lut_len, const unsigned long long* bits, long bits_len, unsigned int* counts, long counts_len, void* stream);
+
 /* ---- channel-blocked bf16 activations: the storage half of the bf16 path (BASELINE.json configs[2..4]) --------------------------
  * A logical [B][C][H][W] tensor stored as bf16 [B][C/8][H][W][8] ("blk": the 8 channels of a pixel are one 16-byte cell, C % 8 == 0).
  * The reference has no counterpart (fp32 NCHW throughout); these entry points serve the ResNet-101 trunk of

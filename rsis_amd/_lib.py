@@ -167,6 +167,9 @@ SIGNATURES = {
     "rsis_label_contingency_blocks": (_l, [_l]),
     "rsis_label_contingency_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp]),
     "rsis_label_scores_batch": (_i, [_vp, _l, _vp, _i, _vp, _vp]),
+    "rsis_inst_overlap_blocks": (_l, [_l, _l]),
+    "rsis_inst_presence_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp]),
+    "rsis_inst_overlap_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp, _l, _vp, _l, _vp]),
     "rsis_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "rsis_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _vp]),
     "rsis_rmsprop_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp]),

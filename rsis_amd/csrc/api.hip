@@ -85,6 +85,10 @@ int rsis_l_rle_from_string(const char*, unsigned int*, int);
 long rsis_l_label_contingency_blocks(long);
 int rsis_l_label_contingency_batch(const unsigned char*, long, const long long*, int, int, unsigned int*, long, hipStream_t);
 int rsis_l_label_scores_batch(const unsigned int*, long, const long long*, int, double*, hipStream_t);
+long rsis_l_inst_overlap_blocks(long, long);
+int rsis_l_inst_presence_batch(const unsigned char*, long, const long long*, int, int, unsigned char*, long, hipStream_t);
+int rsis_l_inst_overlap_batch(const unsigned char*, long, const long long*, int, int, const unsigned short*, long, const unsigned long long*, long,
+                              unsigned int*, long, hipStream_t);
 int rsis_l_heads_fwd(const float* const*, const int*, int, int, const float*, const float*, int, const float*, const float*, float*, float*,
                      hipStream_t, const unsigned long long* const* keys = nullptr, float* const* side_out = nullptr, int* const* arg_out = nullptr);
 int rsis_l_heads_bwd(const float* const*, const int*, int, int, const float*, int, const float*, const float*, const float*, const float*,
@@ -885,6 +889,27 @@ int rsis_label_contingency_batch(const unsigned char* pool, long pool_len, const
 int rsis_label_scores_batch(const unsigned int* counts, long counts_len, const long long* jobs, int njobs, double* scores, void* stream) {
   if (!counts || ((uintptr_t)counts & 15) || !jobs || !scores || njobs < 1 || counts_len < 65536) return RSIS_ERR_ARG;
   return rsis_l_label_scores_batch(counts, counts_len, jobs, njobs, scores, (hipStream_t)stream);
+}
+
+long rsis_inst_overlap_blocks(long npix, long P) {
+  if (npix < 1 || npix >= (1L << 32) || P < 0 || P >= (1L << 31)) return 0;
+  return rsis_l_inst_overlap_blocks(npix, P);
+}
+
+int rsis_inst_presence_batch(const void* pool, long pool_len, const long long* jobs, int njobs, int total_blocks, unsigned char* flags,
+                             long flags_len, void* stream) {
+  if (!pool || ((uintptr_t)pool & 15) || (pool_len & 15) || !jobs || !flags || njobs < 1 || total_blocks < 1 || pool_len < 16 || flags_len < 65536)
+    return RSIS_ERR_ARG;
+  return rsis_l_inst_presence_batch((const unsigned char*)pool, pool_len, jobs, njobs, total_blocks, flags, flags_len, (hipStream_t)stream);
+}
+
+int rsis_inst_overlap_batch(const void* pool, long pool_len, const long long* jobs, int njobs, int total_blocks, const unsigned short* lut,
+                            long lut_len, const unsigned long long* bits, long bits_len, unsigned int* counts, long counts_len, void* stream) {
+  if (!pool || ((uintptr_t)pool & 15) || (pool_len & 15) || !jobs || !lut || !counts || njobs < 1 || total_blocks < 1 || pool_len < 16 ||
+      lut_len < 65536 || bits_len < 0 || (bits_len > 0 && (!bits || ((uintptr_t)bits & 7))) || counts_len < 1)
+    return RSIS_ERR_ARG;
+  return rsis_l_inst_overlap_batch((const unsigned char*)pool, pool_len, jobs, njobs, total_blocks, lut, lut_len, bits, bits_len, counts, counts_len,
+                                   (hipStream_t)stream);
 }
 
 int rsis_heads_fwd(const float* const* side, const int* Cside, int nside, int B, const float* Wc, const float* bc, int ncls,

@@ -11,17 +11,46 @@ the same resize path.  Everything after `test()` is the reference's procedure, t
 `rsis_amd.eval_post.write_cityscapes_results`.  Deviations from the reference script: an empty mask is written as an
 all-zero PNG (the reference reuses a stale `max_label` from the previous mask); scores are formatted from float64 (the reference
 prints numpy float32 `str`), i.e. more digits of the same number.
+
+The reference stops here and leaves the numbers to the benchmark's evaluation script.  This driver goes on: unless `--no_run_coco_eval`
+is given (the flag the reference's scripts pass to skip scoring; same meaning here) the masks just written are scored against the
+ground truth with `rsis_amd.cityscapes_eval` (AP, AP50% per class; pixel counting on the device), the table is printed and
+`<models_root>/<model_name>/<model_name>_cityscapes_eval.json` is written.  With `--synthetic` the ground truth is stored the way the
+benchmark stores it, `<model_name>_gt/<sample>_gtFine_instanceIds.png` (16-bit, at the "original" size by pixel replication):
+instance k of class c >= 1 of the loader's targets has the value CITYSCAPES_CLASS_IDS[c - 1] * 1000 + k, the earlier instance keeps a
+contested pixel, the background is 7 (road: neither void nor an instance; 0 would make every false positive "ignored").
+`python -m rsis_amd.cityscapes_eval --results <..._results> --gt <..._gt>` gives the same JSON from the files.
 """
 import os
 import sys
 
+import numpy as np
 import torch
 
 from .args import get_parser
 from .eval import load_models
-from .eval_post import write_cityscapes_results
+from .eval_post import CITYSCAPES_CLASS_IDS, write_cityscapes_results
 from .synthetic import SyntheticLoader
 from .test import test
+
+
+BACKGROUND_ID = 7
+
+
+def synthetic_instance_ids(y_mask, y_class, height, width, scale=2):
+    """(T, height * width) 0 / 1 masks and (T,) classes of one image's targets -> (scale * height, scale * width) uint16 instance-id
+    image (module docstring)"""
+    m = np.asarray(y_mask.detach().cpu()).reshape(-1, height, width) > 0.5
+    c = np.asarray(y_class.detach().cpu()).reshape(-1)
+    gt = np.full((height, width), BACKGROUND_ID, np.uint16)
+    free = np.ones((height, width), bool)
+    for k in range(m.shape[0]):
+        if c[k] < 1:
+            continue
+        cid = CITYSCAPES_CLASS_IDS[c[k] - 1] if c[k] - 1 < len(CITYSCAPES_CLASS_IDS) else int(c[k])
+        gt[m[k] & free] = cid * 1000 + k
+        free &= ~m[k]
+    return np.repeat(np.repeat(gt, scale, 0), scale, 1)
 
 
 class Evaluate(object):
@@ -39,18 +68,51 @@ class Evaluate(object):
         results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results")     # eval_cityscapes.py:99-104
         masks_dir = args.model_name + "_masks"
         os.makedirs(os.path.join(results_dir, masks_dir), exist_ok=True)
+        self.results_dir = results_dir
+        self.gt_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_gt")
+        os.makedirs(self.gt_dir, exist_ok=True)
+        do_score = not getattr(args, "no_run_coco_eval", False)
+        self.records = []
         print("Creating annotations for cityscapes validation...")
+        from PIL import Image
+        from . import cityscapes_eval
         acc, n_lines = 0, 0
-        for x, _y_mask, _y_class, _sw_mask, _sw_class in self.loader:
+        for x, y_mask, y_class, _sw_mask, _sw_class in self.loader:
             out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)               # :108
             Hm, Wm = x.size(-2), x.size(-1)
+            gts, mask_sets, rows, labels, scores = [], [], [], [], []
             for s in range(out_masks.shape[0]):
-                lines = write_cityscapes_results(args, self.sample_list[s + acc], out_masks[s].view(self.T, Hm, Wm), out_scores[s],
-                                                 stop_probs[s], 2 * Hm, 2 * Wm, results_dir, masks_dir)
+                sample, masks = self.sample_list[s + acc], []
+                gt = synthetic_instance_ids(y_mask[s], y_class[s], Hm, Wm)
+                Image.fromarray(gt).save(os.path.join(self.gt_dir, sample + cityscapes_eval.GT_SUFFIX))
+                lines = write_cityscapes_results(args, sample, out_masks[s].view(self.T, Hm, Wm), out_scores[s],
+                                                 stop_probs[s], 2 * Hm, 2 * Wm, results_dir, masks_dir, collect=masks)
                 n_lines += len(lines)
+                gts.append(gt)
+                mask_sets.append(masks)
+                rows.append([q // (len(lines) // len(masks)) for q in range(len(lines))])
+                labels.append([int(l.split()[1]) for l in lines])
+                scores.append([float(l.split()[2]) for l in lines])
+            if do_score:                                           # the arrays that were just saved: nothing is read back
+                self.records += cityscapes_eval.score_image_sets(gts, mask_sets, rows, labels, scores)
             acc += out_masks.shape[0]
         print("%d result lines for %d images -> %s" % (n_lines, acc, results_dir))
         return n_lines
+
+    def score(self):
+        """AP / AP50% of what `create_figures` wrote: prints the table, writes <model_name>_cityscapes_eval.json next to the results folder
+        and returns the result dict; None under --no_run_coco_eval"""
+        from . import cityscapes_eval
+        args = self.args
+        if getattr(args, "no_run_coco_eval", False):
+            print("--no_run_coco_eval: the result files are not scored")
+            return None
+        aps = cityscapes_eval.evaluate_matches(self.records)
+        res = {"aps": aps, "averages": cityscapes_eval.compute_averages(aps), "images": len(self.records)}
+        sys.stdout.write(cityscapes_eval.summary(res["averages"]))
+        name = os.path.join(args.models_root, args.model_name, args.model_name + "_cityscapes_eval.json")
+        print("%d images -> %s" % (res["images"], cityscapes_eval.write_result_json(name, res)))
+        return res
 
 
 if __name__ == "__main__":
@@ -58,5 +120,7 @@ if __name__ == "__main__":
     torch.manual_seed(a.seed)
     if not a.use_gpu or not torch.cuda.is_available():
         raise SystemExit("rsis_amd.eval_cityscapes needs the GPU: the HIP library is the only compute path")
-    Evaluate(a).create_figures()
+    ev = Evaluate(a)
+    ev.create_figures()
+    ev.score()
     sys.exit(0)

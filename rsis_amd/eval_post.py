@@ -117,12 +117,13 @@ def imresize(a, size):
     return np.asarray(im.resize((int(size[1]), int(size[0])), resample=Image.BILINEAR))
 
 
-def write_cityscapes_results(args, sample_idx, out_masks, class_scores, stop_probs, height, width, results_dir, masks_dir):
+def write_cityscapes_results(args, sample_idx, out_masks, class_scores, stop_probs, height, width, results_dir, masks_dir, collect=None):
     """reference src/eval_cityscapes.py:118-167 for one image: per timestep the thresholded mask is reduced to its largest connected
     component (on the device: rsis_largest_component), scaled to 0 / 255, resized to the original image size and saved once per
     foreground class as `<masks_dir>/<sample>_<instance>.png`; `<results_dir>/<sample>.txt` gets one line `<png> <cityscapes class id>
     <class probability * objectness>` per (timestep, class) -- the format of the Cityscapes instance-level evaluation script.
-    out_masks: (T, Hm, Wm) CUDA probabilities, class_scores: (T, C), stop_probs: (T, 1).  Returns the lines written."""
+    out_masks: (T, Hm, Wm) CUDA probabilities, class_scores: (T, C), stop_probs: (T, 1).  Returns the lines written; a list given as
+    `collect` receives the T uint8 arrays that were saved (line q holds mask q // (C - 1)), for scoring without reading them back."""
     from PIL import Image
     abs_masks = os.path.join(results_dir, masks_dir)
     os.makedirs(abs_masks, exist_ok=True)
@@ -134,6 +135,8 @@ def write_cityscapes_results(args, sample_idx, out_masks, class_scores, stop_pro
     lines, instance_id = [], 0
     for t in range(T):
         mask = imresize(comp[t] * np.uint8(255), [height, width])
+        if collect is not None:
+            collect.append(mask)
         for i in range(cls.shape[1] - 1):                               # class 0 = <eos> (eval_cityscapes.py:156-162)
             name = "%s_%d.png" % (sample_idx, instance_id)
             score = cls[t][i + 1] * stop[t][0]
