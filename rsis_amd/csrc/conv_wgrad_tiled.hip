@@ -21,10 +21,45 @@
 // tile (128 MFMAs per wave for 3x3).  The spatial tile is as wide as the map allows (32x2 / 16x4 / 8x8 pixels for 3x3,
 // 32x1 / 16x2 / 8x4 for 1x1) so that dy / x rows are read as full 128-byte lines; maps that no tile shape divides use
 // conv_wgrad.hip.
+//
+// LIMB = 1 (the same kernels, another MFMA loop): the products run on v_mfma_f32_32x32x16_bf16.  The operands stay fp32 in LDS as the
+// DMA lands them; after the ds_reads that exist anyway every value is split IN REGISTERS into three bf16 limbs whose sum is the value
+// bit for bit (limb_split.h: by truncation; non-finite inputs give non-finite results, not necessarily of the same kind), and the
+// limb pairs (i, j) with i + j <= 2 -- the six products of weight >= 2^-16, each exact in the fp32 accumulator's product -- replace
+// the eight 64-cycle f32 MFMAs of a 16-pixel k-step by six 32-cycle ones.  Two consecutive step blocks g, g + 1 make one K16 step:
+// lane (r, h) uses the 4 + 4 pixels it already reads as elements j = 0..7 of its k = 8h + j fragment, A and B alike.  Which tile
+// configurations take this loop is a measured table (wg_limb_mask); RSIS_WGRAD_LIMBS=0 puts every job back on the f32 loop.
 #include "common.h"
+#include "limb_split.h"
 #include <stdlib.h>
+#include <string.h>
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;
+typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
+
+// limb pairs (A limb, B limb) of one K16 step, smallest weight first.  The first WG_LIMB_PRODUCTS are issued: 6 = the pairs with
+// i + j <= 2; 9 would be the exact product
+#define WG_LIMB_PRODUCTS 6
+[[maybe_unused]] __device__ constexpr int wg_limb_pa[9] = {2, 1, 0, 1, 0, 0, 2, 1, 2};
+[[maybe_unused]] __device__ constexpr int wg_limb_pb[9] = {0, 1, 2, 0, 1, 0, 1, 2, 2};
+
+// eight fp32 values (k = 0..7 of a lane's fragment) -> three bf16x8 limb fragments; element 2m sits in the low half of dword m
+__device__ __forceinline__ void wg_limb_pack8(const float (&v)[8], wg_bf16x8 (&out)[3]) {
+  wg_u32x4 q[3];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    float lo[3], hi[3];
+    rsis_limb_split3(v[2 * m], lo[0], lo[1], lo[2]);
+    rsis_limb_split3(v[2 * m + 1], hi[0], hi[1], hi[2]);
+    // (limb 0 is packed from v itself: the permute takes the high halves, the mask is only needed for the residual)
+    q[0][m] = __builtin_amdgcn_perm(__float_as_uint(v[2 * m + 1]), __float_as_uint(v[2 * m]), 0x07060302u);
+    q[1][m] = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(lo[1]), 0x07060302u);
+    q[2][m] = __builtin_amdgcn_perm(__float_as_uint(hi[2]), __float_as_uint(lo[2]), 0x07060302u);
+  }
+#pragma unroll
+  for (int l = 0; l < 3; ++l) out[l] = __builtin_bit_cast(wg_bf16x8, q[l]);
+}
 
 struct WgradTiledArgs {
   const float* dy;   // [B][CoutDy][H][W]
@@ -45,7 +80,7 @@ struct WgradTiledArgs {
 // 0.  The MFMA loop is unchanged (zeros add nothing); the tile grid rounds up.  RAG = 2: the map width is a multiple of 4 (28-pixel maps;
 // every 1x1 whose H * W is, since a 1x1 may walk the FLATTENED map): a dwordx4 group is inside or outside as a whole, so the one
 // DMA per group stays and only carries the two flag bits.
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0>
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
 __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__   // (the host pass only needs the launch stub; the buffer-resource builtins do not exist there)
   constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
@@ -61,7 +96,7 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
   constexpr int NA = BM * NG / 256;           // dwordx4 DMA per thread per tile (dy)
   constexpr int NB4 = KS == 1 ? BN * NG / 256 : 0;   // dwordx4 DMA per thread per tile (x, 1x1)
   constexpr int NB1 = KS == 1 ? 0 : XS / 256;        // dword DMA per thread per tile (x patch, 3x3)
-  static_assert(WGM * WGN * KSP == 4 && (BM * NG) % 256 == 0 && (KS == 3 || (BN * NG) % 256 == 0) && (NG / 2) % KSP == 0, "config");
+  static_assert(WGM * WGN * KSP == 4 && (BM * NG) % 256 == 0 && (KS == 3 || (BN * NG) % 256 == 0) && (NG / 2) % KSP == 0 && (NG / 2 / KSP) % 2 == 0, "config");
 
   __shared__ __attribute__((aligned(16))) float lds[2 * (AS + XS)];
   float* const As0 = lds;
@@ -232,6 +267,44 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
     {
       const float* As = As0 + cur * AS + arow;
       const float* Xs = Xs0 + cur * XS;
+      if constexpr (LIMB) {
+#pragma unroll
+        for (int g = 0; g < NG / 2 / KSP; g += 2) {       // step blocks g, g + 1 = one K16 step
+          wg_bf16x8 al[TM][3], bl[TN][3];
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(As + i * 32 * TP + sg[g]);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(As + i * 32 * TP + sg[g + 1]);
+            const float v[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+            wg_limb_pack8(v, al[i]);
+          }
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            float v[8];
+            if constexpr (KS == 1) {
+              const f32x4 b0 = *reinterpret_cast<const f32x4*>(Xs + xb[j] + sg[g]);
+              const f32x4 b1 = *reinterpret_cast<const f32x4*>(Xs + xb[j] + sg[g + 1]);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) { v[e] = b0[e]; v[4 + e] = b1[e]; }
+            } else {
+#pragma unroll
+              for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  v[4 * u + e] = Xs[xb[j] + (KSP == 1 ? ((g + u) / (TW / 8)) * PW + ((g + u) % (TW / 8)) * 8 : bo[g + u]) + e];
+            }
+            wg_limb_pack8(v, bl[j]);
+          }
+          // limb pairs outside, tiles inside: consecutive MFMAs never share an accumulator (where TM * TN > 1)
+#pragma unroll
+          for (int q = 0; q < WG_LIMB_PRODUCTS; ++q)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i][wg_limb_pa[q]], bl[j][wg_limb_pb[q]], acc[i][j], 0, 0, 0);
+        }
+      } else
 #pragma unroll
       for (int g = 0; g < NG / 2 / KSP; ++g) {
         f32x4 a4[TM];
@@ -293,9 +366,9 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
 #endif
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1>
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int LIMB = 0>
 __global__ __launch_bounds__(256) void conv_wgrad_tiled_kernel(const WgradTiledArgs p) {
-  wgrad_tiled_body<BM, BN, WGM, WGN, KS, TW, KSP>(p, blockIdx.x, blockIdx.y);
+  wgrad_tiled_body<BM, BN, WGM, WGN, KS, TW, KSP, 0, LIMB>(p, blockIdx.x, blockIdx.y);
 }
 
 // ---- grouped launch: the weight gradients of many layers in ONE grid (rsis_conv2d_wgrad_batch).  A weight gradient is off the
@@ -312,7 +385,7 @@ struct WgradTiledGroup {
 };
 static_assert(sizeof(WgradTiledGroup) <= 4000, "kernel arguments are limited to 4 KB");
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0>
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
 __global__ __launch_bounds__(256) void conv_wgrad_tiled_group_kernel(const WgradTiledGroup g) {
   const int b = blockIdx.x;
   int lo = 0, hi = g.n - 1;
@@ -323,10 +396,34 @@ __global__ __launch_bounds__(256) void conv_wgrad_tiled_group_kernel(const Wgrad
   const WgradTiledArgs& p = g.job[lo];
   const int local = b - g.begin[lo];
   const int ntile = p.n_co_tiles * p.n_n_tiles;
-  wgrad_tiled_body<BM, BN, WGM, WGN, KS, TW, KSP, RAG>(p, local % ntile, local / ntile);
+  wgrad_tiled_body<BM, BN, WGM, WGN, KS, TW, KSP, RAG, LIMB>(p, local % ntile, local / ntile);
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1>
+// ---- which tile configurations run the limb loop (LIMB = 1) ----
+// One bit per tile configuration code of tiled_cfg_code (0 = 32x64 KSP 2, 1 = 32x128, 2 = 64x64, 3 = 64x128, 4 = 128x64, 5 = 128x128),
+// per kernel size and tile width.  A bit is set where the grouped launch of that bucket in the 256 x 256 training step measured
+// faster than the f32 loop by more than the run-to-run spread (profiles/r07_a_wgrad_limbs_per_config.txt, NOTES (73)): every 3x3
+// bucket (0.66-0.93 of the f32 loop's time) and the 64x64 1x1 tile on 16- and 8-wide tiles (0.86 / 0.88); the 1x1 on 32-wide tiles
+// (the 64- and 32-pixel maps) measured 1.20 and stays on the f32 loop.  Buckets the step does not have, the ragged (RAG) ones
+// among them, are unmeasured and stay off.
+static unsigned wg_limb_mask(int ks, int tw) {
+  if (ks == 3) return tw == 16 ? 0x3Fu : (tw == 8 ? 1u << 5 : 0u);
+  return tw == 16 || tw == 8 ? 1u << 2 : 0u;
+}
+// RSIS_WGRAD_LIMBS, read once: unset = the table; 0 = every job on the f32 loop (A/B, bisecting); all = every job on the limb loop
+// (the per-configuration measurement and tests/test_gpu_wgrad_limbs.py)
+static bool wg_use_limbs(int ks, int tw, int code, int rag) {
+  static const int mode = [] {
+    const char* e = getenv("RSIS_WGRAD_LIMBS");
+    if (!e || !e[0]) return 0;
+    if (e[0] == '0') return 1;
+    return strcmp(e, "all") == 0 ? 2 : 0;
+  }();
+  if (mode) return mode == 2;
+  return rag == 0 && ((wg_limb_mask(ks, tw) >> code) & 1u);
+}
+
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int LIMB = 0>
 static int launch_tiled_cfg(WgradTiledArgs& a, hipStream_t st) {
   constexpr int TH = (KS == 1 ? 32 : 64) / TW;
   a.n_co_tiles = rsis_cdiv(a.Cout, BM);
@@ -345,25 +442,35 @@ static int launch_tiled_cfg(WgradTiledArgs& a, hipStream_t st) {
   if (nsplit < 1 || rsis_deterministic()) nsplit = 1;     // deterministic mode: one block walks every spatial tile of its dW tile
   a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
   nsplit = rsis_cdiv(a.n_sp_tiles, a.tiles_per_split);
-  hipLaunchKernelGGL((conv_wgrad_tiled_kernel<BM, BN, WGM, WGN, KS, TW, KSP>), dim3(ntile, nsplit), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((conv_wgrad_tiled_kernel<BM, BN, WGM, WGN, KS, TW, KSP, LIMB>), dim3(ntile, nsplit), dim3(256), 0, st, a);
   return rsis_check_launch();
 }
 
+template <int KS, int TW, int LIMB>
+static int launch_tiled_code(int code, WgradTiledArgs& a, hipStream_t st) {
+  switch (code) {
+    case 0: return launch_tiled_cfg<32, 64, 1, 2, KS, TW, 2, LIMB>(a, st);
+    case 1: return launch_tiled_cfg<32, 128, 1, 4, KS, TW, 1, LIMB>(a, st);
+    case 2: return launch_tiled_cfg<64, 64, 2, 2, KS, TW, 1, LIMB>(a, st);
+    case 3: return launch_tiled_cfg<64, 128, 2, 2, KS, TW, 1, LIMB>(a, st);
+    case 4: return launch_tiled_cfg<128, 64, 2, 2, KS, TW, 1, LIMB>(a, st);
+    default: return launch_tiled_cfg<128, 128, 2, 2, KS, TW, 1, LIMB>(a, st);
+  }
+}
+
+static int tiled_cfg_code(const WgradTiledArgs& a, int ks);
+
+// The tile configuration (tiled_cfg_code):
+// N = Cs * KS * KS columns: a 64-wide tile when that pads N less than the 128-wide one (N mod 128 in 1..64), e.g. the decoder's
+// 16- and 32-channel sources (N = 144 / 288: 56 % / 75 % -> 75 % / 90 % useful MFMA columns)
+// (deterministic mode: not the KSP = 2 tile -- its two wave copies both add into dW, in either order)
+// 1x1: 64 x 64 tiles with two blocks per CU.  The split count -- and with it the dW-sized passes of fp32 atomics, which run at
+// ~0.3 T atomics/s and were a third of these launches -- goes with slots / tiles: a quarter of the 128 x 128 tile's at twice
+// its slots.  Measured on every 1x1 shape of the trunk at batch 32 (tools/exp/bf16_shape_sweep.py --dtype fp32): 47-54 -> 38-44 us.
 template <int KS, int TW>
 static int launch_tiled_tw(WgradTiledArgs& a, hipStream_t st) {
-  // N = Cs * KS * KS columns: a 64-wide tile when that pads N less than the 128-wide one (N mod 128 in 1..64), e.g. the decoder's
-  // 16- and 32-channel sources (N = 144 / 288: 56 % / 75 % -> 75 % / 90 % useful MFMA columns)
-  const int nmod = (a.Cs * KS * KS) % 128;
-  const bool narrow = nmod != 0 && nmod <= 64;
-  // (deterministic mode: not the KSP = 2 tile -- its two wave copies both add into dW, in either order)
-  if (rsis_deterministic() && a.Cout <= 32) return launch_tiled_cfg<32, 128, 1, 4, KS, TW>(a, st);
-  // 1x1: 64 x 64 tiles with two blocks per CU.  The split count -- and with it the dW-sized passes of fp32 atomics, which run at
-  // ~0.3 T atomics/s and were a third of these launches -- goes with slots / tiles: a quarter of the 128 x 128 tile's at twice
-  // its slots.  Measured on every 1x1 shape of the trunk at batch 32 (tools/exp/bf16_shape_sweep.py --dtype fp32): 47-54 -> 38-44 us.
-  if (KS == 1 && a.Cout > 32) return launch_tiled_cfg<64, 64, 2, 2, KS, TW>(a, st);
-  if (a.Cout <= 32) return narrow ? launch_tiled_cfg<32, 64, 1, 2, KS, TW, 2>(a, st) : launch_tiled_cfg<32, 128, 1, 4, KS, TW>(a, st);
-  if (a.Cout <= 64) return narrow ? launch_tiled_cfg<64, 64, 2, 2, KS, TW>(a, st) : launch_tiled_cfg<64, 128, 2, 2, KS, TW>(a, st);
-  return narrow ? launch_tiled_cfg<128, 64, 2, 2, KS, TW>(a, st) : launch_tiled_cfg<128, 128, 2, 2, KS, TW>(a, st);
+  const int code = tiled_cfg_code(a, KS);
+  return wg_use_limbs(KS, TW, code, 0) ? launch_tiled_code<KS, TW, 1>(code, a, st) : launch_tiled_code<KS, TW, 0>(code, a, st);
 }
 
 // widest tile the map allows: full 128-byte lines of dy / x per tile row on the wide maps, whole rows on the narrow ones
@@ -382,7 +489,7 @@ static int tiled_tw_ragged(int W, int ks) {
 }
 
 // ---- grouped launch (host side) ----
-// tile configuration of a job, the same rule as launch_tiled_tw: 0 = 32x64 (KSP 2), 1 = 32x128, 2 = 64x64, 3 = 64x128, 4 = 128x64, 5 = 128x128
+// tile configuration of a job: 0 = 32x64 (KSP 2), 1 = 32x128, 2 = 64x64, 3 = 64x128, 4 = 128x64, 5 = 128x128
 static int tiled_cfg_code(const WgradTiledArgs& a, int ks) {
   const int nmod = (a.Cs * ks * ks) % 128;
   const bool narrow = nmod != 0 && nmod <= 64;
@@ -392,7 +499,7 @@ static int tiled_cfg_code(const WgradTiledArgs& a, int ks) {
   return narrow ? 4 : 5;
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0>
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
 static int launch_group_cfg(WgradTiledArgs* jobs, int n, hipStream_t st) {
   constexpr int TH = (KS == 1 ? 32 : 64) / TW;
   long total_iters = 0;
@@ -425,22 +532,27 @@ static int launch_group_cfg(WgradTiledArgs* jobs, int n, hipStream_t st) {
       blocks += a.n_co_tiles * a.n_n_tiles * nsplit;
     }
     g.begin[g.n] = blocks;
-    hipLaunchKernelGGL((conv_wgrad_tiled_group_kernel<BM, BN, WGM, WGN, KS, TW, KSP, RAG>), dim3(blocks), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((conv_wgrad_tiled_group_kernel<BM, BN, WGM, WGN, KS, TW, KSP, RAG, LIMB>), dim3(blocks), dim3(256), 0, st, g);
     if (rsis_check_launch() != RSIS_OK) return RSIS_ERR_LAUNCH;
   }
   return RSIS_OK;
 }
 
+template <int KS, int TW, int RAG, int LIMB>
+static int launch_group_code(int code, WgradTiledArgs* jobs, int n, hipStream_t st) {
+  switch (code) {
+    case 0: return launch_group_cfg<32, 64, 1, 2, KS, TW, 2, RAG, LIMB>(jobs, n, st);
+    case 1: return launch_group_cfg<32, 128, 1, 4, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+    case 2: return launch_group_cfg<64, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+    case 3: return launch_group_cfg<64, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+    case 4: return launch_group_cfg<128, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+    default: return launch_group_cfg<128, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+  }
+}
+
 template <int KS, int TW, int RAG = 0>
 static int launch_group_tw(int code, WgradTiledArgs* jobs, int n, hipStream_t st) {
-  switch (code) {
-    case 0: return launch_group_cfg<32, 64, 1, 2, KS, TW, 2, RAG>(jobs, n, st);
-    case 1: return launch_group_cfg<32, 128, 1, 4, KS, TW, 1, RAG>(jobs, n, st);
-    case 2: return launch_group_cfg<64, 64, 2, 2, KS, TW, 1, RAG>(jobs, n, st);
-    case 3: return launch_group_cfg<64, 128, 2, 2, KS, TW, 1, RAG>(jobs, n, st);
-    case 4: return launch_group_cfg<128, 64, 2, 2, KS, TW, 1, RAG>(jobs, n, st);
-    default: return launch_group_cfg<128, 128, 2, 2, KS, TW, 1, RAG>(jobs, n, st);
-  }
+  return wg_use_limbs(KS, TW, code, RAG) ? launch_group_code<KS, TW, RAG, 1>(code, jobs, n, st) : launch_group_code<KS, TW, RAG, 0>(code, jobs, n, st);
 }
 
 // n weight gradients that rsis_wgrad_tiled_supported accepts, all with the same kernel size: bucketed by (tile width, tile
