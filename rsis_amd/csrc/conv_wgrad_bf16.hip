@@ -18,6 +18,8 @@
 //     a wave is transposed through LDS before the fp32 atomics so that consecutive lanes hit consecutive dW addresses.
 // Ragged maps (the 7/14/28/56/112-pixel pyramid of 224 x 224 inputs) need no special case: out-of-map pixels are zero-filled
 // when the tile is staged.  Split-K over spatial tiles / images with fp32 atomics into dW, as conv_wgrad_tiled.hip.
+// One launch path: every weight gradient, a single one included, runs on the *_group_kernel of its body through wgb_dispatch, and
+// wgb_key alone says which instantiation a layer gets.
 #include "common.h"
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;
@@ -760,19 +762,10 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
 //  to 150-190 VGPRs + 144 AGPRs, one wave per SIMD, and a loop whose every s_waitcnt / barrier stalls the whole SIMD; held to 256
 //  registers (no AGPRs, at most 9 spilled in three fp32-operand variants) two blocks share a CU and the bf16 224^2 step went
 //  19.66 -> 18.80 ms.  LDS allows two blocks in every variant.)
-// single launches, and grouped launches: the weight gradients of many layers in one grid (rsis_conv2d_wgrad_batch; see
-// conv_wgrad_tiled.hip).  The jobs travel by value in the kernel arguments.
-template <int BM, int TW, int IN>
-__global__ __launch_bounds__(256, 2) void wgrad3_bf16_kernel(const WgradBf16Args p) { wgrad3_bf16_body<BM, TW, IN>(p, blockIdx.x, blockIdx.y); }
-template <int BM, int TW, int TH, int NR>
-__global__ __launch_bounds__(256, 2) void wgrad3_tr_kernel(const WgradBf16Args p) {
-  wgrad3_tr_body<BM, TW, TH, NR>(p, blockIdx.x, blockIdx.y);
-}
-template <int BM, int BN, int WGM, int WGN, int TW, int IN>
-__global__ __launch_bounds__(256) void wgrad1_bf16_kernel(const WgradBf16Args p) {
-  wgrad1_bf16_body<BM, BN, WGM, WGN, TW, IN>(p, blockIdx.x, blockIdx.y);
-}
-
+// The launch is a GROUP: the weight gradients of many layers in one grid (rsis_conv2d_wgrad_batch; see conv_wgrad_tiled.hip), the
+// jobs travelling by value in the kernel arguments.  A single weight gradient (rsis_conv2d_wgrad, and every job of the
+// deterministic mode) is a group of one job in the PLAIN mode below.
+//
 // XCD placement of a grouped launch.  A (job, range of consecutive splits) ITEM -- all dW tiles of one job over one range of its
 // spatial tiles -- runs on ONE XCD: its blocks re-read the same dy / x pixels once per dW tile (4-16 times each), and only inside
 // one L2 are those re-reads hits.  With consecutive block indices spread round-robin over the eight XCDs every XCD fetched the pixels
@@ -785,7 +778,7 @@ __global__ __launch_bounds__(256) void wgrad1_bf16_kernel(const WgradBf16Args p)
 #define RSIS_WGB_LANE_ITEMS 28
 struct WgradBf16Group {
   int n;
-  int lane_n[8];
+  int lane_n[8];                                  // lane_n[0] < 0: the plain mode, see wgb_find
   int lane_start[8][RSIS_WGB_LANE_ITEMS + 1];     // first k of each item of a lane, ascending; [lane_n] = the lane's block count
   unsigned short lane_split0[8][RSIS_WGB_LANE_ITEMS];   // an item covers the consecutive splits split0, split0 + 1, ... of its job
   unsigned char lane_job[8][RSIS_WGB_LANE_ITEMS];
@@ -794,7 +787,15 @@ struct WgradBf16Group {
 static_assert(sizeof(WgradBf16Group) <= 4000, "kernel arguments are limited to 4 KB");
 
 // block -> (job, tile, split); false: a padding block of a short lane
+// Plain mode (a launch of ONE job on its own): no lanes -- a job with fewer than eight splits, as every job of the deterministic mode,
+// would leave XCDs idle behind padding blocks -- but exactly tiles * splits blocks, block b = (tile b % tiles, split b / tiles): the
+// order of a (tiles, splits) grid.
 __device__ __forceinline__ bool wgb_find(const WgradBf16Group& g, int& job, int& tile, int& split) {
+  if (g.lane_n[0] < 0) {                                          // (uniform: a scalar branch)
+    const int ntile = g.job[0].n_co_tiles * g.job[0].n_n_tiles;
+    job = 0; tile = blockIdx.x % ntile; split = blockIdx.x / ntile;
+    return true;
+  }
   const int x = blockIdx.x & 7, k = blockIdx.x >> 3;
   const int nl = g.lane_n[x];
   if (k >= g.lane_start[x][nl]) return false;
@@ -820,13 +821,6 @@ __global__ __launch_bounds__(256, 2) void wgrad3_tr_group_kernel(const WgradBf16
 }
 // the ring is dynamic LDS (up to 80 KB: two blocks per CU); sizes above 64 KB are an opt-in per kernel
 template <int BM, int TW, int TH, int NR>
-static void w3t_launch(const WgradBf16Args& a, dim3 grid, hipStream_t st) {
-  constexpr int lds = w3t_lds_bytes<BM, TW, TH, NR>();
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad3_tr_kernel<BM, TW, TH, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad3_tr_kernel<BM, TW, TH, NR>), grid, dim3(256), lds, st, a);
-}
-template <int BM, int TW, int TH, int NR>
 static void w3t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
   constexpr int lds = w3t_lds_bytes<BM, TW, TH, NR>();
   static const hipError_t once = hipFuncSetAttribute((const void*)wgrad3_tr_group_kernel<BM, TW, TH, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -834,19 +828,10 @@ static void w3t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st
   hipLaunchKernelGGL((wgrad3_tr_group_kernel<BM, TW, TH, NR>), dim3(blocks), dim3(256), lds, st, g);
 }
 template <int BM, int BN, int TP, int NR>
-__global__ __launch_bounds__(256, 2) void wgrad1_tr_kernel(const WgradBf16Args p) { wgrad1_tr_body<BM, BN, TP, NR>(p, blockIdx.x, blockIdx.y); }
-template <int BM, int BN, int TP, int NR>
 __global__ __launch_bounds__(256, 2) void wgrad1_tr_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
   if (!wgb_find(g, j, tile, split)) return;
   wgrad1_tr_body<BM, BN, TP, NR>(g.job[j], tile, split);
-}
-template <int BM, int BN, int TP, int NR>
-static void w1t_launch(const WgradBf16Args& a, dim3 grid, hipStream_t st) {
-  constexpr int lds = w1t_lds_bytes<BM, BN, TP, NR>();
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad1_tr_kernel<BM, BN, TP, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad1_tr_kernel<BM, BN, TP, NR>), grid, dim3(256), lds, st, a);
 }
 template <int BM, int BN, int TP, int NR>
 static void w1t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
@@ -855,36 +840,6 @@ static void w1t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st
   (void)once;
   hipLaunchKernelGGL((wgrad1_tr_group_kernel<BM, BN, TP, NR>), dim3(blocks), dim3(256), lds, st, g);
 }
-#ifdef RSIS_W3T_SWEEP      // tuning build: tile height / ring depth of the single launches from the environment (tools/exp/wgrad_blk_bench.py)
-template <int BM, int TW, int TH, int NR>
-static int w3t_try(WgradBf16Args& a, int ntile, hipStream_t st) {
-  constexpr int st_b = w3t_lds_bytes<BM, TW, TH, NR>() / NR;
-  if constexpr (w3t_lds_bytes<BM, TW, TH, NR>() <= 81920 && (NR - 2) * (st_b / 4096) < 64 && (TW * TH / 16) % (4 / (BM / 32)) == 0) {
-    void split_plan(WgradBf16Args&, int, int, int, int);
-    split_plan(a, TW, TH, ntile, 256);
-    w3t_launch<BM, TW, TH, NR>(a, dim3(ntile, rsis_cdiv(a.n_sp_tiles, a.tiles_per_split)), st);
-    return rsis_check_launch();
-  }
-  return RSIS_ERR_UNSUPPORTED;
-}
-template <int BM, int TW, int TH>
-static int w3t_sweep_nr(WgradBf16Args& a, int ntile, int nr, hipStream_t st) {
-  if (nr == 2) return w3t_try<BM, TW, TH, 2>(a, ntile, st);
-  if (nr == 3) return w3t_try<BM, TW, TH, 3>(a, ntile, st);
-  if (nr == 4) return w3t_try<BM, TW, TH, 4>(a, ntile, st);
-  if (nr == 5) return w3t_try<BM, TW, TH, 5>(a, ntile, st);
-  return RSIS_ERR_UNSUPPORTED;
-}
-template <int BM, int TW>
-static int w3t_sweep(WgradBf16Args& a, int ntile, hipStream_t st) {
-  const int th = atoi(getenv("RSIS_W3T_TH")), nr = atoi(getenv("RSIS_W3T_NR"));
-  if (th == 2) return w3t_sweep_nr<BM, TW, 2>(a, ntile, nr, st);
-  if (th == 4) return w3t_sweep_nr<BM, TW, 4>(a, ntile, nr, st);
-  if (th == 8) return w3t_sweep_nr<BM, TW, 8>(a, ntile, nr, st);
-  if (th == 16) return w3t_sweep_nr<BM, TW, 16>(a, ntile, nr, st);
-  return RSIS_ERR_UNSUPPORTED;
-}
-#endif
 template <int BM, int BN, int WGM, int WGN, int TW, int IN>
 __global__ __launch_bounds__(256) void wgrad1_bf16_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
@@ -892,7 +847,8 @@ __global__ __launch_bounds__(256) void wgrad1_bf16_group_kernel(const WgradBf16G
   wgrad1_bf16_body<BM, BN, WGM, WGN, TW, IN>(g.job[j], tile, split);
 }
 
-void split_plan(WgradBf16Args& a, int TW, int TH, int ntile, int slots) {
+// the split of a job that is launched on its own
+static void split_plan(WgradBf16Args& a, int TW, int TH, int ntile, int slots) {
   a.n_sp_tiles = a.B * rsis_cdiv(a.H, TH) * rsis_cdiv(a.W, TW);
   // Every split adds a dW-sized pass of fp32 atomics, and those run at ~0.3 T atomics/s whatever the layer: measured on the
   // trunk shapes at batch 32 (tools/exp/bf16_shape_sweep.py), one block per CU (256 slots) beats two (512) on every layer --
@@ -904,52 +860,6 @@ void split_plan(WgradBf16Args& a, int TW, int TH, int ntile, int slots) {
   a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
 }
 
-template <int BM, int TW>
-static int launch_w3(WgradBf16Args& a, hipStream_t st) {
-  a.n_co_tiles = rsis_cdiv(a.Cout, BM);
-  a.n_n_tiles = rsis_cdiv(a.Cs, 32);
-  const int ntile = a.n_co_tiles * a.n_n_tiles;
-#ifdef RSIS_W3T_SWEEP
-  if (a.blk && getenv("RSIS_W3T_TH")) return w3t_sweep<BM, TW>(a, ntile, st);
-#endif
-  split_plan(a, TW, a.blk ? w3t_th(BM, TW) : 64 / TW, ntile, 256);
-  const dim3 grid(ntile, rsis_cdiv(a.n_sp_tiles, a.tiles_per_split));
-  if (a.blk) w3t_launch<BM, TW, w3t_th(BM, TW), w3t_nr(BM, TW)>(a, grid, st);
-  else if (a.W % 4 == 0) hipLaunchKernelGGL((wgrad3_bf16_kernel<BM, TW, 1>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((wgrad3_bf16_kernel<BM, TW, 0>), grid, dim3(256), 0, st, a);
-  return rsis_check_launch();
-}
-
-template <int TW>
-static int launch_w3_tw(WgradBf16Args& a, hipStream_t st) {
-  // 64 dy rows per block unless the patch side is deep: half the splits (= half the atomics) of the 128-row tile for 20 % more
-  // operand reads (128 -> 128 @28^2: 51 -> 36 us, 256 -> 256 @14^2: 62 -> 59 us; 1024 -> 128 @14^2: 92 -> 101 us, kept at 128)
-  if (a.Cout <= 32) return launch_w3<32, TW>(a, st);
-  if (a.Cout <= 64 || a.Cs <= 512) return launch_w3<64, TW>(a, st);
-  return launch_w3<128, TW>(a, st);
-}
-
-template <int BM, int BN, int WGM, int WGN, int TW>
-static int launch_w1(WgradBf16Args& a, hipStream_t st) {
-  a.n_co_tiles = rsis_cdiv(a.Cout, BM);
-  a.n_n_tiles = rsis_cdiv(a.Cs, BN);
-  const int ntile = a.n_co_tiles * a.n_n_tiles;
-  split_plan(a, a.blk ? W1T_TP : TW, a.blk ? 1 : 64 / TW, ntile, 256);
-  const dim3 grid(ntile, rsis_cdiv(a.n_sp_tiles, a.tiles_per_split));
-  if (a.blk) w1t_launch<BM, BN, W1T_TP, w1t_nr(BM, BN)>(a, grid, st);
-  else if (a.W % 4 == 0) hipLaunchKernelGGL((wgrad1_bf16_kernel<BM, BN, WGM, WGN, TW, 1>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((wgrad1_bf16_kernel<BM, BN, WGM, WGN, TW, 0>), grid, dim3(256), 0, st, a);
-  return rsis_check_launch();
-}
-
-template <int TW>
-static int launch_w1_tw(WgradBf16Args& a, hipStream_t st) {
-  if (a.Cout <= 64 && a.Cs <= 64) return launch_w1<64, 64, 2, 2, TW>(a, st);
-  if (a.Cout <= 64) return launch_w1<64, 128, 2, 2, TW>(a, st);
-  if (a.Cs <= 64) return launch_w1<128, 64, 2, 2, TW>(a, st);
-  return launch_w1<128, 128, 2, 2, TW>(a, st);
-}
-
 // stride 1, "same" padding, 32-bit offsets inside one image slab
 bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks) {
   if (!(ks == 1 || ks == 3) || w.stride != 1 || w.pad != ks / 2 || w.H != w.Ho || w.W != w.Wo) return false;
@@ -959,26 +869,16 @@ bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks) {
   return (long)w.Cout * img < (1L << 30) && (long)w.Cs * img < (1L << 30);
 }
 
-int rsis_launch_conv_wgrad_bf16(const WgradArgs& w, int ks, hipStream_t st) {
-  WgradBf16Args a = {};
-  a.dy = w.dy; a.x = w.x; a.dw = w.dw; a.B = w.B; a.Cs = w.Cs; a.H = w.H; a.W = w.W; a.Cout = w.Cout;
-  a.ldo = w.ldo; a.n_off = w.n_off; a.interleave_hid = (short)w.interleave_hid; a.blk = (short)w.blk;
-  const int tw = w.W > 16 ? 32 : (w.W > 8 ? 16 : 8);     // widest 64-pixel tile the map fills
-  if (ks == 3) {
-    if (tw == 32) return launch_w3_tw<32>(a, st);
-    if (tw == 16) return launch_w3_tw<16>(a, st);
-    return launch_w3_tw<8>(a, st);
-  }
-  // 1x1: the reduction runs over the flattened map (the H*W pixels of a channel are contiguous), 64 pixels per tile: whole
-  // 16-byte loads whenever H*W % 4 == 0.  Tiled in 2-D the 14-pixel rows of the 224 x 224 pyramid went dword by dword, 4x the
-  // VMEM instructions, and the texture-address rate -- not HBM -- bound the loop (256 -> 1024 @14^2: 43 -> 29 us).
-  a.W = w.H * w.W; a.H = 1;
-  return launch_w1_tw<64>(a, st);
-}
-
-// ---- grouped launch (host side): jobs bucketed by kernel instantiation, every block of a bucket walks ~L spatial tiles ----
+// ---- launch (host side): jobs bucketed by kernel instantiation ----
+// The instantiation of a job -- the ONE statement of the rule, for a job launched on its own and for a job of a group alike.
+//   3x3: the widest 64-pixel tile the map fills; 64 dy rows per block unless the patch side is deep: half the splits (= half the
+//   atomics) of the 128-row tile for 20 % more operand reads (128 -> 128 @28^2: 51 -> 36 us, 256 -> 256 @14^2: 62 -> 59 us;
+//   1024 -> 128 @14^2: 92 -> 101 us, kept at 128).
+//   1x1: the reduction runs over the flattened map (the H*W pixels of a channel are contiguous; the caller has set W = H * W, H = 1),
+//   64 pixels per tile: whole 16-byte loads whenever H*W % 4 == 0.  Tiled in 2-D the 14-pixel rows of the 224 x 224 pyramid went
+//   dword by dword, 4x the VMEM instructions, and the texture-address rate -- not HBM -- bound the loop (256 -> 1024 @14^2: 43 -> 29 us).
 struct WgbKey { int ks, bm, bn, tw, v4, th; };
-static WgbKey wgb_key(const WgradBf16Args& a, int ks) {      // the rules of launch_w3_tw / launch_w1_tw / rsis_launch_conv_wgrad_bf16
+static WgbKey wgb_key(const WgradBf16Args& a, int ks) {
   WgbKey k = {ks, 0, 0, 0, 0, 0};
   if (ks == 3) {
     k.tw = a.W > 16 ? 32 : (a.W > 8 ? 16 : 8);
@@ -995,8 +895,10 @@ static WgbKey wgb_key(const WgradBf16Args& a, int ks) {      // the rules of lau
 }
 static inline bool wgb_same(const WgbKey& a, const WgbKey& b) { return a.ks == b.ks && a.bm == b.bm && a.bn == b.bn && a.tw == b.tw && a.v4 == b.v4; }
 
+// `alone`: the jobs are ONE job that rsis_launch_conv_wgrad_bf16 launches on its own -- split_plan, plain mode; otherwise every block
+// of the bucket walks ~L spatial tiles and the blocks are placed on the XCD lanes
 template <typename LaunchFn>
-static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, LaunchFn launch) {
+static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, bool alone, LaunchFn launch) {
   const int TH = k.th;
   long total = 0;
   for (int j = 0; j < n; ++j) {
@@ -1005,6 +907,16 @@ static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, Launch
     a.n_n_tiles = rsis_cdiv(a.Cs, k.bn);
     a.n_sp_tiles = a.B * rsis_cdiv(a.H, TH) * rsis_cdiv(a.W, k.tw);
     total += (long)a.n_co_tiles * a.n_n_tiles * a.n_sp_tiles;
+  }
+  if (alone) {
+    WgradBf16Group g = {};
+    const int ntile = jobs[0].n_co_tiles * jobs[0].n_n_tiles;
+    split_plan(jobs[0], k.tw, TH, ntile, 256);
+    g.n = 1;
+    g.lane_n[0] = -1;
+    g.job[0] = jobs[0];
+    launch(g, ntile * rsis_cdiv(jobs[0].n_sp_tiles, jobs[0].tiles_per_split));
+    return rsis_check_launch();
   }
   static const int env_tb = getenv("RSIS_WGB_GROUP_BLOCKS") ? atoi(getenv("RSIS_WGB_GROUP_BLOCKS")) : 0;     // tuning knob
   // (swept at the bench geometry, 224^2 / batch 32, with two blocks per CU resident: 640 18.77 ms per step, 768 18.51, 896 18.43,
@@ -1064,23 +976,23 @@ static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, Launch
 
 #define WGB3(BMv, TWv)                                                                                             \
   if (k.bm == BMv && k.tw == TWv) {                                                                                \
-    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                 \
+    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       w3t_launch_group<BMv, TWv, w3t_th(BMv, TWv), w3t_nr(BMv, TWv)>(g, blocks, st); });                           \
-    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                 \
+    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       hipLaunchKernelGGL((wgrad3_bf16_group_kernel<BMv, TWv, 1>), dim3(blocks), dim3(256), 0, st, g); });          \
-    return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                                \
+    return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                                \
       hipLaunchKernelGGL((wgrad3_bf16_group_kernel<BMv, TWv, 0>), dim3(blocks), dim3(256), 0, st, g); });          \
   }
 #define WGB1(BMv, BNv)                                                                                             \
   if (k.bm == BMv && k.bn == BNv) {                                                                                \
-    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                 \
+    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       w1t_launch_group<BMv, BNv, W1T_TP, w1t_nr(BMv, BNv)>(g, blocks, st); });                                     \
-    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                 \
+    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       hipLaunchKernelGGL((wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 1>), dim3(blocks), dim3(256), 0, st, g); });      \
-    return wgb_launch_bucket(jobs, n, k, [&](const WgradBf16Group& g, int blocks) {                                \
+    return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                                \
       hipLaunchKernelGGL((wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 0>), dim3(blocks), dim3(256), 0, st, g); });      \
   }
-static int wgb_dispatch(WgradBf16Args* jobs, int n, const WgbKey& k, hipStream_t st) {
+static int wgb_dispatch(WgradBf16Args* jobs, int n, const WgbKey& k, bool alone, hipStream_t st) {
   if (k.ks == 3) {
     WGB3(32, 32) WGB3(64, 32) WGB3(128, 32) WGB3(32, 16) WGB3(64, 16) WGB3(128, 16) WGB3(32, 8) WGB3(64, 8) WGB3(128, 8)
   } else {
@@ -1092,7 +1004,7 @@ static int wgb_dispatch(WgradBf16Args* jobs, int n, const WgbKey& k, hipStream_t
 #undef WGB1
 
 // n weight gradients that rsis_wgrad_bf16_supported accepts, all with the same kernel size
-int rsis_launch_conv_wgrad_bf16_group(const WgradArgs* w, int n, int ks, hipStream_t st) {
+static int wgb_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipStream_t st) {
   if (n < 1) return RSIS_OK;
   WgradBf16Args* all = (WgradBf16Args*)malloc(sizeof(WgradBf16Args) * n * 2);
   WgbKey* key = (WgbKey*)malloc(sizeof(WgbKey) * n);
@@ -1113,8 +1025,12 @@ int rsis_launch_conv_wgrad_bf16_group(const WgradArgs* w, int n, int ks, hipStre
     int m = 0;
     for (int i = j; i < n; ++i)
       if (key[i].ks >= 0 && wgb_same(key[i], k)) { bucket[m++] = all[i]; key[i].ks = -1; }
-    rc = wgb_dispatch(bucket, m, k, st);
+    rc = wgb_dispatch(bucket, m, k, alone, st);
   }
   free(all); free(key);
   return rc;
 }
+
+int rsis_launch_conv_wgrad_bf16_group(const WgradArgs* w, int n, int ks, hipStream_t st) { return wgb_launch_jobs(w, n, ks, false, st); }
+// one weight gradient in a launch of its own: a group of one job, plain mode
+int rsis_launch_conv_wgrad_bf16(const WgradArgs& w, int ks, hipStream_t st) { return wgb_launch_jobs(&w, 1, ks, true, st); }

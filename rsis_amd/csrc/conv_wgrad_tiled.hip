@@ -29,6 +29,9 @@
 // the eight 64-cycle f32 MFMAs of a 16-pixel k-step by six 32-cycle ones.  Two consecutive step blocks g, g + 1 make one K16 step:
 // lane (r, h) uses the 4 + 4 pixels it already reads as elements j = 0..7 of its k = 8h + j fragment, A and B alike.  Which tile
 // configurations take this loop is a measured table (wg_limb_mask); RSIS_WGRAD_LIMBS=0 puts every job back on the f32 loop.
+//
+// One launch path: conv_wgrad_tiled_group_kernel.  A single weight gradient is a group of one job; what differs between a job on its
+// own and a group is the split plan (tiled_split_plan), nothing else.
 #include "common.h"
 #include "limb_split.h"
 #include <stdlib.h>
@@ -366,17 +369,14 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
 #endif
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int LIMB = 0>
-__global__ __launch_bounds__(256) void conv_wgrad_tiled_kernel(const WgradTiledArgs p) {
-  wgrad_tiled_body<BM, BN, WGM, WGN, KS, TW, KSP, 0, LIMB>(p, blockIdx.x, blockIdx.y);
-}
-
-// ---- grouped launch: the weight gradients of many layers in ONE grid (rsis_conv2d_wgrad_batch).  A weight gradient is off the
+// ---- the launch: the weight gradients of many layers in ONE grid (rsis_conv2d_wgrad_batch); a single weight gradient
+// (rsis_conv2d_wgrad, and every job of the deterministic mode) is a group of one job.  A weight gradient is off the
 // backward pass's critical path (nothing reads it before the optimizer step), so the training driver parks them and flushes
 // them together: every launch costs ~15 us of ramp, prologue and drain whatever its size, and alone a layer has to split its
 // pixel axis 8-32 ways to fill the chip -- each split a dW-sized pass of fp32 atomics -- while forty layers together fill it with
 // one or two.  The jobs travel by value in the kernel arguments (no device-side table, nothing to keep alive under graph replay);
-// block b belongs to the job whose [begin, end) range holds it and plays block (x, y) = (b' % tiles, b' / tiles) of that job. ----
+// block b belongs to the job whose [begin, end) range holds it and plays block (x, y) = (b' % tiles, b' / tiles) of that job -- for
+// one job the order of a (tiles, splits) grid. ----
 #define RSIS_WG_MAXJ 48
 struct WgradTiledGroup {
   int n;
@@ -423,56 +423,6 @@ static bool wg_use_limbs(int ks, int tw, int code, int rag) {
   return rag == 0 && ((wg_limb_mask(ks, tw) >> code) & 1u);
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int LIMB = 0>
-static int launch_tiled_cfg(WgradTiledArgs& a, hipStream_t st) {
-  constexpr int TH = (KS == 1 ? 32 : 64) / TW;
-  a.n_co_tiles = rsis_cdiv(a.Cout, BM);
-  a.n_n_tiles = rsis_cdiv((long)a.Cs * KS * KS, BN);
-  a.n_sp_tiles = a.B * (a.H / TH) * (a.W / TW);
-  const int ntile = a.n_co_tiles * a.n_n_tiles;
-  // split-K over the spatial tiles: fill the resident block slots (2 blocks per CU for the 128-wide tiles, 3 otherwise) in one
-  // round, keeping >= 2 spatial tiles per split
-  // Every split adds a full dW-sized pass of atomics: with the slots filled that is slots * BM * BN atomics per launch whatever
-  // the layer (8.4 M for 128 x 128 tiles, ~20 us) -- a third of a 1x1 weight gradient's time but < 10 % of a 3x3's.  Measured:
-  // 1x1 layers +15 % with one block per CU (half the splits), 3x3 layers lose up to 20 % (they need the second block to hide
-  // the patch staging).
-  const int slots = KS == 1 ? (BM * BN >= 128 * 128 ? 256 : 512) : 256 * (BM * BN >= 128 * 128 ? 2 : 3);
-  int nsplit = ntile >= slots ? 1 : slots / ntile;
-  if (nsplit > a.n_sp_tiles / 2) nsplit = a.n_sp_tiles / 2;
-  if (nsplit < 1 || rsis_deterministic()) nsplit = 1;     // deterministic mode: one block walks every spatial tile of its dW tile
-  a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
-  nsplit = rsis_cdiv(a.n_sp_tiles, a.tiles_per_split);
-  hipLaunchKernelGGL((conv_wgrad_tiled_kernel<BM, BN, WGM, WGN, KS, TW, KSP, LIMB>), dim3(ntile, nsplit), dim3(256), 0, st, a);
-  return rsis_check_launch();
-}
-
-template <int KS, int TW, int LIMB>
-static int launch_tiled_code(int code, WgradTiledArgs& a, hipStream_t st) {
-  switch (code) {
-    case 0: return launch_tiled_cfg<32, 64, 1, 2, KS, TW, 2, LIMB>(a, st);
-    case 1: return launch_tiled_cfg<32, 128, 1, 4, KS, TW, 1, LIMB>(a, st);
-    case 2: return launch_tiled_cfg<64, 64, 2, 2, KS, TW, 1, LIMB>(a, st);
-    case 3: return launch_tiled_cfg<64, 128, 2, 2, KS, TW, 1, LIMB>(a, st);
-    case 4: return launch_tiled_cfg<128, 64, 2, 2, KS, TW, 1, LIMB>(a, st);
-    default: return launch_tiled_cfg<128, 128, 2, 2, KS, TW, 1, LIMB>(a, st);
-  }
-}
-
-static int tiled_cfg_code(const WgradTiledArgs& a, int ks);
-
-// The tile configuration (tiled_cfg_code):
-// N = Cs * KS * KS columns: a 64-wide tile when that pads N less than the 128-wide one (N mod 128 in 1..64), e.g. the decoder's
-// 16- and 32-channel sources (N = 144 / 288: 56 % / 75 % -> 75 % / 90 % useful MFMA columns)
-// (deterministic mode: not the KSP = 2 tile -- its two wave copies both add into dW, in either order)
-// 1x1: 64 x 64 tiles with two blocks per CU.  The split count -- and with it the dW-sized passes of fp32 atomics, which run at
-// ~0.3 T atomics/s and were a third of these launches -- goes with slots / tiles: a quarter of the 128 x 128 tile's at twice
-// its slots.  Measured on every 1x1 shape of the trunk at batch 32 (tools/exp/bf16_shape_sweep.py --dtype fp32): 47-54 -> 38-44 us.
-template <int KS, int TW>
-static int launch_tiled_tw(WgradTiledArgs& a, hipStream_t st) {
-  const int code = tiled_cfg_code(a, KS);
-  return wg_use_limbs(KS, TW, code, 0) ? launch_tiled_code<KS, TW, 1>(code, a, st) : launch_tiled_code<KS, TW, 0>(code, a, st);
-}
-
 // widest tile the map allows: full 128-byte lines of dy / x per tile row on the wide maps, whole rows on the narrow ones
 static int tiled_tw(int H, int W, int ks) {
   const int tp = ks == 1 ? 32 : 64;
@@ -488,8 +438,14 @@ static int tiled_tw_ragged(int W, int ks) {
   return W > 16 ? wide : (W > 8 ? 16 : 8);
 }
 
-// ---- grouped launch (host side) ----
+// ---- launch (host side) ----
 // tile configuration of a job: 0 = 32x64 (KSP 2), 1 = 32x128, 2 = 64x64, 3 = 64x128, 4 = 128x64, 5 = 128x128
+// N = Cs * KS * KS columns: a 64-wide tile when that pads N less than the 128-wide one (N mod 128 in 1..64), e.g. the decoder's
+// 16- and 32-channel sources (N = 144 / 288: 56 % / 75 % -> 75 % / 90 % useful MFMA columns)
+// (deterministic mode: not the KSP = 2 tile -- its two wave copies both add into dW, in either order)
+// 1x1: 64 x 64 tiles with two blocks per CU.  The split count -- and with it the dW-sized passes of fp32 atomics, which run at
+// ~0.3 T atomics/s and were a third of these launches -- goes with slots / tiles: a quarter of the 128 x 128 tile's at twice
+// its slots.  Measured on every 1x1 shape of the trunk at batch 32 (tools/exp/bf16_shape_sweep.py --dtype fp32): 47-54 -> 38-44 us.
 static int tiled_cfg_code(const WgradTiledArgs& a, int ks) {
   const int nmod = (a.Cs * ks * ks) % 128;
   const bool narrow = nmod != 0 && nmod <= 64;
@@ -499,37 +455,61 @@ static int tiled_cfg_code(const WgradTiledArgs& a, int ks) {
   return narrow ? 4 : 5;
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
-static int launch_group_cfg(WgradTiledArgs* jobs, int n, hipStream_t st) {
-  constexpr int TH = (KS == 1 ? 32 : 64) / TW;
+// ---- split plan: tiles_per_split of every job of one launch (n_co_tiles / n_n_tiles / n_sp_tiles are set).  Every split adds a
+// full dW-sized pass of fp32 atomics, so a job is split as little as filling the chip allows; deterministic mode: no split, one
+// block walks every spatial tile of its dW tile. ----
+static void tiled_split_plan(WgradTiledArgs* jobs, int n, int ks, bool big_tile, bool alone, int rag) {
+  if (alone && rag == 0) {
+    // a launch of its own on an aligned map (rsis_conv2d_wgrad): fill the resident block slots (2 blocks per CU for the 128 x 128
+    // tile, 3 otherwise) in one round, keeping >= 2 spatial tiles per split.  With the slots filled the atomics are
+    // slots * BM * BN per launch whatever the layer (8.4 M for 128 x 128 tiles, ~20 us) -- a third of a 1x1 weight gradient's time
+    // but < 10 % of a 3x3's.  Measured: 1x1 layers +15 % with one block per CU (half the splits), 3x3 layers lose up to 20 % (they
+    // need the second block to hide the patch staging).
+    WgradTiledArgs& a = jobs[0];
+    const int ntile = a.n_co_tiles * a.n_n_tiles;
+    const int slots = ks == 1 ? (big_tile ? 256 : 512) : 256 * (big_tile ? 2 : 3);
+    int nsplit = ntile >= slots ? 1 : slots / ntile;
+    if (nsplit > a.n_sp_tiles / 2) nsplit = a.n_sp_tiles / 2;
+    if (nsplit < 1 || rsis_deterministic()) nsplit = 1;
+    a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
+    return;
+  }
+  // a group -- and a ragged map launched on its own (rag != 0), which has always been planned as a group of one: equal work per block, every
+  // block walks ~L >= 2 spatial tiles of its job; ~8 blocks per CU over the whole group keeps the tail short
   long total_iters = 0;
+  for (int j = 0; j < n; ++j) total_iters += (long)jobs[j].n_co_tiles * jobs[j].n_n_tiles * jobs[j].n_sp_tiles;
+  static const int env_tb = getenv("RSIS_WG_GROUP_BLOCKS") ? atoi(getenv("RSIS_WG_GROUP_BLOCKS")) : 0;     // tuning knob
+  const long target_blocks = env_tb > 0 ? env_tb : 2048;
+  long L = (total_iters + target_blocks - 1) / target_blocks;
+  if (L < 2) L = 2;
+  if (rsis_deterministic()) L = 1L << 40;
+  for (int j = 0; j < n; ++j) {
+    int nsplit = rsis_cdiv(jobs[j].n_sp_tiles, L);
+    if (nsplit < 1) nsplit = 1;
+    jobs[j].tiles_per_split = rsis_cdiv(jobs[j].n_sp_tiles, nsplit);
+  }
+}
+
+// `alone`: the jobs are ONE job that rsis_launch_conv_wgrad_tiled launches on its own
+template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
+static int launch_group_cfg(WgradTiledArgs* jobs, int n, bool alone, hipStream_t st) {
+  constexpr int TH = (KS == 1 ? 32 : 64) / TW;
   for (int j = 0; j < n; ++j) {
     WgradTiledArgs& a = jobs[j];
     a.n_co_tiles = rsis_cdiv(a.Cout, BM);
     a.n_n_tiles = rsis_cdiv((long)a.Cs * KS * KS, BN);
     a.n_sp_tiles = RAG ? a.B * rsis_cdiv(a.H, TH) * rsis_cdiv(a.W, TW) : a.B * (a.H / TH) * (a.W / TW);
-    total_iters += (long)a.n_co_tiles * a.n_n_tiles * a.n_sp_tiles;
   }
-  // equal work per block: every block walks ~L spatial tiles of its job; ~8 blocks per CU over the whole group keeps the tail short,
-  // and a job is split as little as that allows (each split is a dW-sized pass of atomics)
-  static const int env_tb = getenv("RSIS_WG_GROUP_BLOCKS") ? atoi(getenv("RSIS_WG_GROUP_BLOCKS")) : 0;     // tuning knob
-  const long target_blocks = env_tb > 0 ? env_tb : 2048;
-  long L = (total_iters + target_blocks - 1) / target_blocks;
-  if (L < 2) L = 2;
-  if (rsis_deterministic()) L = 1L << 40;            // no split: every dW tile has one contributor
+  tiled_split_plan(jobs, n, KS, BM * BN >= 128 * 128, alone, RAG);
   for (int j0 = 0; j0 < n; j0 += RSIS_WG_MAXJ) {
     WgradTiledGroup g;
     g.n = n - j0 < RSIS_WG_MAXJ ? n - j0 : RSIS_WG_MAXJ;
     int blocks = 0;
     for (int j = 0; j < g.n; ++j) {
-      WgradTiledArgs a = jobs[j0 + j];
-      int nsplit = rsis_cdiv(a.n_sp_tiles, L);
-      if (nsplit < 1) nsplit = 1;
-      a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
-      nsplit = rsis_cdiv(a.n_sp_tiles, a.tiles_per_split);
+      const WgradTiledArgs& a = jobs[j0 + j];
       g.begin[j] = blocks;
       g.job[j] = a;
-      blocks += a.n_co_tiles * a.n_n_tiles * nsplit;
+      blocks += a.n_co_tiles * a.n_n_tiles * rsis_cdiv(a.n_sp_tiles, a.tiles_per_split);
     }
     g.begin[g.n] = blocks;
     hipLaunchKernelGGL((conv_wgrad_tiled_group_kernel<BM, BN, WGM, WGN, KS, TW, KSP, RAG, LIMB>), dim3(blocks), dim3(256), 0, st, g);
@@ -539,39 +519,61 @@ static int launch_group_cfg(WgradTiledArgs* jobs, int n, hipStream_t st) {
 }
 
 template <int KS, int TW, int RAG, int LIMB>
-static int launch_group_code(int code, WgradTiledArgs* jobs, int n, hipStream_t st) {
+static int launch_group_code(int code, WgradTiledArgs* jobs, int n, bool alone, hipStream_t st) {
   switch (code) {
-    case 0: return launch_group_cfg<32, 64, 1, 2, KS, TW, 2, RAG, LIMB>(jobs, n, st);
-    case 1: return launch_group_cfg<32, 128, 1, 4, KS, TW, 1, RAG, LIMB>(jobs, n, st);
-    case 2: return launch_group_cfg<64, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
-    case 3: return launch_group_cfg<64, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
-    case 4: return launch_group_cfg<128, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
-    default: return launch_group_cfg<128, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, st);
+    case 0: return launch_group_cfg<32, 64, 1, 2, KS, TW, 2, RAG, LIMB>(jobs, n, alone, st);
+    case 1: return launch_group_cfg<32, 128, 1, 4, KS, TW, 1, RAG, LIMB>(jobs, n, alone, st);
+    case 2: return launch_group_cfg<64, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, alone, st);
+    case 3: return launch_group_cfg<64, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, alone, st);
+    case 4: return launch_group_cfg<128, 64, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, alone, st);
+    default: return launch_group_cfg<128, 128, 2, 2, KS, TW, 1, RAG, LIMB>(jobs, n, alone, st);
   }
 }
 
-template <int KS, int TW, int RAG = 0>
-static int launch_group_tw(int code, WgradTiledArgs* jobs, int n, hipStream_t st) {
-  return wg_use_limbs(KS, TW, code, RAG) ? launch_group_code<KS, TW, RAG, 1>(code, jobs, n, st) : launch_group_code<KS, TW, RAG, 0>(code, jobs, n, st);
+template <int KS, int TW>
+static int launch_group_tw(int rag, int code, WgradTiledArgs* jobs, int n, bool alone, hipStream_t st) {
+  const bool limb = wg_use_limbs(KS, TW, code, rag);
+  switch (rag * 2 + limb) {
+    case 0: return launch_group_code<KS, TW, 0, 0>(code, jobs, n, alone, st);
+    case 1: return launch_group_code<KS, TW, 0, 1>(code, jobs, n, alone, st);
+    case 2: return launch_group_code<KS, TW, 1, 0>(code, jobs, n, alone, st);
+    case 3: return launch_group_code<KS, TW, 1, 1>(code, jobs, n, alone, st);
+    case 4: return launch_group_code<KS, TW, 2, 0>(code, jobs, n, alone, st);
+    default: return launch_group_code<KS, TW, 2, 1>(code, jobs, n, alone, st);
+  }
+}
+
+// the one dispatcher over (kernel size, tile width, RAG); the tile widths are those of tiled_tw / tiled_tw_ragged
+static int launch_group(int ks, int tw, int rag, int code, WgradTiledArgs* jobs, int n, bool alone, hipStream_t st) {
+  if (ks == 1 && tw == 32) return launch_group_tw<1, 32>(rag, code, jobs, n, alone, st);
+  if (ks == 1 && tw == 16) return launch_group_tw<1, 16>(rag, code, jobs, n, alone, st);
+  if (ks == 1 && tw == 8) return launch_group_tw<1, 8>(rag, code, jobs, n, alone, st);
+  if (ks == 3 && tw == 16) return launch_group_tw<3, 16>(rag, code, jobs, n, alone, st);
+  if (ks == 3 && tw == 8) return launch_group_tw<3, 8>(rag, code, jobs, n, alone, st);
+  return RSIS_ERR_ARG;
+}
+
+static WgradTiledArgs tiled_args(const WgradArgs& w) {
+  WgradTiledArgs a = {};
+  a.dy = w.dy; a.x = w.x; a.dw = w.dw; a.B = w.B; a.Cs = w.Cs; a.H = w.H; a.W = w.W; a.Cout = w.Cout;
+  a.ldo = w.ldo; a.n_off = w.n_off; a.interleave_hid = w.interleave_hid;
+  return a;
 }
 
 // n weight gradients that rsis_wgrad_tiled_supported accepts, all with the same kernel size: bucketed by (tile width, tile
 // configuration), one grouped launch per bucket (per RSIS_WG_MAXJ jobs of a bucket)
-int rsis_launch_conv_wgrad_tiled_group(const WgradArgs* w, int n, int ks, hipStream_t st) {
+static int tiled_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipStream_t st) {
   if (n < 1) return RSIS_OK;
   WgradTiledArgs* all = (WgradTiledArgs*)malloc(sizeof(WgradTiledArgs) * n * 2);
   int* key = (int*)malloc(sizeof(int) * n);
   if (!all || !key) { free(all); free(key); return RSIS_ERR_LAUNCH; }
   WgradTiledArgs* bucket = all + n;
   for (int j = 0; j < n; ++j) {
-    WgradTiledArgs a = {};
-    a.dy = w[j].dy; a.x = w[j].x; a.dw = w[j].dw; a.B = w[j].B; a.Cs = w[j].Cs; a.H = w[j].H; a.W = w[j].W; a.Cout = w[j].Cout;
-    a.ldo = w[j].ldo; a.n_off = w[j].n_off; a.interleave_hid = w[j].interleave_hid;
-    all[j] = a;
+    WgradTiledArgs& a = all[j] = tiled_args(w[j]);
     const int twa = tiled_tw(a.H, a.W, ks);
     if (twa) key[j] = twa * 8 + tiled_cfg_code(a, ks);
     else {                      // ragged map: 1024 = dword DMA (RAG 1), 2048 = whole dwordx4 groups (RAG 2)
-      if (ks == 1 && (a.H * a.W) % 4 == 0) { all[j].W = a.W = a.H * a.W; all[j].H = a.H = 1; }      // a 1x1 walks the flattened map
+      if (ks == 1 && (a.H * a.W) % 4 == 0) { a.W = a.H * a.W; a.H = 1; }      // a 1x1 walks the flattened map
       key[j] = (a.W % 4 == 0 ? 2048 : 1024) + tiled_tw_ragged(a.W, ks) * 8 + tiled_cfg_code(a, ks);
     }
   }
@@ -582,20 +584,15 @@ int rsis_launch_conv_wgrad_tiled_group(const WgradArgs* w, int n, int ks, hipStr
     int m = 0;
     for (int i = j; i < n; ++i)
       if (key[i] == k) { bucket[m++] = all[i]; key[i] = -1; }
-    const int rag = k >> 10;
-    const int tw = (k & 1023) / 8, code = k % 8;
-    if (rag == 1) {
-      if (ks == 1) rc = tw == 32 ? launch_group_tw<1, 32, 1>(code, bucket, m, st) : (tw == 16 ? launch_group_tw<1, 16, 1>(code, bucket, m, st) : launch_group_tw<1, 8, 1>(code, bucket, m, st));
-      else rc = tw == 16 ? launch_group_tw<3, 16, 1>(code, bucket, m, st) : launch_group_tw<3, 8, 1>(code, bucket, m, st);
-    } else if (rag == 2) {
-      if (ks == 1) rc = tw == 32 ? launch_group_tw<1, 32, 2>(code, bucket, m, st) : (tw == 16 ? launch_group_tw<1, 16, 2>(code, bucket, m, st) : launch_group_tw<1, 8, 2>(code, bucket, m, st));
-      else rc = tw == 16 ? launch_group_tw<3, 16, 2>(code, bucket, m, st) : launch_group_tw<3, 8, 2>(code, bucket, m, st);
-    } else if (ks == 1) rc = tw == 32 ? launch_group_tw<1, 32>(code, bucket, m, st) : (tw == 16 ? launch_group_tw<1, 16>(code, bucket, m, st) : launch_group_tw<1, 8>(code, bucket, m, st));
-    else rc = tw == 16 ? launch_group_tw<3, 16>(code, bucket, m, st) : launch_group_tw<3, 8>(code, bucket, m, st);
+    rc = launch_group(ks, (k & 1023) / 8, k >> 10, k % 8, bucket, m, alone, st);
   }
   free(all); free(key);
   return rc;
 }
+
+int rsis_launch_conv_wgrad_tiled_group(const WgradArgs* w, int n, int ks, hipStream_t st) { return tiled_launch_jobs(w, n, ks, false, st); }
+// one weight gradient in a launch of its own: a group of one job under the split plan of a single launch
+int rsis_launch_conv_wgrad_tiled(const WgradArgs& w, int ks, hipStream_t st) { return tiled_launch_jobs(&w, 1, ks, true, st); }
 
 // true when the LDS-DMA tiled kernel covers this weight gradient (stride 1, "same" padding, tile-aligned map, 32-bit offsets)
 bool rsis_wgrad_tiled_supported(const WgradArgs& w, int ks) {
@@ -604,19 +601,4 @@ bool rsis_wgrad_tiled_supported(const WgradArgs& w, int ks) {
   if (tiled_tw(w.H, w.W, ks) == 0 && !ragged_on) return false;      // (ragged maps: the RAG instantiations, grouped launch)
   const long img = (long)w.H * w.W * 4;
   return (long)w.Cout * img < (1L << 30) && (long)w.Cs * img < (1L << 30);
-}
-
-int rsis_launch_conv_wgrad_tiled(const WgradArgs& w, int ks, hipStream_t st) {
-  WgradTiledArgs a = {};
-  a.dy = w.dy; a.x = w.x; a.dw = w.dw; a.B = w.B; a.Cs = w.Cs; a.H = w.H; a.W = w.W; a.Cout = w.Cout;
-  a.ldo = w.ldo; a.n_off = w.n_off; a.interleave_hid = w.interleave_hid;
-  const int tw = tiled_tw(w.H, w.W, ks);
-  if (tw == 0) return rsis_launch_conv_wgrad_tiled_group(&w, 1, ks, st);       // ragged map: the grouped kernel with one job
-  if (ks == 1) {
-    if (tw == 32) return launch_tiled_tw<1, 32>(a, st);
-    if (tw == 16) return launch_tiled_tw<1, 16>(a, st);
-    return launch_tiled_tw<1, 8>(a, st);
-  }
-  if (tw == 16) return launch_tiled_tw<3, 16>(a, st);
-  return launch_tiled_tw<3, 8>(a, st);
 }

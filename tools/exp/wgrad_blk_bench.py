@@ -42,24 +42,3 @@ for (B, cin, cout, hw, ks) in SHAPES:
     byts = 2.0 * B * hw * hw * (cin + cout)
     fl = 2.0 * B * hw * hw * cin * cout * ks * ks
     print("%-26s %8.1f us | unique operand bytes %7.1f MB -> %6.2f TB/s | %7.1f TFLOP/s" % (tag, us, byts / 1e6, byts / us / 1e6, fl / us / 1e6))
-
-if os.environ.get("SWEEP"):      # library built with -DRSIS_W3T_SWEEP: tile height x ring depth of the 3x3 DMA kernel, per shape
-    from rsis_amd._lib import lib, ptr, stream
-    L = lib()
-    for (B, cin, cout, hw, ks) in SHAPES:
-        if ks != 3:
-            continue
-        x = torch.randn(B, cin // 8, hw, hw, 8, device="cuda").to(torch.bfloat16)
-        dy = torch.randn(B, cout // 8, hw, hw, 8, device="cuda").to(torch.bfloat16)
-        dW = torch.zeros(cout, cin, ks, ks, device="cuda")
-        row = []
-        for th in (2, 4, 8, 16):
-            for nr in (2, 3, 4, 5):
-                os.environ["RSIS_W3T_TH"], os.environ["RSIS_W3T_NR"] = str(th), str(nr)
-                call = lambda: L.rsis_conv2d_wgrad(ptr(dy), ptr(x), ptr(dW), B, cin, hw, hw, cout, hw, hw, ks, 1, 1, cin, 0, 0, ops.DTYPE_BF16_BLK, stream())
-                if call() != 0:
-                    continue
-                row.append((t_us(call), th, nr))
-        del os.environ["RSIS_W3T_TH"]
-        row.sort()
-        print("%dx%d->%d @%d: " % (B, cin, cout, hw) + "  ".join("th%d/nr%d %.1f" % (th, nr, us) for us, th, nr in row[:8]) + "  ... worst %.1f" % row[-1][0])
