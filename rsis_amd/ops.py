@@ -528,7 +528,7 @@ class _ConvLSTMFn(torch.autograd.Function):
     """ConvLSTMCell.forward (reference clstm.py:19-62) as one fused kernel; returns (h, c)."""
 
     @staticmethod
-    def forward(ctx, pack, pad, nx, has_state, *tensors):
+    def forward(ctx, pack, pad, nx, has_state, training, *tensors):
         xs = [_contig(t) for t in tensors[:nx]]
         h_prev, c_prev, weight, bias = tensors[nx], tensors[nx + 1], tensors[nx + 2], tensors[nx + 3]
         require_cuda_f32(weight, bias, h_prev, c_prev, *xs)
@@ -540,7 +540,10 @@ class _ConvLSTMFn(torch.autograd.Function):
             h_prev, c_prev = _contig(h_prev), _contig(c_prev)
             srcs.append(h_prev)
         wp = pack.fwd(weight, bias)
-        need_grad = any(ctx.needs_input_grad)  # (grad mode is off inside Function.forward)
+        # (grad mode is off inside Function.forward and ctx.needs_input_grad is True for parameters even under no_grad: convlstm()
+        #  decides whether this is a training call.  An inference call saves no gates -- act_out == NULL is what selects the
+        #  segmented-accumulation kernel in the library)
+        need_grad = training and any(ctx.needs_input_grad)
         h = torch.empty((B, hid, H, W), dtype=torch.float32, device=weight.device)
         c = torch.empty_like(h)
         act = torch.empty((B, 4 * hid, H, W), dtype=torch.float32, device=weight.device) if need_grad else None
@@ -570,7 +573,7 @@ class _ConvLSTMFn(torch.autograd.Function):
         check(L.rsis_convlstm_bwd_gates(ptr(dh), None, ptr(dc), ptr(act), ptr(c_prev), ptr(c), ptr(da), ptr(dc_prev), None, B, hid, H * W,
                                         stream()), "rsis_convlstm_bwd_gates")
         grads = [None] * (nx + 4)
-        need_src = list(ctx.needs_input_grad[4:4 + nx]) + ([ctx.needs_input_grad[4 + nx]] if has_state else [])
+        need_src = list(ctx.needs_input_grad[5:5 + nx]) + ([ctx.needs_input_grad[5 + nx]] if has_state else [])
         if any(need_src):
             wd = ctx.pack.dgrad(weight)
             dxs = _dgrad_all(L, da, wd, ctx.pack.cin, ks, 1, ctx.pad, srcs, H, W, dtype=ctx.pack.dtype)
@@ -581,21 +584,22 @@ class _ConvLSTMFn(torch.autograd.Function):
                 grads[nx] = dxs[nx]
         if has_state:
             grads[nx + 1] = dc_prev
-        if ctx.needs_input_grad[4 + nx + 2]:
+        if ctx.needs_input_grad[5 + nx + 2]:
             # zero state: the h_prev channels of dW get no contribution (h_prev == 0)
             grads[nx + 2] = _wgrad_all(L, da, srcs, tuple(weight.shape), ks, 1, ctx.pad, hid, dtype=ctx.pack.dtype)
-        if ctx.needs_input_grad[4 + nx + 3]:
+        if ctx.needs_input_grad[5 + nx + 3]:
             db = torch.zeros(4 * hid, dtype=torch.float32, device=da.device)
             check(L.rsis_bias_grad(ptr(da), ptr(db), B, 4 * hid, H * W, hid, stream()), "rsis_bias_grad")
             grads[nx + 3] = db
-        return (None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None) + tuple(grads)
 
 
 def convlstm(xs, state, weight, bias, pad, pack):
     """xs: list of NCHW tensors whose channel concat is the cell input; state: None or (h, c)."""
     has_state = state is not None
     h_prev, c_prev = (state[0], state[1]) if has_state else (None, None)
-    return _ConvLSTMFn.apply(pack, int(pad), len(xs), has_state, *xs, h_prev, c_prev, weight, bias)
+    training = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in list(xs) + [h_prev, c_prev, weight, bias])
+    return _ConvLSTMFn.apply(pack, int(pad), len(xs), has_state, training, *xs, h_prev, c_prev, weight, bias)
 
 
 class _UpsampleFn(torch.autograd.Function):

@@ -71,3 +71,52 @@ def same_matching(what, assignment, class_perm, ref_scores, ref_class_perm, tie=
 def sub_idx(n, cap=4096):
     """the deterministic sub-sample oracle/make_golden.py stores of a flat gradient / parameter vector"""
     return slice(0, n, max(1, n // cap))
+
+
+# ---- host models of the fp32 summation order of the direct 3x3 kernels (test_gpu_infer_paths.py, test_infer_paths_host.py)
+CK, ACC_FLUSH = 8, 4          # RSIS_CK, RSIS_ACC_FLUSH of csrc/conv3x3_direct.hip
+
+
+def f32_normal(seed, shape, scale=1.0):
+    return np.random.default_rng(seed).normal(0, scale, shape).astype(np.float32)
+
+
+def to_tensor(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def max_err(a, ref):
+    """max |a - ref| in float64; a: a tensor on any device or a numpy array, ref: a float64 tensor on the host"""
+    a = a.detach().double().cpu() if torch.is_tensor(a) else to_tensor(a).double()
+    return float((a - ref).abs().max())
+
+
+def host_sums(xs, w, b):
+    """3x3 / stride 1 / pad 1 conv of the channel concat of xs (float32 arrays) formed with fp32 products and fp32 additions in the two
+    summation orders; returns (chain, segmented), float32 (B, Cout, H, W).  `chain`: one running sum, sources in order, channels
+    ascending, taps row-major.  `segmented`: the same order, the running sum moved to a second fp32 total every ACC_FLUSH chunks of CK
+    channels, chunks counted on across the sources as the kernel counts them.  The bias is added last, as the kernels' epilogues add it."""
+    B, _, H, W = xs[0].shape
+    Cout = w.shape[0]
+    chain = np.zeros((B, Cout, H, W), np.float32)
+    acc, tot = np.zeros_like(chain), np.zeros_like(chain)
+    chunk, c_off = 0, 0
+    for x in xs:
+        xp = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)))
+        for c in range(x.shape[1]):
+            if c % CK == 0:                      # chunk number `chunk` (counted from 0 across the sources) begins
+                if chunk > 0 and chunk % ACC_FLUSH == 0:
+                    tot += acc
+                    acc[:] = 0
+                chunk += 1
+            for r in range(3):
+                for s in range(3):
+                    term = w[None, :, c_off + c, r, s, None, None] * xp[:, None, c, r:r + H, s:s + W]
+                    chain += term
+                    acc += term
+        c_off += x.shape[1]
+    seg = tot + acc
+    if b is not None:
+        chain, seg = chain + b[None, :, None, None], seg + b[None, :, None, None]
+    assert chain.dtype == np.float32 and seg.dtype == np.float32
+    return chain, seg
