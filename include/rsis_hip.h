@@ -8,7 +8,8 @@
  * Conventions
  *   - every pointer is a device pointer to a caller-owned, contiguous fp32 NCHW tensor unless stated (also under
  *     RSIS_DTYPE_BF16: only the private packed weight copies are bf16);
- *   - no hidden allocation, no host synchronisation, graph-capture safe; work is enqueued on `stream`
+ *   - no hidden allocation, no host synchronisation (one stated exception: rsis_targets_from_maps), graph-capture safe; work is
+ *     enqueued on `stream`
  *     (a hipStream_t passed as void*; NULL = the default stream);
  *   - return value: 0 = OK, nonzero = error code (rsis_error_string); nothing throws across the ABI;
  *   - thread-safe / re-entrant per stream.
@@ -324,6 +325,30 @@ int rsis_sum_leading(const float* x, float* y, int T, long n, void* stream);
  * row ignored) or 2.  y[n][c][i][j] = x[n][c][round(clamp(A (i-ci, j-cj) + b + (ci, cj)))], ci = H/2 - 0.5, cj = W/2 - 0.5,
  * float32 arithmetic in the reference's operation order, round half to even: bit-exact with the reference. ---- */
 int rsis_affine_nearest(const float* x, float* y, const float* mat, int mat_rows, int N, int C, int H, int W, void* stream);
+
+/* ---- data-layer targets for a whole batch in one call (dataloader/dataset.py:86-146 sequence_from_masks + utils.batch_to_var):
+ * ins, seg: [B][H][W] int32 instance-id / class-id maps; T = gt_maxseqlen.  Per image the smallest id PRESENT is the background and is
+ * dropped; the other ids become rows ordered by area, largest first (equal areas: the larger id first), truncated to T:
+ *   y_mask[B][T][H*W] fp32 = 1 where ins == the row's id (EVERY element is written: no memset is needed), y_class[B][T] int64 = the
+ *   smallest seg value under the instance (0 on an empty row), sw_mask[B][T] fp32 = 1 on instance rows, sw_class[B][T] fp32 = 1 on
+ *   instance rows and on the first empty row.
+ * Integer counts and integer atomics only: the result does not depend on the order of execution.  work: caller-owned scratch of
+ * rsis_targets_work_ints(B) int32.  Instance ids must lie in 0..255 (Pascal VOC, CVPPP); otherwise RSIS_ERR_UNSUPPORTED is returned and
+ * no output has been written.  That test needs the histogram of the batch, so this call -- unlike the rest of the library --
+ * synchronises `stream` once and must not be made during a stream capture.  H*W < 2^31, B <= 65535. ---- */
+long rsis_targets_work_ints(int B);
+int rsis_targets_from_maps(const int* ins, const int* seg, int B, int H, int W, int T, float* y_mask, long long* y_class, float* sw_mask,
+                           float* sw_class, int* work, void* stream);
+
+/* ---- Pascal VOC preparation (dataloader/pascal_precompute.py:36-101; dataset_utils.py convert_from_color_segmentation) ----
+ * rsis_palette_to_ids: rgb[npix][3] uint8 -> ids[npix] uint8 through a colour table table[ntab][4] = (r, g, b, id) in DEVICE memory,
+ *   ntab <= 256; the first matching entry wins, a colour that is not in the table maps to 0.
+ * rsis_idmap_rle_encode: idmap[h][w] uint8 (ROW-major, as the .npy stores it) and k ids[k] (device, int32) -> the run counts of the k
+ *   masks (idmap == ids[j]) in the COLUMN-major element order of rsis_rle_encode, one launch, without forming the k byte masks:
+ *   counts[k][cap] / nruns[k] exactly as rsis_rle_encode writes them (nruns negative when cap is too small).  h*w < 2^32. */
+int rsis_palette_to_ids(const unsigned char* rgb, long npix, const unsigned char* table, int ntab, unsigned char* ids, void* stream);
+int rsis_idmap_rle_encode(const unsigned char* idmap, int h, int w, const int* ids, int k, unsigned int* counts, int cap, int* nruns,
+                          void* stream);
 
 /* ---- soft-IoU matching scores and matched-loss gradient (train.py:98-110,127-131,162-163; hungarian.py:62-89 softIoU) ----
  * rsis_softiou_sums: logits[B][T][N] (mask logits of the T predictions), y[B][G][N] (ground-truth masks, 0/1 floats) ->

@@ -68,6 +68,10 @@ int rsis_l_gmax_bwd_add(const float*, const int*, float*, long, int, hipStream_t
 int rsis_l_pack_batch(const rsis_pack_job*, int, int, hipStream_t);
 int rsis_l_pack_blocks(int mode, int krows, int ldw, int ks);
 int rsis_l_affine_nearest(const float*, float*, const float*, int, int, int, int, int, hipStream_t);
+long rsis_l_targets_work_ints(int);
+int rsis_l_targets_from_maps(const int*, const int*, int, int, int, int, float*, long long*, float*, float*, int*, hipStream_t);
+int rsis_l_palette_to_ids(const unsigned char*, long, const unsigned char*, int, unsigned char*, hipStream_t);
+int rsis_l_idmap_rle_encode(const unsigned char*, int, int, const int*, int, unsigned int*, int, int*, hipStream_t);
 int rsis_l_mask_resize_threshold(const float*, int, int, int, const unsigned char*, float, unsigned char*, unsigned char*, unsigned int*,
                                  int, int, hipStream_t);
 int rsis_l_rle_encode(const unsigned char*, int, long, unsigned int*, int, int*, hipStream_t);
@@ -293,6 +297,26 @@ int rsis_affine_nearest(const float* x, float* y, const float* mat, int mat_rows
   if (!x || !y || !mat || x == y || N < 1 || C < 1 || H < 1 || W < 1 || (mat_rows != 2 && mat_rows != 3)) return RSIS_ERR_ARG;
   if ((long)H * W >= (1L << 31) || N > 65535) return RSIS_ERR_UNSUPPORTED;
   return rsis_l_affine_nearest(x, y, mat, N, C, H, W, mat_rows * 3, (hipStream_t)stream);
+}
+
+long rsis_targets_work_ints(int B) { return B < 1 ? 0 : rsis_l_targets_work_ints(B); }
+
+int rsis_targets_from_maps(const int* ins, const int* seg, int B, int H, int W, int T, float* y_mask, long long* y_class, float* sw_mask,
+                           float* sw_class, int* work, void* stream) {
+  if (!ins || !seg || !y_mask || !y_class || !sw_mask || !sw_class || !work || B < 1 || H < 1 || W < 1 || T < 1) return RSIS_ERR_ARG;
+  if ((long)H * W >= (1L << 31) || B > 65535) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_targets_from_maps(ins, seg, B, H, W, T, y_mask, y_class, sw_mask, sw_class, work, (hipStream_t)stream);
+}
+
+int rsis_palette_to_ids(const unsigned char* rgb, long npix, const unsigned char* table, int ntab, unsigned char* ids, void* stream) {
+  if (!rgb || !table || !ids || npix < 1 || ntab < 1 || ntab > 256) return RSIS_ERR_ARG;
+  return rsis_l_palette_to_ids(rgb, npix, table, ntab, ids, (hipStream_t)stream);
+}
+
+int rsis_idmap_rle_encode(const unsigned char* idmap, int h, int w, const int* ids, int k, unsigned int* counts, int cap, int* nruns,
+                          void* stream) {
+  if (!idmap || !ids || !counts || !nruns || h < 1 || w < 1 || k < 1 || cap < 1 || (long)h * w >= (1L << 32)) return RSIS_ERR_ARG;
+  return rsis_l_idmap_rle_encode(idmap, h, w, ids, k, counts, cap, nruns, (hipStream_t)stream);
 }
 
 int rsis_conv_pack_job_fill(rsis_pack_job* j) {

@@ -1,5 +1,6 @@
 """Target-tensor construction of the reference's data layer (reference src/dataloader/dataset.py:86-146), SURVEY.md section
 8(f) row N3: the step that turns an instance-id map + a class map into what `runIter` consumes (targets), the affine augmentation
-(augment), and the CVPPP A1 leaves reader + device batch loader of BASELINE configs[0] (leaves).  The Pascal VOC (HDF5 / SBD) and
-Cityscapes (JSON polygons) readers are host I/O outside the hot path and are not part of this build."""
+(augment), and the CVPPP A1 leaves reader + device batch loader of BASELINE configs[0] (leaves), and the Pascal VOC reader on the same loader
+(pascal; its ProcMasks / VOCGT_<split>.pkl come from `python -m rsis_amd.pascal_precompute`).  The Cityscapes (JSON polygons) reader
+is host I/O outside the hot path and is not part of this build."""
 from .targets import sequence_from_masks, targets_from_maps  # noqa: F401

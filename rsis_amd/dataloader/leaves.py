@@ -89,7 +89,7 @@ class LeavesDataset(object):
         if hit is not None:
             return hit
         item = self._decode(index)
-        nbytes = item[0].nbytes + item[1].nbytes
+        nbytes = sum(a.nbytes for a in item)
         if self._cache_bytes + nbytes <= self._cache_limit:
             self._cache[index] = item
             self._cache_bytes += nbytes
@@ -143,6 +143,8 @@ class DeviceLoader(object):
     """DataLoader(dataset, batch_size, shuffle=True, drop_last=True) of train.py:46-49 yielding DEVICE batches
     (x, y_mask, y_class, sw_mask, sw_class) -- what utils.batch_to_var returns.  The next batch is decoded into pinned memory by
     `num_workers` threads and copied on a side stream while the current one trains.
+    A dataset whose `host_item` returns (image, ins) has its class map derived as `ins > 0` (leaves); one that returns (image, ins, seg)
+    (dataloader/pascal.py) has `seg` staged, copied and warped next to `ins`.
 
     One process per GPU (rank / world): `batch_size` is the PER-RANK batch; every rank shuffles the whole dataset with the SAME
     seed and takes samples r, r + world, ... of each global batch of batch_size * world, so that an epoch is
@@ -176,15 +178,18 @@ class DeviceLoader(object):
         with torch.cuda.stream(self.copy_stream):           # (sw_mask was produced there: the sync waits for the batch, not for the step in flight)
             return steps_to_run(args, sw_mask)
 
-    def _pinned(self, slot, n, S):
+    def _pinned(self, slot, n, S, with_seg=False):
         """two sets of pinned staging buffers, reused: `torch.empty(...).pin_memory()` per batch is a hipHostMalloc + first-touch page faults
         -- 1.9 of the 2.15 ms a batch of two CACHED samples took to stage (tools/exp/stage_bench.py), more than the GPU needs for a tenth
         of its step.  A set is refilled only after the host-to-device copy that last read it has completed (event)."""
-        key = (slot & 1, n, tuple(S))
+        key = (slot & 1, n, tuple(S), bool(with_seg))
         ent = self._pins.get(key)
         if ent is None:
             ent = [torch.empty((n, 3) + tuple(S), dtype=torch.uint8).pin_memory(), torch.empty((n,) + tuple(S), dtype=torch.int32).pin_memory(), None]
             ent += [ent[0].numpy(), ent[1].numpy()]            # (filled through numpy: a torch CPU copy_ of 200 KB costs ~1 ms of thread-pool wake-up)
+            if with_seg:                                       # a dataset with a class map of its own (Pascal VOC): ent[5], ent[6]
+                ent.append(torch.empty((n,) + tuple(S), dtype=torch.int32).pin_memory())
+                ent.append(ent[5].numpy())
             self._pins[key] = ent
         if ent[2] is not None:
             ent[2].synchronize()
@@ -200,11 +205,14 @@ class DeviceLoader(object):
         else:
             items = list(self.pool.map(lambda a: self.ds.host_item(a[0], random.Random(a[1])), work))
         S = items[0][0].shape[1:]
-        ent = self._pinned(slot, len(items), S)
+        with_seg = len(items[0]) == 3                          # (image, ins, seg): the class map is staged, copied and warped too
+        ent = self._pinned(slot, len(items), S, with_seg)
         img, ins = ent[0], ent[1]
-        for i, (a, b) in enumerate(items):
-            np.copyto(ent[3][i], a)
-            np.copyto(ent[4][i], b)
+        for i, it in enumerate(items):
+            np.copyto(ent[3][i], it[0])
+            np.copyto(ent[4][i], it[1])
+            if with_seg:
+                np.copyto(ent[6][i], it[2])
         mats = None
         if self.ds.augmentation_transform is not None:                      # one matrix per sample, drawn as the reference draws them
             with self._lock:
@@ -222,6 +230,7 @@ class DeviceLoader(object):
         with torch.cuda.stream(st):
             x = img.to(self.device, non_blocking=True)
             m = ins.to(self.device, non_blocking=True)
+            sg = ent[5].to(self.device, non_blocking=True) if ent is not None and len(ent) > 5 else None
             if ent is not None:                 # the staging set may be refilled once these two copies have run
                 ent[2] = torch.cuda.Event()
                 ent[2].record(st)
@@ -231,7 +240,13 @@ class DeviceLoader(object):
                 x = affine_nearest(x, mats)
                 mf = affine_nearest(mf, mats)
             ins_d = mf.squeeze(1).round().long()
-            seg_d = (ins_d > 0).long()                                          # leaves.py:105-106
+            if sg is None:
+                seg_d = (ins_d > 0).long()                                      # leaves.py:105-106
+            else:
+                sf = sg.float().unsqueeze(1)
+                if mats is not None:
+                    sf = affine_nearest(sf, mats)
+                seg_d = sf.squeeze(1).round().long()
             y_mask, y_class, sw_mask, sw_class = targets_from_maps(ins_d, seg_d, self.ds.max_seq_len, device=self.device)
             out = (x.contiguous(), y_mask, y_class, sw_mask, sw_class)
         cur.wait_stream(st)

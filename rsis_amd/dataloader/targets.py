@@ -42,14 +42,46 @@ def sequence_from_masks(ins, seg, max_seq_len):
     return np.concatenate((gt_seg, gt_classes, sw_mask, sw_class), axis=1)
 
 
-def targets_from_maps(ins, seg, max_seq_len, device="cuda"):
+ERR_UNSUPPORTED = 3          # RSIS_ERR_UNSUPPORTED of include/rsis_hip.h
+
+
+def targets_kernel(ins, seg, max_seq_len):
+    """The whole batch in one call of librsis_hip.so (rsis_targets_from_maps: a histogram launch, one host sync, a write launch):
+    ins, seg: (B, H, W) CUDA integer tensors -> (y_mask, y_class, sw_mask, sw_class), or None when an instance id lies outside 0..255
+    (the kernel's range: RSIS_ERR_UNSUPPORTED).  Class ids must fit int32."""
+    from .._lib import check, lib, ptr, stream
+    L = lib()
+    B, H, W = ins.shape
+    T = int(max_seq_len)
+    dev = ins.device
+    ins32 = ins.clamp(-1, 256).to(torch.int32).contiguous()               # (out-of-range ids stay out of range after the narrowing)
+    seg32 = seg.to(torch.int32).contiguous()
+    y_mask = torch.empty((B, T, H * W), dtype=torch.float32, device=dev)   # every element is written by the kernel
+    y_class = torch.empty((B, T), dtype=torch.int64, device=dev)
+    sw_mask = torch.empty((B, T), dtype=torch.float32, device=dev)
+    sw_class = torch.empty((B, T), dtype=torch.float32, device=dev)
+    work = torch.empty((int(L.rsis_targets_work_ints(B)),), dtype=torch.int32, device=dev)
+    rc = L.rsis_targets_from_maps(ptr(ins32), ptr(seg32), B, H, W, T, ptr(y_mask), ptr(y_class), ptr(sw_mask), ptr(sw_class), ptr(work),
+                                  stream())
+    if rc == ERR_UNSUPPORTED:
+        return None
+    check(rc, "rsis_targets_from_maps")
+    return y_mask, y_class, sw_mask, sw_class
+
+
+def targets_from_maps(ins, seg, max_seq_len, device="cuda", use_kernel=True):
     """Same content as utils.batch_to_var(sequence_from_masks(...)) for a batch of maps, built on the device:
     ins, seg: (B, H, W) integer arrays / tensors -> (y_mask (B, T, H*W) fp32, y_class (B, T) int64, sw_mask (B, T) fp32,
-    sw_class (B, T) fp32) with T = max_seq_len."""
+    sw_class (B, T) fp32) with T = max_seq_len.  The grouped kernel (targets_kernel) is tried first; maps it does not take (an
+    instance id above 255, CPU tensors) go through the per-image loop below, whose result the kernel's equals bit for bit."""
     ins = torch.as_tensor(np.asarray(ins) if not torch.is_tensor(ins) else ins).to(device).long()
     seg = torch.as_tensor(np.asarray(seg) if not torch.is_tensor(seg) else seg).to(device).long()
     B, H, W = ins.shape
     T = int(max_seq_len)
+    if use_kernel and ins.is_cuda and B > 0 and H * W > 0 and T > 0:
+        out = targets_kernel(ins, seg, T)
+        if out is not None:
+            return out
     y_mask = torch.zeros((B, T, H * W), dtype=torch.float32, device=device)
     y_class = torch.zeros((B, T), dtype=torch.int64, device=device)
     sw_mask = torch.zeros((B, T), dtype=torch.float32, device=device)

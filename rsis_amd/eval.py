@@ -12,8 +12,16 @@ maxDets = [1, -max_dets, 100], useCats = not --ignore_cats, all classes together
 device (rsis_amd/cocoeval.py): the thresholded masks are bit-packed where they lie, one row per predicted MASK (the C - 1 records
 of a mask share it), the ground truth comes from the loader's targets.  The 13 stats are printed in the reference's format and
 written to <model_name>_<eval_split>_cocoeval.json.  `-cat_id` is parsed and has no effect, as in the reference (eval.py:381-385
-overwrites it).  Not built (out of scope): the dataset readers (so only `--synthetic` inputs are wired; a
-ground-truth FILE is evaluated with `python -m rsis_amd.cocoeval`), the matplotlib display path.
+overwrites it).
+
+    python -m rsis_amd.eval -dataset pascal -pascal_dir D -eval_split val -model_name <name> -batch_size 1
+
+evaluates Pascal VOC (eval.py:191-218,280-295): the images come from dataloader/pascal.py in sample order (drop_last=False), every
+mask is resampled to its image's ORIGINAL size, the ground truth is <D>/VOCGT_<eval_split>.pkl (rsis_amd.pascal_precompute, or the
+reference's own file, python-2 pickle included) and each image's `ignore == 1` record gives the pixels cleared from its predictions.
+Nothing is written into the dataset directory (the reference's pascal_<split>.json is an artefact of pycocotools' file interface).
+Not built (out of scope): the Cityscapes reader, the matplotlib display path; a ground-truth FILE of another
+dataset is evaluated with `python -m rsis_amd.cocoeval`.
 """
 import json
 import os
@@ -23,12 +31,12 @@ import numpy as np
 import torch
 
 from .args import get_parser
-from .cocoeval import COCOEvalDevice, run_reference_protocol
+from .cocoeval import COCOEvalDevice, rle_from_string, run_reference_protocol
 from .eval_post import encode_masks, resize_mask  # noqa: F401  (resize_mask: reference signature, eval.py:96-127)
 from .modules.model import RSIS, FeatureExtractor
 from .synthetic import SyntheticLoader
 from .test import test
-from .utils.utils import check_parallel, load_checkpoint
+from .utils.utils import check_parallel, load_checkpoint, load_plain_pickle
 
 
 def create_annotation(args, imname, pred_mask, class_id, score, classes, is_valid=True):
@@ -64,19 +72,51 @@ class Evaluate(object):
     def __init__(self, args):
         self.args = args
         self.split = args.eval_split
+        self.gt_records = self.ignore_rle = self.dataset = None
         if not getattr(args, "synthetic", False):
-            raise Exception("only --synthetic inputs are wired in this build (the dataset readers of the reference's "
-                            "src/dataloader are host-side I/O outside the hot path: SURVEY.md section 8)")
+            if args.dataset != "pascal":
+                raise Exception("only --synthetic inputs and -dataset pascal are wired in this build (the Cityscapes reader of the "
+                                "reference's src/dataloader is host-side I/O outside the hot path: SURVEY.md section 8)")
+            self._init_pascal()
+            return
         self.encoder, self.decoder = load_models(self.args)
         self.class_names = ["<eos>"] + ["class%d" % i for i in range(1, self.args.num_classes)]
         self.loader = SyntheticLoader(args, max(1, args.synthetic_batches // 4), args.seed + 7)
         self.sample_list = ["synthetic_%06d" % i for i in range(len(self.loader) * args.batch_size)]
+
+    def _init_pascal(self):
+        """eval.py:191-218 for -dataset pascal"""
+        from .dataloader.leaves import DeviceLoader
+        from .dataloader.pascal import PascalVOC
+        args = self.args
+        self.dataset = PascalVOC(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        self.sample_list = [s.rstrip() for s in self.dataset.get_sample_list()]
+        self.class_names = self.dataset.get_classes()
+        self.gt_records = load_plain_pickle(os.path.join(args.pascal_dir, "VOCGT_%s.pkl" % self.split))
+        self.ignore_rle = {}                                        # image id -> segmentation of its ignore mask (eval.py:198-209)
+        for ann in self.gt_records:
+            if ann["ignore"] == 1:
+                self.ignore_rle[ann["image_id"]] = ann["segmentation"]
+        self.encoder, self.decoder = load_models(args)
+        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
+                                   drop_last=False)
+
+    def _ignore_mask(self, sample_idx):
+        """the (h, w) uint8 ignore mask of one image, decoded from its record (column-major runs, the first one of zeros)"""
+        seg = self.ignore_rle[sample_idx]
+        h, w = int(seg["size"][0]), int(seg["size"][1])
+        counts = rle_from_string(seg["counts"])
+        vals = np.arange(len(counts), dtype=np.uint8) & 1
+        return np.ascontiguousarray(np.repeat(vals, counts.astype(np.int64)).reshape(w, h).T)
 
     def _create_json(self):
         """eval.py:254-345: one record per (instance, class) with score = class probability * objectness"""
         args = self.args
         predictions, shown, acc = [], [], 0
         coco = self.coco = None if getattr(args, "no_run_coco_eval", False) else COCOEvalDevice()
+        if coco is not None and self.gt_records is not None:
+            mine = set(self.sample_list)
+            coco.add_gt([r for r in self.gt_records if r["image_id"] in mine])
         for inputs, y_mask, y_class, sw_mask, _sw_class in self.loader:
             x = inputs
             out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)       # eval.py:262
@@ -86,8 +126,12 @@ class Evaluate(object):
             h, w = x.size(-2), x.size(-1)                          # (synthetic images: the "original" size is the input size)
             for s in range(out_masks.shape[0]):
                 sample_idx = self.sample_list[s + acc]
+                ignore = None
+                if self.dataset is not None:                       # eval.py:280-295: the ORIGINAL size, the image's ignore pixels
+                    h, w = self.dataset.raw_size(s + acc)
+                    ignore = self._ignore_mask(sample_idx)
                 # all T masks of the image in one launch each: resample + threshold + area, then run-length encoding
-                segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, None, want_bits=True)
+                segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True)
                 rows, cats, recscores = [], [], []                  # of the records that reach the predictions file
                 for i in range(out_masks.shape[1]):
                     objectness = float(stops[s][i][0])
@@ -109,9 +153,9 @@ class Evaluate(object):
                         recscores.append(score)
                 if coco is not None:
                     # ground truth of the image from the loader's targets, in the detections' (column-major) element order
-                    n_gt = int((sw_mask[s] > 0).sum())
-                    gt_m = (y_mask[s, :n_gt].reshape(n_gt, h, w).transpose(1, 2) > 0.5).to(torch.uint8).reshape(n_gt, h * w)
+                    n_gt = int((sw_mask[s] > 0).sum()) if self.gt_records is None else 0     # (Pascal: the records of the file)
                     if n_gt:
+                        gt_m = (y_mask[s, :n_gt].reshape(n_gt, h, w).transpose(1, 2) > 0.5).to(torch.uint8).reshape(n_gt, h * w)
                         coco.add_gt_masks(sample_idx, gt_m, [int(c) for c in y_class[s, :n_gt].cpu()])
                     if rows:
                         kept = sorted(set(rows))                     # only the masks that have records go into the pool

@@ -139,6 +139,19 @@ def _plain(v):
     return v
 
 
+def load_plain_pickle(path):
+    """A pickle of plain values (lists / dicts of numbers, strings, bytes, numpy scalars) through the closed-list unpickler above:
+    a file written by python 3, or by python 2 (whose `str` payloads are read as latin1 -- the VOCGT_<split>.pkl of the reference's
+    pascal_precompute.py holds its RLE counts that way).  Anything that references another class is refused."""
+    with open(path, "rb") as f:
+        try:
+            obj = _ArgsUnpickler(f).load()
+        except UnicodeDecodeError:
+            f.seek(0)
+            obj = _ArgsUnpickler(f, encoding="latin1").load()
+    return _plain(obj)
+
+
 def load_checkpoint(model_name, use_gpu=True, root="../models"):
     """reference utils/utils.py:97-111.  The four .pt files are tensor dictionaries: files in torch's current zip format (this build's
     own checkpoints, anything saved by torch >= 1.6) are read with weights_only=True; files in the pre-zip container the REFERENCE's
