@@ -859,7 +859,7 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* __restric
     for (long g = blockIdx.y * 256L + threadIdx.x; g < ng; g += gridDim.y * 256L) {
       const long b = g / hwg; const int sp = (int)(g - b * hwg) * 4;
       const f32x4 v = *reinterpret_cast<const f32x4*>(dy + (b * C + c) * HW + sp);
-      s += (v[0] + v[1]) + (v[2] + v[3]);
+      s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);   // (fp32 pair sums would round once per group: both paths add in double)
     }
   } else {
     for (long e = blockIdx.y * 256L + threadIdx.x; e < N; e += gridDim.y * 256L) {

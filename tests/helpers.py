@@ -120,3 +120,105 @@ def host_sums(xs, w, b):
         chain, seg = chain + b[None, :, None, None], seg + b[None, :, None, None]
     assert chain.dtype == np.float32 and seg.dtype == np.float32
     return chain, seg
+
+
+# ---- the fp32 ConvLSTM pointwise backward (test_gpu_decoder_bwd_ops.py, test_decoder_bwd_host.py): reference, bars, guarded buffers
+LSTM_BWD_K = 24               # allowed error in units of 2^-24 * lstm_bwd_scales(..): see test_decoder_bwd_host.py for the derivation
+LSTM_BWD_OUTS = ("da_i", "da_f", "da_o", "da_g", "dc_prev")
+
+
+def lstm_bwd_inputs(seed, B, hid, HW, c_scale=1.0):
+    """fp32 operands of one cell's pointwise backward: act (B, 4 hid, HW) in gate-interleaved rows 4 j + gate (i, f, o sigmoid, g tanh of
+    N(0, 2) pre-activations, so saturated gates occur), c / c_prev N(0, c_scale), dh / dh2 / dc_next N(0, 1)"""
+    rs = np.random.default_rng(seed)
+    pre = rs.normal(0, 2, (B, hid, 4, HW))
+    act = np.concatenate([1.0 / (1.0 + np.exp(-pre[:, :, :3])), np.tanh(pre[:, :, 3:])], 2).astype(np.float32).reshape(B, 4 * hid, HW)
+    n = lambda s: rs.normal(0, s, (B, hid, HW)).astype(np.float32)
+    return dict(act=act, c=n(c_scale), c_prev=n(c_scale), dh=n(1), dh2=n(1), dc_next=n(1))
+
+
+def _lstm_bwd_terms(q, dt):
+    """the operands of pointwise.hip's header formulas in dtype dt; an absent operand (None) is 0"""
+    B, hid4, HW = q["act"].shape
+    a = q["act"].astype(dt).reshape(B, hid4 // 4, 4, HW)
+    z = np.zeros((B, hid4 // 4, HW), dt)
+    get = lambda k: q[k].astype(dt) if q.get(k) is not None else z
+    return a[:, :, 0], a[:, :, 1], a[:, :, 2], a[:, :, 3], q["c"].astype(dt), get("c_prev"), get("dh"), get("dh2"), get("dc_next")
+
+
+def lstm_bwd_eval(q, dt=np.float64):
+    """do = dh tanh(c); dc = dc_next + dh o (1 - tanh(c)^2); da_i = dc g i (1 - i), da_f = dc c_prev f (1 - f), da_o = do o (1 - o),
+    da_g = dc i (1 - g^2), dc_prev = dc f  (dh = dh + dh2), every operation in dtype dt: float64 is the reference, float32 the host
+    model of the kernels' arithmetic.  Returns {name: (B, hid, HW)} for LSTM_BWD_OUTS."""
+    i, f, o, g, c, cp, dh, dh2, dn = _lstm_bwd_terms(q, dt)
+    one = dt(1)
+    tc = np.tanh(c)
+    dhv = dh + dh2
+    dcv = dhv * o * (one - tc * tc) + dn
+    out = dict(da_i=dcv * g * i * (one - i), da_f=dcv * cp * f * (one - f), da_o=dhv * tc * o * (one - o), da_g=dcv * i * (one - g * g),
+               dc_prev=dcv * f)
+    assert all(v.dtype == dt for v in out.values())
+    return out
+
+
+def lstm_bwd_scales(q):
+    """per-element magnitudes that one fp32 rounding is measured against (float64), M = (|dh| + |dh2|) o + |dc_next|: cancellation in dc
+    and in 1 - g^2 is charged to the terms that cancel, not hidden behind max|ref|.  The 1/8 of da_g admits the one ABSOLUTE rounding
+    of g^2 next to 1."""
+    i, f, o, g, c, cp, dh, dh2, dn = _lstm_bwd_terms(q, np.float64)
+    adh = np.abs(dh) + np.abs(dh2)
+    M = adh * o + np.abs(dn)
+    return dict(da_i=M * np.abs(g * i * (1 - i)), da_f=M * np.abs(cp * f * (1 - f)), da_o=adh * np.abs(np.tanh(c)) * o * (1 - o),
+                da_g=M * i * ((1 - g * g) + 0.125), dc_prev=M * f)
+
+
+def lstm_bwd_ratios(got, q):
+    """{name: worst |got - float64 reference| / (2^-24 * scale)} over the outputs present in `got` ({name: (B, hid, HW) array});
+    where the scale is 0 the output must be exactly the reference (inf otherwise)"""
+    ref, sc = lstm_bwd_eval(q), lstm_bwd_scales(q)
+    worst = {}
+    for k, v in got.items():
+        v = np.asarray(v, np.float64)
+        assert v.shape == ref[k].shape, "%s: shape %s vs %s" % (k, v.shape, ref[k].shape)
+        if not np.isfinite(v).all():
+            worst[k] = float("inf")
+            continue
+        err, s = np.abs(v - ref[k]), sc[k] * 2.0 ** -24
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(s > 0, err / s, np.where(err > 0, np.inf, 0.0))
+        worst[k] = float(r.max())
+    return worst
+
+
+def split_da(da):
+    """(B, 4 hid, HW) gate-interleaved rows -> {da_i, da_f, da_o, da_g: (B, hid, HW)}"""
+    da = np.asarray(da)
+    B, hid4, HW = da.shape
+    v = da.reshape(B, hid4 // 4, 4, HW)
+    return dict(da_i=v[:, :, 0], da_f=v[:, :, 1], da_o=v[:, :, 2], da_g=v[:, :, 3])
+
+
+GUARD, SENTINEL = 64, -12345.5
+
+
+class Guarded(object):
+    """an output tensor as a view into one larger allocation with GUARD floats of SENTINEL on each side: .t is the view (filled with
+    SENTINEL, or with `init`), .check() asserts that both guard zones still hold the sentinel -- writes outside the tensor but inside
+    the allocation are seen, nothing is provoked.  offset: extra floats in front (1: a view that is not 16-byte aligned)."""
+
+    def __init__(self, shape, device="cuda", init=None, offset=0):
+        n = int(np.prod(shape))
+        self.buf = torch.full((n + 2 * GUARD + offset,), SENTINEL, dtype=torch.float32, device=device)
+        self.lo, self.hi = GUARD + offset, GUARD + offset + n
+        self.t = self.buf[self.lo:self.hi].view(*shape)
+        if init is not None:
+            self.t.copy_(torch.as_tensor(init))
+
+    def check(self, what="output"):
+        lo, hi = self.buf[:self.lo], self.buf[self.hi:]
+        assert hi.numel() == GUARD
+        assert bool((lo == SENTINEL).all()), "%s: the guard zone in FRONT of the tensor was written" % what
+        assert bool((hi == SENTINEL).all()), "%s: the guard zone BEHIND the tensor was written" % what
+
+    def untouched(self):
+        return bool((self.t == SENTINEL).all())
