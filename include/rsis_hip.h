@@ -246,6 +246,22 @@ int rsis_bn_bwd_eval(const float* dy, const float* x, const float* y, const floa
                      const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW,
                      float eps, int relu, void* stream);
 
+/* The same three with the ReLU mask of the forward output as bytes, for layers with ReLU and HW % 4 == 0 (RSIS_ERR_UNSUPPORTED
+ * otherwise, before anything is launched: the caller keeps y and uses the three above).  ReLU is implied (no relu argument / bit0).
+ * mask is [B*C*HW / 4] bytes: mask[i / 4] for the float4 group at flat NCHW element index i, bit k = (y[i + k] > 0) taken from
+ * the value stored as y (NaN gives 0) -- the layout depends on the element index alone.  rsis_bn_fwd_mask writes y exactly as
+ * rsis_bn_fwd(relu = 1) does, and the mask beside it; the backward entry points read the mask where the ones above read y (1 byte
+ * instead of 16 per group) and write exactly what those write given that y.  flags: bit1 / bit2 as the relu argument above. */
+int rsis_bn_fwd_mask(const float* x, const float* res, float* y, unsigned char* mask, double* stats, const float* gamma, const float* beta,
+                     float* running_mean, float* running_var, float* save_mean, float* save_rstd, int B, int C, int HW,
+                     float eps, float momentum, int train, void* stream);
+int rsis_bn_bwd_mask(const float* dy, const float* x, const unsigned char* mask, const float* save_mean, const float* save_rstd,
+                     const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C,
+                     int HW, int flags, void* stream);
+int rsis_bn_bwd_eval_mask(const float* dy, const float* x, const unsigned char* mask, const float* running_mean, const float* running_var,
+                          const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW,
+                          float eps, int flags, void* stream);
+
 /* ---- y[bc][ho][wo] = x[bc][ho * stride][wo * stride], y is [BC][(H-1)/stride+1][(W-1)/stride+1]: the dense input of a
  * 1x1 / stride-s conv (torchvision Bottleneck downsample, layers 2-4; reference vision.py:16-19) -- x[:, :, ::s, ::s].contiguous().
  * The conv then runs as its stride-1 form (rsis_conv2d_fwd on y) and y is what its weight gradient reads. ---- */

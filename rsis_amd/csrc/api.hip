@@ -53,10 +53,10 @@ int rsis_l_upsample_fwd(const float*, float*, long, int, int, int, int, hipStrea
 int rsis_l_upsample_bwd(const float*, float*, long, int, int, int, int, const float*, const int*, hipStream_t);
 int rsis_l_gmax_fwd(const float*, float*, int*, long, int, hipStream_t);
 int rsis_l_gmax_bwd(const float*, const int*, float*, long, int, hipStream_t);
-int rsis_l_bn_fwd(const float*, const float*, float*, double*, const float*, const float*, float*, float*, float*, float*, int,
-                  int, int, float, float, int, int, hipStream_t);
-int rsis_l_bn_bwd(const float*, const float*, const float*, const float*, const float*, const float*, double*, float*, float*,
-                  float*, float*, int, int, int, int, float, hipStream_t);
+int rsis_l_bn_fwd(const float*, const float*, float*, unsigned char*, double*, const float*, const float*, float*, float*, float*, float*,
+                  int, int, int, float, float, int, int, hipStream_t);
+int rsis_l_bn_bwd(const float*, const float*, const float*, const unsigned char*, const float*, const float*, const float*, double*,
+                  float*, float*, float*, float*, int, int, int, int, float, hipStream_t);
 int rsis_l_maxpool_fwd(const float*, float*, unsigned char*, long, int, int, int, int, hipStream_t);
 int rsis_l_subsample(const float*, float*, long, int, int, int, int, int, hipStream_t);
 int rsis_l_maxpool_bwd(const float*, const unsigned char*, float*, long, int, int, int, int, int, hipStream_t);
@@ -707,15 +707,32 @@ int rsis_bn_fwd(const float* x, const float* res, float* y, double* stats, const
                 float eps, float momentum, int relu, int train, void* stream) {
   if (!x || !y || !gamma || !beta || !running_mean || !running_var) return RSIS_ERR_ARG;
   if ((train & 1) && (!stats || !save_mean || !save_rstd)) return RSIS_ERR_ARG;
-  return rsis_l_bn_fwd(x, res, y, stats, gamma, beta, running_mean, running_var, save_mean, save_rstd, B, C, HW, eps,
+  return rsis_l_bn_fwd(x, res, y, nullptr, stats, gamma, beta, running_mean, running_var, save_mean, save_rstd, B, C, HW, eps,
                        momentum, relu, train, (hipStream_t)stream);
+}
+int rsis_bn_fwd_mask(const float* x, const float* res, float* y, unsigned char* mask, double* stats, const float* gamma, const float* beta,
+                     float* running_mean, float* running_var, float* save_mean, float* save_rstd, int B, int C, int HW,
+                     float eps, float momentum, int train, void* stream) {
+  if (!x || !y || !mask || !gamma || !beta || !running_mean || !running_var) return RSIS_ERR_ARG;
+  if ((train & 1) && (!stats || !save_mean || !save_rstd)) return RSIS_ERR_ARG;
+  if (HW & 3) return RSIS_ERR_UNSUPPORTED;       // nothing launched: the caller keeps y for the backward (rsis_bn_fwd)
+  return rsis_l_bn_fwd(x, res, y, mask, stats, gamma, beta, running_mean, running_var, save_mean, save_rstd, B, C, HW, eps,
+                       momentum, 1, train, (hipStream_t)stream);
 }
 int rsis_bn_bwd(const float* dy, const float* x, const float* y, const float* save_mean, const float* save_rstd,
                 const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C,
                 int HW, int relu, void* stream) {
   if (!dy || !x || !save_mean || !save_rstd || !gamma || !stats || !dx || !dgamma || !dbeta) return RSIS_ERR_ARG;
   if ((relu & 1) && !y) return RSIS_ERR_ARG;
-  return rsis_l_bn_bwd(dy, x, y, save_mean, save_rstd, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, relu, -1.f,
+  return rsis_l_bn_bwd(dy, x, y, nullptr, save_mean, save_rstd, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, relu, -1.f,
+                       (hipStream_t)stream);
+}
+int rsis_bn_bwd_mask(const float* dy, const float* x, const unsigned char* mask, const float* save_mean, const float* save_rstd,
+                     const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C,
+                     int HW, int flags, void* stream) {
+  if (!dy || !x || !mask || !save_mean || !save_rstd || !gamma || !stats || !dx || !dgamma || !dbeta) return RSIS_ERR_ARG;
+  if (HW & 3) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_bn_bwd(dy, x, nullptr, mask, save_mean, save_rstd, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, flags | 1, -1.f,
                        (hipStream_t)stream);
 }
 int rsis_bn_bwd_eval(const float* dy, const float* x, const float* y, const float* running_mean, const float* running_var,
@@ -723,7 +740,17 @@ int rsis_bn_bwd_eval(const float* dy, const float* x, const float* y, const floa
                      float eps, int relu, void* stream) {
   if (!dy || !x || !running_mean || !running_var || !gamma || !stats || !dx || !dgamma || !dbeta || !(eps >= 0.f)) return RSIS_ERR_ARG;
   if ((relu & 1) && !y) return RSIS_ERR_ARG;
-  return rsis_l_bn_bwd(dy, x, y, running_mean, running_var, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, relu, eps, (hipStream_t)stream);
+  return rsis_l_bn_bwd(dy, x, y, nullptr, running_mean, running_var, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, relu, eps,
+                       (hipStream_t)stream);
+}
+int rsis_bn_bwd_eval_mask(const float* dy, const float* x, const unsigned char* mask, const float* running_mean, const float* running_var,
+                          const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW,
+                          float eps, int flags, void* stream) {
+  if (!dy || !x || !mask || !running_mean || !running_var || !gamma || !stats || !dx || !dgamma || !dbeta || !(eps >= 0.f))
+    return RSIS_ERR_ARG;
+  if (HW & 3) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_bn_bwd(dy, x, nullptr, mask, running_mean, running_var, gamma, stats, dx, dres, dgamma, dbeta, B, C, HW, flags | 1, eps,
+                       (hipStream_t)stream);
 }
 // ---- channel-blocked bf16 activations (conv_blk.hip) ----
 int rsis_blk_conv2d(const void* x, int B, int C, int H, int W, const void* Wp, int Cout, int ks, const void* addend, void* out, int variant,

@@ -467,6 +467,18 @@ __device__ __forceinline__ void block_reduce2_atomic(double a, double b, double*
     }                                                                                           \
   }
 
+// ReLU mask of the forward output: one byte per float4 group, mask[idx / 4] with idx the flat NCHW element index of the group
+// (H*W % 4 == 0), bit k = (y[idx + k] > 0) taken from the value stored as y (NaN gives 0, as !(y > 0) does).  The layout depends
+// on the element index alone, so any forward kernel's mask serves any backward kernel.  The backward reads the byte instead of the
+// float4 of y: g = dy * [y > 0] keeps its bits at 1/16 of the bytes.
+__device__ __forceinline__ unsigned char bn_relu_bits(const f32x4 v) {
+  return (unsigned char)((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u));
+}
+__device__ __forceinline__ void bn_mask_grad(f32x4& g, const unsigned bits) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) if (!((bits >> k) & 1u)) g[k] = 0.f;
+}
+
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, double* __restrict__ stats, int C, int HW,
                                                        long N) {
   const int c = blockIdx.x;
@@ -485,8 +497,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
 }
 
 // mode 0: train (batch stats from `stats`, updates running stats, saves mean/rstd); mode 1: eval (running stats)
+// mask (may be null; the launcher passes it only with relu and H*W % 4 == 0): ReLU mask bytes of y, see bn_relu_bits
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                       float* __restrict__ y, const double* __restrict__ stats,
+                                                       float* __restrict__ y, unsigned char* __restrict__ mask,
+                                                       const double* __restrict__ stats,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        float* __restrict__ run_mean, float* __restrict__ run_var,
                                                        float* __restrict__ save_mean, float* __restrict__ save_rstd,
@@ -518,6 +532,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
       if (res) r = *reinterpret_cast<const f32x4*>(res + idx);
       for (int k = 0; k < 4; ++k) v[k] = rsis_bn_apply(v[k], sc, sh, r[k], relu);
       *reinterpret_cast<f32x4*>(y + idx) = v;
+      if (mask) mask[idx >> 2] = bn_relu_bits(v);
     })
   } else {
     BN_FOREACH(1, { y[idx] = rsis_bn_apply(x[idx], sc, sh, res ? res[idx] : 0.f, relu); })
@@ -525,8 +540,12 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 }
 
 // backward pass 1: stats[c] = {sum g, sum g*xhat},  g = dy * (y > 0 if relu)
+// MASK: the forward applied ReLU and left its mask bytes (H*W % 4 == 0): `mask` is read, `y` is not.  The byte load is unconditional
+// and sits with the dy / x loads; the MASK = false instantiation is the kernel as it was.
+template <bool MASK>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                            const float* __restrict__ y, const float* __restrict__ mean,
+                                                            const float* __restrict__ y, const unsigned char* __restrict__ mask,
+                                                            const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, double* __restrict__ stats,
                                                             int C, int HW, long N, int relu, float eval_eps) {
   const int c = blockIdx.x;
@@ -537,7 +556,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
     BN_FOREACH(4, {
       f32x4 g = *reinterpret_cast<const f32x4*>(dy + idx);
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + idx);
-      if (relu) {
+      if constexpr (MASK) {
+        bn_mask_grad(g, mask[idx >> 2]);
+      } else if (relu) {
         const f32x4 yv = *reinterpret_cast<const f32x4*>(y + idx);
         for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[k] = 0.f;
       }
@@ -556,8 +577,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 }
 
 // backward pass 2: dx = gamma*rstd*(g - mean(g) - xhat*mean(g*xhat)); dres = g; dgamma/dbeta from the sums
+template <bool MASK>       // as in bn_bwd_reduce_kernel
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                           const float* __restrict__ y, const float* __restrict__ mean,
+                                                           const float* __restrict__ y, const unsigned char* __restrict__ mask,
+                                                           const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                            const double* __restrict__ stats, float* __restrict__ dx,
                                                            float* __restrict__ dres, float* __restrict__ dgamma,
@@ -577,7 +600,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     BN_FOREACH(4, {
       f32x4 g = *reinterpret_cast<const f32x4*>(dy + idx);
       const f32x4 xv = *reinterpret_cast<const f32x4*>(x + idx);
-      if (relu) {
+      if constexpr (MASK) {
+        bn_mask_grad(g, mask[idx >> 2]);
+      } else if (relu) {
         const f32x4 yv = *reinterpret_cast<const f32x4*>(y + idx);
         for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[k] = 0.f;
       }
@@ -618,7 +643,8 @@ __device__ __forceinline__ void block_allreduce2(double& a, double& b) {
 
 template <int NT, int VPT>
 __global__ __launch_bounds__(NT) void bn_fwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                          float* __restrict__ y, const float* __restrict__ gamma,
+                                                          float* __restrict__ y, unsigned char* __restrict__ mask,
+                                                          const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ run_mean,
                                                           float* __restrict__ run_var, float* __restrict__ save_mean,
                                                           float* __restrict__ save_rstd, int C, int HW, long N, float eps,
@@ -661,13 +687,15 @@ __global__ __launch_bounds__(NT) void bn_fwd_fused_kernel(const float* __restric
 #pragma unroll
       for (int k = 0; k < 4; ++k) { const float t = v[i][k] * sc + sh + r[k]; o[k] = relu ? fmaxf(t, 0.f) : t; }
       *reinterpret_cast<f32x4*>(y + idx) = o;
+      if (mask) mask[idx >> 2] = bn_relu_bits(o);      // (launcher: only with relu)
     }
   }
 }
 
-template <int NT, int VPT>
+template <int NT, int VPT, bool MASK>      // MASK as in bn_bwd_reduce_kernel
 __global__ __launch_bounds__(NT) void bn_bwd_fused_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                          const float* __restrict__ y, const float* __restrict__ mean,
+                                                          const float* __restrict__ y, const unsigned char* __restrict__ mask,
+                                                          const float* __restrict__ mean,
                                                           const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                           float* __restrict__ dx, float* __restrict__ dres,
                                                           float* __restrict__ dgamma, float* __restrict__ dbeta, int C, int HW,
@@ -677,23 +705,49 @@ __global__ __launch_bounds__(NT) void bn_bwd_fused_kernel(const float* __restric
   const float m = mean[c], r = rstd[c];
   f32x4 g[VPT], xh[VPT];
   double s1 = 0.0, s2 = 0.0;
+  if constexpr (MASK) {
+    // every load of the thread first, from a clamped group index and under no condition: with the loads inside `if (gi < ng)` each
+    // of the VPT iterations is its own memory round trip (load, s_waitcnt vmcnt(0), arithmetic), and at 2-5 waves per SIMD nothing
+    // hides eight of them in a row.  Groups past the end read the channel's last group and are not used.
+    unsigned mb[VPT];
 #pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int gi = threadIdx.x + i * NT;
-    if (gi < ng) {
+    for (int i = 0; i < VPT; ++i) {
+      const int gi = min((int)threadIdx.x + i * NT, ng - 1);
       const int b = gi / hwg, sp = (gi - b * hwg) * 4;
       const size_t idx = ((size_t)b * C + c) * HW + sp;
       g[i] = *reinterpret_cast<const f32x4*>(dy + idx);
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + idx);
-      if (relu) {
-        const f32x4 yv = *reinterpret_cast<const f32x4*>(y + idx);
+      xh[i] = *reinterpret_cast<const f32x4*>(x + idx);
+      mb[i] = mask[idx >> 2];
+    }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[i][k] = 0.f;
+    for (int i = 0; i < VPT; ++i) {
+      if ((int)threadIdx.x + i * NT < ng) {
+        bn_mask_grad(g[i], mb[i]);
+        float p1 = 0.f, p2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { xh[i][k] = (xh[i][k] - m) * r; p1 += g[i][k]; p2 += g[i][k] * xh[i][k]; }
+        s1 += p1; s2 += p2;
       }
-      float p1 = 0.f, p2 = 0.f;
+    }
+  } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { xh[i][k] = (xv[k] - m) * r; p1 += g[i][k]; p2 += g[i][k] * xh[i][k]; }
-      s1 += p1; s2 += p2;
+    for (int i = 0; i < VPT; ++i) {
+      const int gi = threadIdx.x + i * NT;
+      if (gi < ng) {
+        const int b = gi / hwg, sp = (gi - b * hwg) * 4;
+        const size_t idx = ((size_t)b * C + c) * HW + sp;
+        g[i] = *reinterpret_cast<const f32x4*>(dy + idx);
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + idx);
+        if (relu) {
+          const f32x4 yv = *reinterpret_cast<const f32x4*>(y + idx);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) if (!(yv[k] > 0.f)) g[i][k] = 0.f;
+        }
+        float p1 = 0.f, p2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { xh[i][k] = (xv[k] - m) * r; p1 += g[i][k]; p2 += g[i][k] * xh[i][k]; }
+        s1 += p1; s2 += p2;
+      }
     }
   }
   block_allreduce2<NT>(s1, s2);
@@ -1118,23 +1172,26 @@ int rsis_l_gmax_bwd(const float* dy, const int* arg, float* dx, long BC, int HW,
   hipLaunchKernelGGL(global_maxpool_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, st, dy, arg, dx, HW, total);
   return rsis_check_launch();
 }
-int rsis_l_bn_fwd(const float* x, const float* res, float* y, double* stats, const float* gamma, const float* beta,
+// mask (fwd: written, bwd: read; may be null): ReLU mask bytes, [B*C*HW / 4], see bn_relu_bits.  Meaningful only with relu and
+// H*W % 4 == 0 (api.hip rejects anything else before it gets here); null = the kernels as they were.
+int rsis_l_bn_fwd(const float* x, const float* res, float* y, unsigned char* mask, double* stats, const float* gamma, const float* beta,
                   float* run_mean, float* run_var, float* save_mean, float* save_rstd, int B, int C, int HW, float eps,
                   float momentum, int relu, int train_flags, hipStream_t st) {
   const long N = (long)B * HW;
   const int S = chan_splits(C, N);
   const int train = train_flags & 1;
+  if (mask && (!relu || (HW & 3))) return RSIS_ERR_UNSUPPORTED;
   if (train && bn_fused_ok(C, HW, N)) {      // channel fits one block: one launch, one read of x
     // few channels = few blocks (one per channel): 512 threads x 4 float4 instead of 256 x 8 puts twice the waves on a CU
     // (measured +0.5 % on the training step; 1024 x 2 is no better)
     if (N / 4 <= 256 * 8 && C <= 512)
-      hipLaunchKernelGGL((bn_fwd_fused_kernel<512, 4>), dim3(C), dim3(512), 0, st, x, res, y, gamma, beta, run_mean, run_var, save_mean,
-                         save_rstd, C, HW, N, eps, momentum, relu);
+      hipLaunchKernelGGL((bn_fwd_fused_kernel<512, 4>), dim3(C), dim3(512), 0, st, x, res, y, mask, gamma, beta, run_mean, run_var,
+                         save_mean, save_rstd, C, HW, N, eps, momentum, relu);
     else if (N / 4 <= 256 * 8)
-      hipLaunchKernelGGL((bn_fwd_fused_kernel<256, 8>), dim3(C), dim3(256), 0, st, x, res, y, gamma, beta, run_mean, run_var, save_mean,
-                         save_rstd, C, HW, N, eps, momentum, relu);
+      hipLaunchKernelGGL((bn_fwd_fused_kernel<256, 8>), dim3(C), dim3(256), 0, st, x, res, y, mask, gamma, beta, run_mean, run_var,
+                         save_mean, save_rstd, C, HW, N, eps, momentum, relu);
     else
-      hipLaunchKernelGGL((bn_fwd_fused_kernel<1024, 8>), dim3(C), dim3(1024), 0, st, x, res, y, gamma, beta, run_mean, run_var,
+      hipLaunchKernelGGL((bn_fwd_fused_kernel<1024, 8>), dim3(C), dim3(1024), 0, st, x, res, y, mask, gamma, beta, run_mean, run_var,
                          save_mean, save_rstd, C, HW, N, eps, momentum, relu);
     return rsis_check_launch();
   }
@@ -1142,32 +1199,49 @@ int rsis_l_bn_fwd(const float* x, const float* res, float* y, double* stats, con
     if (!(train_flags & 2) && rsis_zero_async(stats, sizeof(double) * 2 * C, st) != RSIS_OK) return RSIS_ERR_LAUNCH;
     hipLaunchKernelGGL(bn_stats_kernel, dim3(C, S), dim3(256), 0, st, x, stats, C, HW, N);
   }
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(C, S), dim3(256), 0, st, x, res, y, stats, gamma, beta, run_mean, run_var, save_mean,
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(C, S), dim3(256), 0, st, x, res, y, mask, stats, gamma, beta, run_mean, run_var, save_mean,
                      save_rstd, C, HW, N, eps, momentum, relu, train ? 0 : 1);
   return rsis_check_launch();
 }
-int rsis_l_bn_bwd(const float* dy, const float* x, const float* y, const float* mean, const float* rstd, const float* gamma,
-                  double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW, int relu_flags,
-                  float eval_eps, hipStream_t st) {
+template <int NT, int VPT>
+static void bn_bwd_fused_launch(const float* dy, const float* x, const float* y, const unsigned char* mask, const float* mean,
+                                const float* rstd, const float* gamma, float* dx, float* dres, float* dgamma, float* dbeta, int C,
+                                int HW, long N, int relu, int accum, hipStream_t st) {
+  if (mask)
+    hipLaunchKernelGGL((bn_bwd_fused_kernel<NT, VPT, true>), dim3(C), dim3(NT), 0, st, dy, x, y, mask, mean, rstd, gamma, dx, dres,
+                       dgamma, dbeta, C, HW, N, relu, accum);
+  else
+    hipLaunchKernelGGL((bn_bwd_fused_kernel<NT, VPT, false>), dim3(C), dim3(NT), 0, st, dy, x, y, mask, mean, rstd, gamma, dx, dres,
+                       dgamma, dbeta, C, HW, N, relu, accum);
+}
+int rsis_l_bn_bwd(const float* dy, const float* x, const float* y, const unsigned char* mask, const float* mean, const float* rstd,
+                  const float* gamma, double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW,
+                  int relu_flags, float eval_eps, hipStream_t st) {
   const long N = (long)B * HW;
   const int S = chan_splits(C, N);
   const int relu = relu_flags & 1, accum = (relu_flags >> 2) & 1;
+  if (mask && (!relu || (HW & 3))) return RSIS_ERR_UNSUPPORTED;
   if (eval_eps < 0.f && bn_fused_ok(C, HW, N)) {
     if (N / 4 <= 256 * 8 && C <= 512)          // (as in the forward)
-      hipLaunchKernelGGL((bn_bwd_fused_kernel<512, 4>), dim3(C), dim3(512), 0, st, dy, x, y, mean, rstd, gamma, dx, dres, dgamma, dbeta,
-                         C, HW, N, relu, accum);
+      bn_bwd_fused_launch<512, 4>(dy, x, y, mask, mean, rstd, gamma, dx, dres, dgamma, dbeta, C, HW, N, relu, accum, st);
     else if (N / 4 <= 256 * 8)
-      hipLaunchKernelGGL((bn_bwd_fused_kernel<256, 8>), dim3(C), dim3(256), 0, st, dy, x, y, mean, rstd, gamma, dx, dres, dgamma, dbeta,
-                         C, HW, N, relu, accum);
+      bn_bwd_fused_launch<256, 8>(dy, x, y, mask, mean, rstd, gamma, dx, dres, dgamma, dbeta, C, HW, N, relu, accum, st);
     else
-      hipLaunchKernelGGL((bn_bwd_fused_kernel<1024, 8>), dim3(C), dim3(1024), 0, st, dy, x, y, mean, rstd, gamma, dx, dres, dgamma,
-                         dbeta, C, HW, N, relu, accum);
+      bn_bwd_fused_launch<1024, 8>(dy, x, y, mask, mean, rstd, gamma, dx, dres, dgamma, dbeta, C, HW, N, relu, accum, st);
     return rsis_check_launch();
   }
   if (!(relu_flags & 2) && rsis_zero_async(stats, sizeof(double) * 2 * C, st) != RSIS_OK) return RSIS_ERR_LAUNCH;
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, S), dim3(256), 0, st, dy, x, y, mean, rstd, stats, C, HW, N, relu, eval_eps);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(C, S), dim3(256), 0, st, dy, x, y, mean, rstd, gamma, stats, dx, dres, dgamma,
-                     dbeta, C, HW, N, relu, accum, eval_eps);
+  if (mask) {
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(C, S), dim3(256), 0, st, dy, x, y, mask, mean, rstd, stats, C, HW, N, relu,
+                       eval_eps);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(C, S), dim3(256), 0, st, dy, x, y, mask, mean, rstd, gamma, stats, dx, dres,
+                       dgamma, dbeta, C, HW, N, relu, accum, eval_eps);
+  } else {
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(C, S), dim3(256), 0, st, dy, x, y, mask, mean, rstd, stats, C, HW, N, relu,
+                       eval_eps);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(C, S), dim3(256), 0, st, dy, x, y, mask, mean, rstd, gamma, stats, dx, dres,
+                       dgamma, dbeta, C, HW, N, relu, accum, eval_eps);
+  }
   return rsis_check_launch();
 }
 int rsis_l_gmax_bwd_add(const float* dy, const int* arg, float* dx, long BC, int HW, hipStream_t st) {

@@ -660,7 +660,7 @@ def global_maxpool(x):
 
 class _BatchNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, running_mean, running_var, train, relu, eps, momentum, arena, res_slot=None):
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, train, relu, eps, momentum, arena, res_slot=None, want_grad=True):
         x = _contig(x)
         ctx.res_slot = res_slot
         res = _contig(res) if res is not None else None
@@ -677,20 +677,32 @@ class _BatchNormFn(torch.autograd.Function):
             rstd = torch.empty_like(mean)
         else:
             stats = mean = rstd = None
-        check(lib().rsis_bn_fwd(ptr(x), ptr(res), ptr(y), ptr(stats), ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean),
-                                ptr(running_var), ptr(mean), ptr(rstd), B, C, H * W, float(eps), float(momentum), int(relu),
-                                flags, stream()), "rsis_bn_fwd")
+        # with ReLU on float4-able planes the forward leaves the ReLU mask as bytes (one per 4 elements) and the backward reads
+        # those instead of y: 1/16 of the bytes for the same bits (rsis_bn_*_mask); otherwise y is kept.  No mask is written when
+        # nothing will be back-propagated (want_grad, decided in batchnorm(): grad mode is off in here and ctx.needs_input_grad is
+        # True for parameters even under no_grad).
+        ctx.masked = bool(relu) and (H * W) % 4 == 0 and want_grad
+        if ctx.masked:
+            keep = torch.empty(x.numel() // 4, dtype=torch.uint8, device=x.device)
+            check(lib().rsis_bn_fwd_mask(ptr(x), ptr(res), ptr(y), ptr(keep), ptr(stats), ptr(gamma.detach()), ptr(beta.detach()),
+                                         ptr(running_mean), ptr(running_var), ptr(mean), ptr(rstd), B, C, H * W, float(eps),
+                                         float(momentum), flags, stream()), "rsis_bn_fwd_mask")
+        else:
+            keep = y if relu else None
+            check(lib().rsis_bn_fwd(ptr(x), ptr(res), ptr(y), ptr(stats), ptr(gamma.detach()), ptr(beta.detach()), ptr(running_mean),
+                                    ptr(running_var), ptr(mean), ptr(rstd), B, C, H * W, float(eps), float(momentum), int(relu),
+                                    flags, stream()), "rsis_bn_fwd")
         ctx.train, ctx.relu, ctx.has_res, ctx.eps = train, relu, res is not None, eps
         ctx.arena, ctx.gparam, ctx.bparam = arena, gamma, beta
         if train:
-            ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
+            ctx.save_for_backward(x, keep, gamma, mean, rstd)
         else:
-            ctx.save_for_backward(x, y if relu else None, gamma, running_mean, running_var)
+            ctx.save_for_backward(x, keep, gamma, running_mean, running_var)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, gamma, mean, rstd = ctx.saved_tensors
+        x, y, gamma, mean, rstd = ctx.saved_tensors      # y: the forward output, or its ReLU mask bytes (ctx.masked)
         dy = _contig(dy)
         B, C, H, W = x.shape
         if not ctx.train:
@@ -702,11 +714,12 @@ class _BatchNormFn(torch.autograd.Function):
             dres = torch.empty_like(x) if need_dres else None
             dgamma = torch.empty(C, dtype=torch.float32, device=dy.device)
             dbeta = torch.empty_like(dgamma)
-            check(lib().rsis_bn_bwd_eval(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma.detach()), ptr(stats), ptr(dx), ptr(dres),
-                                         ptr(dgamma), ptr(dbeta), B, C, H * W, float(ctx.eps), int(ctx.relu), stream()), "rsis_bn_bwd_eval")
+            fn, name = (lib().rsis_bn_bwd_eval_mask, "rsis_bn_bwd_eval_mask") if ctx.masked else (lib().rsis_bn_bwd_eval, "rsis_bn_bwd_eval")
+            check(fn(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma.detach()), ptr(stats), ptr(dx), ptr(dres),
+                     ptr(dgamma), ptr(dbeta), B, C, H * W, float(ctx.eps), int(ctx.relu), stream()), name)
             if ctx.has_res and not need_dres:
                 dres = dy
-            return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
+            return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None, None
         flags = int(ctx.relu)
         if ctx.arena is not None:
             stats, flags = ctx.arena[1], flags | 2
@@ -722,23 +735,25 @@ class _BatchNormFn(torch.autograd.Function):
         else:
             dgamma = torch.empty(C, dtype=torch.float32, device=dy.device)
             dbeta = torch.empty_like(dgamma)
-        check(lib().rsis_bn_bwd(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma.detach()), ptr(stats), ptr(dx), ptr(dres),
-                                ptr(dgamma), ptr(dbeta), B, C, H * W, flags, stream()), "rsis_bn_bwd")
+        fn, name = (lib().rsis_bn_bwd_mask, "rsis_bn_bwd_mask") if ctx.masked else (lib().rsis_bn_bwd, "rsis_bn_bwd")
+        check(fn(ptr(dy), ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma.detach()), ptr(stats), ptr(dx), ptr(dres),
+                 ptr(dgamma), ptr(dbeta), B, C, H * W, flags, stream()), name)
         if ctx.has_res and not need_dres:
             dres = dy
         if direct:
             dgamma = dbeta = None
         if ctx.res_slot is not None and ctx.res_slot.park(dres):
             dres = None                                # picked up by the data-gradient kernel of the block's first conv
-        return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def batchnorm(x, gamma, beta, running_mean, running_var, train, relu=False, res=None, eps=1e-5, momentum=0.1, arena=None,
               res_slot=None):
     """nn.BatchNorm2d (+ residual add) (+ ReLU): y = act(bn(x) + res).  arena: optional (fwd, bwd) float64 [2*C] scratch
     slices that the caller zeroed for this iteration (saves one memset per layer per pass)."""
+    want_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, res, gamma, beta))
     return _BatchNormFn.apply(x, res, gamma, beta, running_mean, running_var, bool(train), bool(relu), eps, momentum, arena,
-                              res_slot if (train and res is not None) else None)
+                              res_slot if (train and res is not None) else None, want_grad)
 
 
 class _MaxPool3x3s2Fn(torch.autograd.Function):
