@@ -356,6 +356,19 @@ long rsis_targets_work_ints(int B);
 int rsis_targets_from_maps(const int* ins, const int* seg, int B, int H, int W, int T, float* y_mask, long long* y_class, float* sw_mask,
                            float* sw_class, int* work, void* stream);
 
+/* ---- Cityscapes label maps of a whole batch from the raw `*_instanceIds` values (dataloader/cityscapes.py:67-92):
+ * raw: [B][H][W] int32; a value outside 0..65535 counts as 0.  class_of_label: [n_labels] int32 in DEVICE memory, n_labels <= 66.
+ * Per pixel label = raw / 1000 and cls = class_of_label[label] if raw >= 1000 and label < n_labels, else 0; a pixel is KEPT when
+ * cls > 0.  seg[B][H][W] = cls; ins[B][H][W] = 1 + the number of distinct kept raw values of image b that are smaller than this
+ * pixel's, 0 on a pixel that is not kept -- the ranks np.unique gives, up to 65536 of them (a rank above 255 is written as it is:
+ * rsis_targets_from_maps is the one that refuses it).  EVERY element of ins and seg is written.  work: caller-owned scratch of
+ * rsis_instance_maps_work_ints(B) int32 (a 65536-bit presence bitmap per image), zeroed by the call itself.  No host sync, no
+ * allocation, capture-safe; bitwise / integer atomics only, so the result does not depend on the order of execution.
+ * H*W < 2^31, B <= 65535. ---- */
+long rsis_instance_maps_work_ints(int B);
+int rsis_instance_maps(const int* raw, const int* class_of_label, int n_labels, int B, int H, int W, int* ins, int* seg, int* work,
+                       void* stream);
+
 /* ---- Pascal VOC preparation (dataloader/pascal_precompute.py:36-101; dataset_utils.py convert_from_color_segmentation) ----
  * rsis_palette_to_ids: rgb[npix][3] uint8 -> ids[npix] uint8 through a colour table table[ntab][4] = (r, g, b, id) in DEVICE memory,
  *   ntab <= 256; the first matching entry wins, a colour that is not in the table maps to 0.

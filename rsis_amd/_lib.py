@@ -96,6 +96,8 @@ SIGNATURES = {
     "rsis_affine_nearest": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "rsis_targets_work_ints": (_l, [_i]),
     "rsis_targets_from_maps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsis_instance_maps_work_ints": (_l, [_i]),
+    "rsis_instance_maps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rsis_palette_to_ids": (_i, [_vp, _l, _vp, _i, _vp, _vp]),
     "rsis_idmap_rle_encode": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "rsis_conv_out_wgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

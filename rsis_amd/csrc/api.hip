@@ -70,6 +70,8 @@ int rsis_l_pack_blocks(int mode, int krows, int ldw, int ks);
 int rsis_l_affine_nearest(const float*, float*, const float*, int, int, int, int, int, hipStream_t);
 long rsis_l_targets_work_ints(int);
 int rsis_l_targets_from_maps(const int*, const int*, int, int, int, int, float*, long long*, float*, float*, int*, hipStream_t);
+long rsis_l_instance_maps_work_ints(int);
+int rsis_l_instance_maps(const int*, const int*, int, int, int, int, int*, int*, int*, hipStream_t);
 int rsis_l_palette_to_ids(const unsigned char*, long, const unsigned char*, int, unsigned char*, hipStream_t);
 int rsis_l_idmap_rle_encode(const unsigned char*, int, int, const int*, int, unsigned int*, int, int*, hipStream_t);
 int rsis_l_mask_resize_threshold(const float*, int, int, int, const unsigned char*, float, unsigned char*, unsigned char*, unsigned int*,
@@ -306,6 +308,17 @@ int rsis_targets_from_maps(const int* ins, const int* seg, int B, int H, int W, 
   if (!ins || !seg || !y_mask || !y_class || !sw_mask || !sw_class || !work || B < 1 || H < 1 || W < 1 || T < 1) return RSIS_ERR_ARG;
   if ((long)H * W >= (1L << 31) || B > 65535) return RSIS_ERR_UNSUPPORTED;
   return rsis_l_targets_from_maps(ins, seg, B, H, W, T, y_mask, y_class, sw_mask, sw_class, work, (hipStream_t)stream);
+}
+
+long rsis_instance_maps_work_ints(int B) { return B < 1 ? 0 : rsis_l_instance_maps_work_ints(B); }
+
+int rsis_instance_maps(const int* raw, const int* class_of_label, int n_labels, int B, int H, int W, int* ins, int* seg, int* work,
+                       void* stream) {
+  if (!raw || !class_of_label || !ins || !seg || !work || raw == ins || raw == seg || ins == seg || n_labels < 1 || n_labels > 66 ||
+      B < 1 || H < 1 || W < 1)
+    return RSIS_ERR_ARG;
+  if ((long)H * W >= (1L << 31) || B > 65535) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_instance_maps(raw, class_of_label, n_labels, B, H, W, ins, seg, work, (hipStream_t)stream);
 }
 
 int rsis_palette_to_ids(const unsigned char* rgb, long npix, const unsigned char* table, int ntab, unsigned char* ids, void* stream) {

@@ -144,7 +144,8 @@ class DeviceLoader(object):
     (x, y_mask, y_class, sw_mask, sw_class) -- what utils.batch_to_var returns.  The next batch is decoded into pinned memory by
     `num_workers` threads and copied on a side stream while the current one trains.
     A dataset whose `host_item` returns (image, ins) has its class map derived as `ins > 0` (leaves); one that returns (image, ins, seg)
-    (dataloader/pascal.py) has `seg` staged, copied and warped next to `ins`.
+    (dataloader/pascal.py) has `seg` staged, copied and warped next to `ins`; one with a `maps_from_ids` (dataloader/cityscapes.py) returns
+    (image, raw ids) and has both maps derived from the warped ids on the device.
 
     One process per GPU (rank / world): `batch_size` is the PER-RANK batch; every rank shuffles the whole dataset with the SAME
     seed and takes samples r, r + world, ... of each global batch of batch_size * world, so that an epoch is
@@ -153,7 +154,7 @@ class DeviceLoader(object):
 
     def __init__(self, dataset, batch_size, shuffle=True, num_workers=4, seed=0, device="cuda", rank=0, world=1, drop_last=True):
         self.drop_last = bool(drop_last)
-        if dataset.crop is False and batch_size != 1:
+        if dataset.crop is False and batch_size != 1 and not getattr(dataset, "same_size", False):   # (same_size: dataloader/cityscapes.py)
             raise ValueError("un-cropped samples have different sizes: batch_size must be 1")
         self.ds, self.bs, self.shuffle, self.device = dataset, int(batch_size), shuffle, device
         self.rank, self.world = int(rank), int(world)
@@ -240,7 +241,9 @@ class DeviceLoader(object):
                 x = affine_nearest(x, mats)
                 mf = affine_nearest(mf, mats)
             ins_d = mf.squeeze(1).round().long()
-            if sg is None:
+            if hasattr(self.ds, "maps_from_ids"):                               # raw ids (dataloader/cityscapes.py): both maps on the device
+                ins_d, seg_d = self.ds.maps_from_ids(ins_d)
+            elif sg is None:
                 seg_d = (ins_d > 0).long()                                      # leaves.py:105-106
             else:
                 sf = sg.float().unsqueeze(1)

@@ -5,9 +5,14 @@ and the mask PNGs (largest connected component of the thresholded mask, resized 
 
     python -m rsis_amd.eval_cityscapes --synthetic -model_name <name> -num_classes 9 -imsize 512 -maxseqlen 20 -batch_size 8 [-dtype bf16]
 
-The Cityscapes READER of the reference (src/dataloader/cityscapes.py: host-side PNG / json I/O) is out of scope,
-so only `--synthetic` inputs are wired: square images of `-imsize` whose "original" size is taken as twice that, which exercises
-the same resize path.  Everything after `test()` is the reference's procedure, through
+    python -m rsis_amd.eval_cityscapes -cityscapes_dir D -eval_split val -model_name <name> -num_classes 9 -imsize 256 -maxseqlen 20
+
+Without `--synthetic` the images of `-eval_split` come from dataloader/cityscapes.py in sorted file order (shuffle=False,
+drop_last=False, no augmentation), a sample is named after its file (`<city>_<seq>_<frame>_leftImg8bit`, eval_cityscapes.py:114-120),
+the masks are resized to the size in the PNG header, and the ground truth scored against is the raw array of each image's
+`*_gtFine_instanceIds.png`: nothing is written into the dataset directory and no `_gt` copy is made.
+With `--synthetic`: square images of `-imsize` whose "original" size is taken as twice that, which exercises the same resize path.
+Everything after `test()` is the reference's procedure, through
 `rsis_amd.eval_post.write_cityscapes_results`.  Deviations from the reference script: an empty mask is written as an
 all-zero PNG (the reference reuses a stale `max_label` from the previous mask); scores are formatted from float64 (the reference
 prints numpy float32 `str`), i.e. more digits of the same number.
@@ -56,14 +61,62 @@ def synthetic_instance_ids(y_mask, y_class, height, width, scale=2):
 class Evaluate(object):
     def __init__(self, args):
         self.args, self.split, self.T = args, args.eval_split, args.maxseqlen
+        self.dataset = None
         if not getattr(args, "synthetic", False):
-            raise Exception("only --synthetic inputs are wired in this build (the Cityscapes reader of the reference's src/dataloader is "
-                            "host-side I/O outside the hot path: SURVEY.md section 8)")
+            self._init_files()
+            return
         self.encoder, self.decoder = load_models(args)
         self.loader = SyntheticLoader(args, max(1, args.synthetic_batches // 4), args.seed + 7)
         self.sample_list = ["synthetic_%06d" % i for i in range(len(self.loader) * args.batch_size)]
 
+    def _init_files(self):
+        """eval_cityscapes.py:38-51: the images of -eval_split through the reader, in file order"""
+        from .dataloader.cityscapes import CityScapes
+        from .dataloader.leaves import DeviceLoader
+        args = self.args
+        self.dataset = CityScapes(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        self.sample_list = [os.path.basename(f).split(".")[0] for f in self.dataset.get_sample_list()]   # :114-120
+        self.encoder, self.decoder = load_models(args)
+        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
+                                   drop_last=False)
+
+    def _create_figures_files(self):
+        """create_figures on the files of the dataset: original sizes from the PNG headers, ground truth = the raw instanceIds arrays"""
+        from . import cityscapes_eval
+        args = self.args
+        results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results")     # eval_cityscapes.py:99-104
+        masks_dir = args.model_name + "_masks"
+        os.makedirs(os.path.join(results_dir, masks_dir), exist_ok=True)
+        self.results_dir, self.gt_dir = results_dir, None
+        do_score = not getattr(args, "no_run_coco_eval", False)
+        self.records = []
+        print("Creating annotations for cityscapes validation...")
+        acc, n_lines = 0, 0
+        for x, _y_mask, _y_class, _sw_mask, _sw_class in self.loader:
+            out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)               # :108
+            Hm, Wm = x.size(-2), x.size(-1)
+            gts, mask_sets, rows, labels, scores = [], [], [], [], []
+            for s in range(out_masks.shape[0]):
+                sample, masks = self.sample_list[s + acc], []
+                h, w = self.dataset.raw_size(s + acc)                                                    # :115-118
+                lines = write_cityscapes_results(args, sample, out_masks[s].view(self.T, Hm, Wm), out_scores[s],
+                                                 stop_probs[s], h, w, results_dir, masks_dir, collect=masks)
+                n_lines += len(lines)
+                if do_score:
+                    gts.append(cityscapes_eval.read_gt_png(self.dataset.ins_files[s + acc]))
+                    mask_sets.append(masks)
+                    rows.append([q // (len(lines) // len(masks)) for q in range(len(lines))])
+                    labels.append([int(l.split()[1]) for l in lines])
+                    scores.append([float(l.split()[2]) for l in lines])
+            if do_score:
+                self.records += cityscapes_eval.score_image_sets(gts, mask_sets, rows, labels, scores)
+            acc += out_masks.shape[0]
+        print("%d result lines for %d images -> %s" % (n_lines, acc, results_dir))
+        return n_lines
+
     def create_figures(self):
+        if self.dataset is not None:
+            return self._create_figures_files()
         args = self.args
         results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results")     # eval_cityscapes.py:99-104
         masks_dir = args.model_name + "_masks"

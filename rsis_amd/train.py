@@ -635,12 +635,12 @@ def init_dataloaders(args, rank=0, world=1):
     GPUs, train.py:269-274): every rank of a torchrun job takes B / world samples, so reference hyper-parameters carry over.
     (The loss is the mean of the per-rank masked means -- equal to the global masked mean for equal shard sizes.)"""
     if not getattr(args, "synthetic", False):
-        if args.dataset not in ("leaves", "pascal"):
-            raise Exception("data: --synthetic, -dataset leaves (CVPPP A1, BASELINE configs[0]) or -dataset pascal; the Cityscapes reader "
-                            "of the reference's src/dataloader is host-side I/O outside the hot path (SURVEY.md section 8(f) row N3)")
+        if args.dataset not in ("leaves", "pascal", "cityscapes"):
+            raise Exception("data: --synthetic, -dataset leaves (CVPPP A1, BASELINE configs[0]), -dataset pascal or -dataset cityscapes")
+        from .dataloader.cityscapes import CityScapes
         from .dataloader.leaves import DeviceLoader, LeavesDataset
         from .dataloader.pascal import PascalVOC
-        Dataset = LeavesDataset if args.dataset == "leaves" else PascalVOC
+        Dataset = {"leaves": LeavesDataset, "pascal": PascalVOC, "cityscapes": CityScapes}[args.dataset]
         if args.batch_size % world != 0:
             raise Exception("-batch_size %d (the global batch) is not divisible by the %d ranks" % (args.batch_size, world))
         loaders = {}
