@@ -34,6 +34,7 @@
 // own and a group is the split plan (tiled_split_plan), nothing else.
 #include "common.h"
 #include "limb_split.h"
+#include "wgrad_block_order.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -375,11 +376,15 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
 // them together: every launch costs ~15 us of ramp, prologue and drain whatever its size, and alone a layer has to split its
 // pixel axis 8-32 ways to fill the chip -- each split a dW-sized pass of fp32 atomics -- while forty layers together fill it with
 // one or two.  The jobs travel by value in the kernel arguments (no device-side table, nothing to keep alive under graph replay);
-// block b belongs to the job whose [begin, end) range holds it and plays block (x, y) = (b' % tiles, b' / tiles) of that job -- for
-// one job the order of a (tiles, splits) grid. ----
+// logical block b belongs to the job whose [begin, end) range holds it and plays block (x, y) = (b' % tiles, b' / tiles) of that job
+// -- for one job the order of a (tiles, splits) grid.  The hardware block index is first permuted (wgrad_block_order.h) so that the
+// blocks one XCD runs are a contiguous range of logical blocks: consecutive dW tiles of a split share an x slab (the co tiles of one
+// n tile) or a dy slab, and dealt round-robin they re-read it through eight different L2s.  The set of blocks, the split plan and the
+// work per block do not change; with one contributor per dW tile (deterministic mode) neither do the bits. ----
 #define RSIS_WG_MAXJ 48
 struct WgradTiledGroup {
   int n;
+  int xcd_order;          // 1: XCD-contiguous block order (grouped launches, wg_xcd_order); 0: the identity
   int begin[RSIS_WG_MAXJ + 1];
   WgradTiledArgs job[RSIS_WG_MAXJ];
 };
@@ -387,7 +392,7 @@ static_assert(sizeof(WgradTiledGroup) <= 4000, "kernel arguments are limited to 
 
 template <int BM, int BN, int WGM, int WGN, int KS, int TW, int KSP = 1, int RAG = 0, int LIMB = 0>
 __global__ __launch_bounds__(256) void conv_wgrad_tiled_group_kernel(const WgradTiledGroup g) {
-  const int b = blockIdx.x;
+  const int b = g.xcd_order ? rsis_xcd_logical_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
   int lo = 0, hi = g.n - 1;
   while (lo < hi) {                       // last job whose begin <= b (uniform: scalar code)
     const int mid = (lo + hi + 1) >> 1;
@@ -403,12 +408,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_tiled_group_kernel(const Wgrad
 // One bit per tile configuration code of tiled_cfg_code (0 = 32x64 KSP 2, 1 = 32x128, 2 = 64x64, 3 = 64x128, 4 = 128x64, 5 = 128x128),
 // per kernel size and tile width.  A bit is set where the grouped launch of that bucket in the 256 x 256 training step measured
 // faster than the f32 loop by more than the run-to-run spread (profiles/r07_a_wgrad_limbs_per_config.txt, NOTES (73)): every 3x3
-// bucket (0.66-0.93 of the f32 loop's time) and the 64x64 1x1 tile on 16- and 8-wide tiles (0.86 / 0.88); the 1x1 on 32-wide tiles
-// (the 64- and 32-pixel maps) measured 1.20 and stays on the f32 loop.  Buckets the step does not have, the ragged (RAG) ones
-// among them, are unmeasured and stay off.
+// bucket (0.66-0.93 of the f32 loop's time) and the 64x64 1x1 tile on 16- and 8-wide tiles (0.86 / 0.88); the 64x64 1x1 on 32-wide
+// tiles (the 64- and 32-pixel maps) measured 1.20 and stays on the f32 loop.  The 128x128 1x1 tile of the grouped launches
+// (wg_group_tile) measured 0.70-0.75 on all three tile widths (profiles/r09_a_wgrad_tiles_per_bucket.txt, NOTES (80)).  Buckets the
+// step does not have, the ragged (RAG) ones among them, are unmeasured and stay off.
 static unsigned wg_limb_mask(int ks, int tw) {
   if (ks == 3) return tw == 16 ? 0x3Fu : (tw == 8 ? 1u << 5 : 0u);
-  return tw == 16 || tw == 8 ? 1u << 2 : 0u;
+  return (tw == 16 || tw == 8 ? 1u << 2 : 0u) | 1u << 5;
 }
 // RSIS_WGRAD_LIMBS, read once: unset = the table; 0 = every job on the f32 loop (A/B, bisecting); all = every job on the limb loop
 // (the per-configuration measurement and tests/test_gpu_wgrad_limbs.py)
@@ -422,6 +428,33 @@ static bool wg_use_limbs(int ks, int tw, int code, int rag) {
   if (mode) return mode == 2;
   return rag == 0 && ((wg_limb_mask(ks, tw) >> code) & 1u);
 }
+
+// ---- which buckets of a GROUPED launch run in the XCD-contiguous block order (wgrad_block_order.h) ----
+// One bit per tile configuration code, per kernel size and tile width, like wg_limb_mask and from the same kind of measurement
+// (profiles/r09_a_wgrad_tiles_per_bucket.txt, NOTES (80)).  A bit is set where every run in XCD order was faster than every run in
+// hardware order: the 3x3 buckets 64 x 64 (0.88 of the hardware order's time) and 32 x 64 KSP 2 (0.93) on 16-wide tiles, the two 3x3
+// buckets with 32 x 32 wave tiles and the highest fabric rates, and the 128 x 128 1x1 on 32-wide tiles (0.34-0.35 ms against 0.37-0.45).
+// 128 x 64, 32 x 128 and 64 x 128 3x3 and the 128 x 128 1x1 on 16- / 8-wide tiles measured 0.95-0.99 with overlapping runs; the
+// 128 x 128 3x3 did not move on 16-wide tiles and measured 1.14 on 8-wide ones; the 64 x 64 1x1 did not move.  Those, buckets the step
+// does not have, and every launch of a single weight gradient (never measured) stay in hardware order.
+static unsigned wg_xcd_mask(int ks, int tw) {
+  if (ks == 3) return tw == 16 ? 0x5u : 0u;
+  return tw == 32 ? 1u << 5 : 0u;
+}
+// RSIS_WGRAD_XCD, read once: unset = the table; 0 = every grouped launch in hardware order (A/B runs); all = every grouped launch
+// in the XCD-contiguous order (tests/test_gpu_wgrad_tiles.py, the per-bucket measurement)
+static int wg_xcd_order(int ks, int tw, int code, int rag) {
+  static const int mode = [] {
+    const char* e = getenv("RSIS_WGRAD_XCD");
+    if (!e || !e[0]) return 0;
+    if (e[0] == '0') return 1;
+    return strcmp(e, "all") == 0 ? 2 : 0;
+  }();
+  if (mode) return mode == 2;
+  return rag == 0 && ((wg_xcd_mask(ks, tw) >> code) & 1u);
+}
+// tile configuration code of a BM x BN block tile (the inverse of launch_group_code's switch)
+static constexpr int tiled_code_of(int bm, int bn) { return bm == 32 ? (bn == 64 ? 0 : 1) : (bm == 64 ? (bn == 64 ? 2 : 3) : (bn == 64 ? 4 : 5)); }
 
 // widest tile the map allows: full 128-byte lines of dy / x per tile row on the wide maps, whole rows on the narrow ones
 static int tiled_tw(int H, int W, int ks) {
@@ -446,13 +479,55 @@ static int tiled_tw_ragged(int W, int ks) {
 // 1x1: 64 x 64 tiles with two blocks per CU.  The split count -- and with it the dW-sized passes of fp32 atomics, which run at
 // ~0.3 T atomics/s and were a third of these launches -- goes with slots / tiles: a quarter of the 128 x 128 tile's at twice
 // its slots.  Measured on every 1x1 shape of the trunk at batch 32 (tools/exp/bf16_shape_sweep.py --dtype fp32): 47-54 -> 38-44 us.
-static int tiled_cfg_code(const WgradTiledArgs& a, int ks) {
+static int tiled_cfg_code_single(const WgradTiledArgs& a, int ks) {
   const int nmod = (a.Cs * ks * ks) % 128;
   const bool narrow = nmod != 0 && nmod <= 64;
   if (ks == 1 && a.Cout > 32) return 2;
   if (a.Cout <= 32) return narrow && !rsis_deterministic() ? 0 : 1;
   if (a.Cout <= 64) return narrow ? 2 : 3;
   return narrow ? 4 : 5;
+}
+
+// ---- tile of a job inside a GROUPED launch on an aligned map ----
+// The rule above was measured on single launches of the f32 loop, where a layer splits 8-32 ways and the atomics of the splits decide;
+// in a group a layer splits 2-3 ways, and on the limb loop the 32 x 32 wave tiles (TM * TN = 1) of the small configurations pay twice
+// the operand split per MFMA and re-read dy / x twice as often as the 128-wide ones.  The jobs for which a wider tile is a candidate
+// fall into classes; which class takes it is a measured table (wg_group_tile), class by class like wg_limb_mask:
+//   1x1, Cout > 32: class 1 = Cout >= 128 and Cs >= 128 (the bottleneck pairs of layers 2-4), class 0 = the rest; candidate 128 x 128
+//   3x3 "narrow" N: class 0 / 1 / 2 = Cout <= 32 / <= 64 / above; candidate the 128-wide tile of the same BM (codes 1 / 3 / 5)
+static int wg_job_class(const WgradTiledArgs& a, int ks) {
+  if (ks == 1) return a.Cout <= 32 ? -1 : (a.Cout >= 128 && a.Cs >= 128 ? 1 : 0);
+  const int nmod = (a.Cs * ks * ks) % 128;
+  if (nmod == 0 || nmod > 64) return -1;
+  return a.Cout <= 32 ? 0 : (a.Cout <= 64 ? 1 : 2);
+}
+static int wg_wide_code(int ks, int cls) { return ks == 1 ? 5 : 2 * cls + 1; }
+// the table: tile configuration code of class `cls` on tw-wide spatial tiles, or -1 = the rule of the single launch.  An entry is
+// set where the grouped launches of the 256 x 256 training step measured faster with it by more than the run-to-run spread
+// (profiles/r09_a_wgrad_tiles_per_bucket.txt, NOTES (80)); classes the step does not have are unmeasured and stay on -1.
+// Measured: the 1x1 bottleneck pairs on the 128 x 128 tile AND the limb loop 0.78 / 0.65 of the 64 x 64 tile's time on 16- / 32-wide
+// tiles; on 8-wide tiles 0.92 in XCD order but 0.94-1.00 in hardware order, inside the spread: not taken.  On the f32 loop the same
+// tile is 1.10 / 0.91 / 1.24 (16- / 32- / 8-wide): the gain is the halved operand split per MFMA, and wg_limb_mask carries the bit.
+// 64 x 128 and 128 x 64 measured 0.85-0.87 on 16-wide tiles, behind it.  The other 1x1 jobs of the 32-wide bucket (Cout or Cs of 64)
+// lose on it (1.76).  3x3: the Cout <= 64 class on 64 x 128 measured 0.96 in one step and 1.03 in another (not robust); the Cout <= 32
+// class loses on 32 x 128 (1.05) and the Cout > 64 class on 128 x 128 (1.00 in hardware order, 1.16 in XCD order): all three stay.
+static int wg_group_tile(int ks, int tw, int cls) {
+  return ks == 1 && cls == 1 && (tw == 32 || tw == 16) ? 5 : -1;
+}
+// RSIS_WGRAD_TILES, read once: unset = the table; 0 = the single launch's rule everywhere; wide = every class on its candidate
+// (tests/test_gpu_wgrad_tiles.py)
+static int tiled_cfg_code(const WgradTiledArgs& a, int ks, int tw, bool grouped) {
+  static const int mode = [] {
+    const char* e = getenv("RSIS_WGRAD_TILES");
+    if (!e || !e[0]) return 0;
+    if (strcmp(e, "0") == 0) return 1;
+    return strcmp(e, "wide") == 0 ? 2 : 0;
+  }();
+  const int single = tiled_cfg_code_single(a, ks);
+  const int cls = wg_job_class(a, ks);
+  if (!grouped || cls < 0 || mode == 1 || rsis_deterministic()) return single;
+  const int code = mode == 2 ? wg_wide_code(ks, cls) : wg_group_tile(ks, tw, cls);
+  return code < 0 ? single : code;
 }
 
 // ---- split plan: tiles_per_split of every job of one launch (n_co_tiles / n_n_tiles / n_sp_tiles are set).  Every split adds a
@@ -479,6 +554,8 @@ static void tiled_split_plan(WgradTiledArgs* jobs, int n, int ks, bool big_tile,
   long total_iters = 0;
   for (int j = 0; j < n; ++j) total_iters += (long)jobs[j].n_co_tiles * jobs[j].n_n_tiles * jobs[j].n_sp_tiles;
   static const int env_tb = getenv("RSIS_WG_GROUP_BLOCKS") ? atoi(getenv("RSIS_WG_GROUP_BLOCKS")) : 0;     // tuning knob
+  // (the target does not go with the tile area: the 128 x 128 1x1 buckets, four times the atomics per block of the 64 x 64 ones, measured
+  //  1.04 / 1.06 / 0.98 at 1024 blocks against 2048 on 16- / 32- / 8-wide tiles -- NOTES (80))
   const long target_blocks = env_tb > 0 ? env_tb : 2048;
   long L = (total_iters + target_blocks - 1) / target_blocks;
   if (L < 2) L = 2;
@@ -503,6 +580,7 @@ static int launch_group_cfg(WgradTiledArgs* jobs, int n, bool alone, hipStream_t
   tiled_split_plan(jobs, n, KS, BM * BN >= 128 * 128, alone, RAG);
   for (int j0 = 0; j0 < n; j0 += RSIS_WG_MAXJ) {
     WgradTiledGroup g;
+    g.xcd_order = !alone && wg_xcd_order(KS, TW, tiled_code_of(BM, BN), RAG);      // (a single launch keeps the hardware order)
     g.n = n - j0 < RSIS_WG_MAXJ ? n - j0 : RSIS_WG_MAXJ;
     int blocks = 0;
     for (int j = 0; j < g.n; ++j) {
@@ -571,10 +649,10 @@ static int tiled_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipS
   for (int j = 0; j < n; ++j) {
     WgradTiledArgs& a = all[j] = tiled_args(w[j]);
     const int twa = tiled_tw(a.H, a.W, ks);
-    if (twa) key[j] = twa * 8 + tiled_cfg_code(a, ks);
+    if (twa) key[j] = twa * 8 + tiled_cfg_code(a, ks, twa, !alone);
     else {                      // ragged map: 1024 = dword DMA (RAG 1), 2048 = whole dwordx4 groups (RAG 2)
       if (ks == 1 && (a.H * a.W) % 4 == 0) { a.W = a.H * a.W; a.H = 1; }      // a 1x1 walks the flattened map
-      key[j] = (a.W % 4 == 0 ? 2048 : 1024) + tiled_tw_ragged(a.W, ks) * 8 + tiled_cfg_code(a, ks);
+      key[j] = (a.W % 4 == 0 ? 2048 : 1024) + tiled_tw_ragged(a.W, ks) * 8 + tiled_cfg_code_single(a, ks);
     }
   }
   int rc = RSIS_OK;
