@@ -293,7 +293,7 @@ int rsis_rmsprop_step(float* p, const float* g, float* sq, long n, float lr, flo
                       void* stream);
 
 /* ---- Hungarian matching of predictions to ground-truth slots (hungarian.py:91-125, munkres.Munkres().compute per
- * sample): scores[B][G][T] fp32 (rows = GT slots, columns = predictions, T <= G <= 64) -> perm[B][G] int64 with
+ * sample): scores[B][G][T] fp32 (rows = GT slots, columns = predictions, T <= G <= 128) -> perm[B][G] int64 with
  * perm[b][t] = GT slot of prediction t for t < T and 0 elsewhere.  Minimum total cost; runs on the device so the training
  * iteration needs no host synchronisation. ---- */
 int rsis_assign_min_cost(const float* scores, long long* perm, int B, int G, int T, void* stream);
@@ -382,7 +382,7 @@ int rsis_idmap_rle_encode(const unsigned char* idmap, int h, int w, const int* i
 /* ---- soft-IoU matching scores and matched-loss gradient (train.py:98-110,127-131,162-163; hungarian.py:62-89 softIoU) ----
  * rsis_softiou_sums: logits[B][T][N] (mask logits of the T predictions), y[B][G][N] (ground-truth masks, 0/1 floats) ->
  *   S[B][T+1][G+1]:  S[t][g] = sum_n sigmoid(logits[t][n]) * y[g][n],  S[t][G] = sum_n sigmoid(logits[t][n]),
- *   S[T][g] = sum_n y[g][n]  (S[T][G] is left 0).  One pass over both tensors; requires T < 32, G < 32, N % 8 == 0.
+ *   S[T][g] = sum_n y[g][n]  (S[T][G] is left 0).  One pass over both tensors; requires T <= 128, G <= 128, N % 8 == 0.
  *   The reference's cost is then 1 - S[t][g] / (S[t][G] + S[T][g] - S[t][g] + 1e-6) for every pair.
  * rsis_softiou_bwd: gradient of the matched costs w.r.t. the logits,
  *   dlogits[b][t][n] = (ca[b][t]*y + cb[b][t]*(1-y)) * p*(1-p),  y = y[b][perm[b*perm_ld + t]][n], p = sigmoid(logits[b][t][n]);

@@ -853,14 +853,14 @@ int rsis_rmsprop_step(float* p, const float* g, float* sq, long n, float lr, flo
 }
 
 int rsis_assign_min_cost(const float* scores, long long* perm, int B, int G, int T, void* stream) {
-  if (!scores || !perm || B < 1 || T < 1 || G < T || G > 64) return RSIS_ERR_ARG;
+  if (!scores || !perm || B < 1 || T < 1 || G < T || G > 128) return RSIS_ERR_ARG;
   return rsis_l_assign(scores, perm, B, G, T, (hipStream_t)stream);
 }
 
 }  // extern "C"
 
 int rsis_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, void* stream) {
-  if (!logits || !y || !S || B < 1 || T < 1 || G < 1 || T >= 32 || G >= 32 || N < 8 || N % 8 != 0) return RSIS_ERR_ARG;
+  if (!logits || !y || !S || B < 1 || T < 1 || G < 1 || T > 128 || G > 128 || N < 8 || N % 8 != 0) return RSIS_ERR_ARG;
   return rsis_l_softiou_sums(logits, y, S, B, T, G, N, (hipStream_t)stream);
 }
 

@@ -63,6 +63,92 @@ __global__ __launch_bounds__(256) void softiou_sums_kernel(const float* __restri
   }
 }
 
+// 32 <= max(T, G) <= 128: the [T] x [G] intersections are tiled into NT x NG 32x32 MFMA tiles (NT = ceil(T / 32), NG = ceil(G / 32)).
+// The 4 waves of a block form 4 / NTR pixel groups of NTR = 1, 2 or 4 waves (NT rounded up to a power of two); the waves of a
+// group walk the SAME pixels, wave tw owns T tile tw and every G tile: NG accumulator tiles = at most 64 registers.  Each wave
+// fetches its own 32 logit rows once and takes their sigmoid once (expf + a division: ~25 VALU instructions per value -- with the
+// roles the other way round, every wave evaluating the sigmoids of all T tiles, 128 x 128 was VALU-bound at the speed of the bmm
+// path); the GT rows, which need no arithmetic, are fetched by every wave of the group, the first from HBM and the siblings from
+// L1 / L2 (same CU, same addresses, within a few steps of each other), so HBM still sees every value once per launch.
+// The plain sums do NOT ride along as a "ones" row / column here -- at T or G = 32, 64, 128 that single row would open a whole
+// extra tile row of MFMAs: each lane adds up the four values of its row it feeds to the MFMAs anyway (pairwise, then one chain
+// per lane), and one cross-half add per row at the end gives sum p and (from the wave of T tile 0) sum y.
+// Same load discipline as above: unconditional loads, rows beyond T / G read row 0 and are selected away, four steps in flight.
+template <int NG>
+__global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __restrict__ logits, const float* __restrict__ y,
+                                                                 float* __restrict__ S, int T, int G, long N, long per_wave, int tshift) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5, wave = threadIdx.x >> 6;
+  const int tw = wave & ((1 << tshift) - 1);                          // T tile of this wave
+  const long pw = (long)blockIdx.x * (4 >> tshift) + (wave >> tshift);   // pixel group
+  const long k0 = pw * per_wave, k1 = min(N, k0 + per_wave);
+  if (k0 >= k1 || tw * 32 >= T) return;
+  const int trow = tw * 32 + l31;
+  const bool arow = trow < T;
+  const float* pa = logits + ((size_t)b * T + (arow ? trow : 0)) * N + 4 * hi;
+  const float* pb[NG];
+  bool brow[NG];
+  f32x16 acc[NG];
+  float ys[NG], ps = 0.f;
+#pragma unroll
+  for (int gt = 0; gt < NG; ++gt) {
+    brow[gt] = gt * 32 + l31 < G;
+    pb[gt] = y + ((size_t)b * G + (brow[gt] ? gt * 32 + l31 : 0)) * N + 4 * hi;
+    ys[gt] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[gt][r] = 0.f;
+  }
+  auto step = [&](const f32x4 va, const f32x4* vb) {
+    f32x4 a, bv[NG];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = arow ? rsis_sigmoid(va[e]) : 0.f;
+    ps += (a[0] + a[1]) + (a[2] + a[3]);
+#pragma unroll
+    for (int gt = 0; gt < NG; ++gt) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bv[gt][e] = brow[gt] ? vb[gt][e] : 0.f;
+      ys[gt] += (bv[gt][0] + bv[gt][1]) + (bv[gt][2] + bv[gt][3]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)                    // (tiles innermost: consecutive MFMAs are independent)
+#pragma unroll
+      for (int gt = 0; gt < NG; ++gt) acc[gt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], bv[gt][e], acc[gt], 0, 0, 0);
+  };
+  long k = k0;
+  for (; k + 32 <= k1; k += 32) {
+    f32x4 va[4], vb[4][NG];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      va[u] = *(gcf4_t)(pa + k + 8 * u);
+#pragma unroll
+      for (int gt = 0; gt < NG; ++gt) vb[u][gt] = *(gcf4_t)(pb[gt] + k + 8 * u);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) step(va[u], vb[u]);
+  }
+  for (; k < k1; k += 8) {
+    f32x4 vb[NG];
+#pragma unroll
+    for (int gt = 0; gt < NG; ++gt) vb[gt] = *(gcf4_t)(pb[gt] + k);
+    step(*(gcf4_t)(pa + k), vb);
+  }
+  float* Sb = S + (size_t)b * (T + 1) * (G + 1);
+#pragma unroll
+  for (int gt = 0; gt < NG; ++gt) {
+    if (brow[gt]) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = tw * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (i < T) atomicAdd(Sb + (size_t)i * (G + 1) + gt * 32 + l31, acc[gt][r]);
+      }
+    }
+    const float yt = ys[gt] + __shfl_xor(ys[gt], 32, 64);      // the two pixel halves of a row
+    if (tw == 0 && brow[gt] && hi == 0) atomicAdd(Sb + (size_t)T * (G + 1) + gt * 32 + l31, yt);
+  }
+  ps += __shfl_xor(ps, 32, 64);
+  if (arow && hi == 0) atomicAdd(Sb + (size_t)trow * (G + 1) + G, ps);
+}
+
 // dlogits[b][t][n] = (ca[b][t] * y + cb[b][t] * (1 - y)) * p (1 - p),  y = Y[b][perm[b][t]][n],  p = sigmoid(logits[b][t][n])
 __global__ __launch_bounds__(256) void softiou_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ y,
                                                           const long long* __restrict__ perm, int perm_ld,
@@ -92,6 +178,29 @@ int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, in
   // no prediction or no ground-truth slot: every sum is zero, and the kernel's unconditional loads of row 0 (lanes beyond T / G
   // read it and discard the value) would touch a row that does not exist
   if (T == 0 || G == 0 || N == 0) return RSIS_OK;
+  if (T >= 32 || G >= 32) {
+    // tiled kernel: `groups` pixel groups per block, ~4 blocks per CU over the whole batch, a multiple of 8 pixels per group
+    const int nT = (T + 31) / 32, nG = (G + 31) / 32;
+    if (nT > 4 || nG > 4) return RSIS_ERR_ARG;
+    const int tshift = nT <= 1 ? 0 : nT == 2 ? 1 : 2, groups = 4 >> tshift;
+    long nblk = (1024 + B - 1) / B;
+    long per = (N + nblk * groups - 1) / (nblk * groups);
+    per = (per + 7) / 8 * 8;
+    if (per < 64) per = 64;
+    if (rsis_deterministic()) per = (N + 7) / 8 * 8;          // one group per image: a single contributor per sum
+    nblk = (N + per * groups - 1) / (per * groups);
+    const dim3 grid((unsigned)nblk, B);
+#define RSIS_SIOU_TILED(NG_) \
+    hipLaunchKernelGGL(softiou_sums_tiled_kernel<NG_>, grid, dim3(256), 0, st, logits, y, S, T, G, N, per, tshift)
+    switch (nG) {
+      case 1: RSIS_SIOU_TILED(1); break;
+      case 2: RSIS_SIOU_TILED(2); break;
+      case 3: RSIS_SIOU_TILED(3); break;
+      default: RSIS_SIOU_TILED(4); break;
+    }
+#undef RSIS_SIOU_TILED
+    return rsis_check_launch();
+  }
   // ~4 blocks per CU over the whole batch; each wave gets a multiple of 8 pixels
   int nsplit = (int)((1024 + B - 1) / B);
   long per_wave = (N + (long)nsplit * 4 - 1) / ((long)nsplit * 4);

@@ -954,13 +954,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 
 // ------------------------------------------------------------------------------------------------
 // Minimum-cost assignment of predictions to ground-truth slots (reference src/utils/hungarian.py:91-125: Munkres per
-// sample on the host, with a D2H copy of the scores and a host sync in the middle of every iteration).  One thread per
+// sample on the host, with a D2H copy of the scores and a host sync in the middle of every iteration).  One wave per
 // sample runs the O(T^2 G) shortest-augmenting-path Hungarian algorithm with potentials in fp64 on the device, so the
 // training step has no host synchronisation at all.  scores[b][g][t]: rows = GT slots, columns = predictions (G >= T);
 // perm[b][t] = GT slot assigned to prediction t, perm[b][t >= T] = 0 (what hungarian.py leaves in unassigned columns).
+// T <= G <= 128: up to 64 GT slots run assign_kernel (one column per lane), 65..128 assign2_kernel (two columns per lane, scores in LDS).
 // ------------------------------------------------------------------------------------------------
 #define RSIS_ASSIGN_MAX 64
-// One 64-lane wave per sample: lane j owns GT slot ("column") j+1 of the classical algorithm -- its potential v, the
+// G <= 64.  One 64-lane wave per sample: lane j owns GT slot ("column") j+1 of the classical algorithm -- its potential v, the
 // running minimum minv, used / way / p -- and lane i owns the potential u of prediction ("row") i+1; the inner scan over
 // columns is a wave-wide arg-min (first minimum wins, as in the sequential scan), row lookups are lane shuffles.
 __global__ __launch_bounds__(64) void assign_kernel(const float* __restrict__ scores, long long* __restrict__ perm, int B, int G,
@@ -1021,6 +1022,115 @@ __global__ __launch_bounds__(64) void assign_kernel(const float* __restrict__ sc
   if (col && p != 0) outp[p - 1] = lane;
   __syncthreads();
   if (lane < G) perm[(size_t)b * G + lane] = outp[lane];
+}
+
+// 65 <= G <= 128: the same algorithm with TWO columns (and two rows) per lane: lane j owns GT slots j and j + 64 and the potentials
+// of predictions j and j + 64.  The arg-min compares COLUMN indices on ties (a lane first prefers its lower column), so the first
+// minimum of the sequential scan still wins.  The sample's scores are staged into LDS once, transposed to [t][g] (a row lookup is
+// then one conflict-free LDS read per column instead of a dependent global load per iteration: ~G * T round trips per sample
+// at G = T = 128); the output staging reuses that buffer.
+#define RSIS_ASSIGN_MAX2 128
+__device__ __forceinline__ int assign2_lane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
+__device__ __forceinline__ double assign2_lane(double x, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+// x of lane i combined (fmin) with x of the lane a DPP control names; lanes the control leaves without a source keep x
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double assign2_min_dpp(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  return fmin(x, __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false),
+                                  __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false)));
+}
+// minimum over the wave: an inclusive scan inside each row of 16 lanes (row_shr 1, 2, 4, 8: lane 15 of a row then holds the row's
+// minimum), row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3: lane 63 holds the wave's.  Register moves, where six xor
+// shuffles of a double are twelve round trips through the LDS crossbar on the critical path of every iteration.
+__device__ __forceinline__ double assign2_wave_min(double x) {
+  x = assign2_min_dpp<0x111, 0xf>(x);
+  x = assign2_min_dpp<0x112, 0xf>(x);
+  x = assign2_min_dpp<0x114, 0xf>(x);
+  x = assign2_min_dpp<0x118, 0xf>(x);
+  x = assign2_min_dpp<0x142, 0xa>(x);
+  x = assign2_min_dpp<0x143, 0xc>(x);
+  return assign2_lane(x, 63);
+}
+__global__ __launch_bounds__(64) void assign2_kernel(const float* __restrict__ scores, long long* __restrict__ perm, int B, int G,
+                                                     int T) {
+  extern __shared__ __attribute__((aligned(16))) float sc_t[];   // G * T floats (at most 64 KB), and at least G int64 for the output
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float* a = scores + (size_t)b * G * T;   // a[g*T + t]
+  for (int e = lane; e < G * T; e += 64) {
+    const int g = e / T, t = e - g * T;
+    sc_t[t * G + g] = a[e];
+  }
+  __syncthreads();
+  const int n = T, m = G;
+  const bool col[2] = {lane < m, lane + 64 < m};
+  double u[2] = {0.0, 0.0}, v[2] = {0.0, 0.0};
+  int p[2] = {0, 0};                               // rows assigned to my columns (0 = free)
+  // value that the owner of (1-based) column / row `idx` holds: idx is wave-uniform (it comes from a ballot or from such a value),
+  // so this is a v_readlane with a scalar lane select, not a shuffle through LDS
+#define ASSIGN2_GET(x, idx) assign2_lane(((idx) - 1) >> 6 ? (x)[1] : (x)[0], ((idx) - 1) & 63)
+  for (int i = 1; i <= n; ++i) {
+    const int p0 = i;
+    int j0 = 0;
+    double minv[2] = {1e300, 1e300};
+    bool used[2] = {false, false}, in_tree[2] = {false, false};
+    int way[2] = {0, 0};
+    for (int it = 0; it <= m; ++it) {              // (cap: see assign_kernel)
+      const int i0 = j0 == 0 ? p0 : ASSIGN2_GET(p, j0);
+      const double ui0 = ASSIGN2_GET(u, i0);
+      double cand[2] = {1e300, 1e300};
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (j0 > 0 && lane + 64 * s == j0 - 1) used[s] = true;
+        if (lane + 64 * s == i0 - 1) in_tree[s] = true;
+        if (col[s] && !used[s]) {
+          const float sc = sc_t[(i0 - 1) * G + lane + 64 * s];
+          const double cur = (sc == sc && fabsf(sc) < 1e30f ? (double)sc : 1e30) - ui0 - v[s];
+          if (cur < minv[s]) { minv[s] = cur; way[s] = j0; }
+          cand[s] = minv[s];
+        }
+      }
+      // wave arg-min, smallest column on ties: the minimum first (cand is never NaN), then the lowest lane that holds it --
+      // columns 0..63 before columns 64..127
+      const double best = assign2_wave_min(fmin(cand[0], cand[1]));
+      const unsigned long long m0 = __ballot(cand[0] == best), m1 = __ballot(cand[1] == best);
+      const int bj = m0 ? __ffsll((long long)m0) - 1 : 64 + __ffsll((long long)m1) - 1;
+      const double delta = best;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (in_tree[s]) u[s] += delta;
+        if (col[s]) { if (used[s]) v[s] -= delta; else minv[s] -= delta; }
+      }
+      j0 = bj + 1;
+      if (ASSIGN2_GET(p, j0) == 0) break;
+    }
+    // augment along the alternating path
+    while (j0 != 0) {
+      const int j1 = ASSIGN2_GET(way, j0);
+      const int pj1 = j1 == 0 ? p0 : ASSIGN2_GET(p, j1);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (lane + 64 * s == j0 - 1) p[s] = pj1;
+      j0 = j1;
+    }
+  }
+#undef ASSIGN2_GET
+  // perm[b][t] = column of row t+1; zeros elsewhere
+  __syncthreads();
+  long long* outp = reinterpret_cast<long long*>(sc_t);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    if (lane + 64 * s < G) outp[lane + 64 * s] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    if (col[s] && p[s] != 0) outp[p[s] - 1] = lane + 64 * s;
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    if (lane + 64 * s < G) perm[(size_t)b * G + lane + 64 * s] = outp[lane + 64 * s];
 }
 
 // zero fill (see common.h: rsis_zero_async)
@@ -1304,6 +1414,8 @@ int rsis_l_adam(float* p, const float* g, float* m, float* v, long n, float lr, 
 }
 
 int rsis_l_assign(const float* scores, long long* perm, int B, int G, int T, hipStream_t st) {
-  hipLaunchKernelGGL(assign_kernel, dim3(B), dim3(64), 0, st, scores, perm, B, G, T);
+  if (G > RSIS_ASSIGN_MAX2) return RSIS_ERR_ARG;
+  if (G <= RSIS_ASSIGN_MAX) hipLaunchKernelGGL(assign_kernel, dim3(B), dim3(64), 0, st, scores, perm, B, G, T);
+  else hipLaunchKernelGGL(assign2_kernel, dim3(B), dim3(64), sizeof(float) * (size_t)G * (T < 2 ? 2 : T), st, scores, perm, B, G, T);
   return rsis_check_launch();
 }

@@ -179,11 +179,11 @@ def runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits
             scores[:, :, :t] = args.iou_weight * softIoU_matrix(y_mask, out_masks)
         valid = (sw_mask.unsqueeze(-1) * sw_mask[:, 0:args.maxseqlen].unsqueeze(1) > 0).float()   # :127-130
         scores = scores * valid + (1 - valid) * 10                                                 # :131
-        if scores.is_cuda and scores.size(1) <= 64 and scores.size(1) >= scores.size(2):
+        if scores.is_cuda and scores.size(1) <= 128 and scores.size(1) >= scores.size(2):
             perm = ops.assign_min_cost(scores)                                                     # :137 on the device: no sync
         else:
             log_once("host-assignment", "assignment on the host (scipy, one D2H sync per step): %d GT slots x %d steps" % (scores.size(1), scores.size(2)))
-            perm = torch.from_numpy(match_indices(scores)).to(x.device)                           # more than 64 GT slots: host assignment (scipy), as the reference does
+            perm = torch.from_numpy(match_indices(scores)).to(x.device)                           # more than 128 GT slots (or fewer slots than steps): host assignment (scipy), as the reference does
         idx = perm[:, 0:t]
         # :140 -- the permuted GT masks are a RETURN value here (the matched loss below reads y_mask through `perm`): 84 MB of
         # gather per step that a training loop which only logs the losses (want_outs=False) does not need; the fallback loss does

@@ -3,8 +3,8 @@
 training steps (no graph: the host-assignment fallback synchronises) at BASELINE configs[1] (256 x 256, T = 10, batch 32, fp32) with
   default            : the sequence decoder node, fused soft-IoU kernels, device assignment (gt_maxseqlen 20)
   per-step decoder   : RSIS_DECODER_SEQ=0 (what runs when decoder_seq.supported() is False)
-  soft-IoU via bmm   : gt_maxseqlen = 40 (>= 32 GT slots: ops.softiou_supported is False), device assignment still applies
-  host assignment    : gt_maxseqlen = 72 (> 64 GT slots: scipy on the host, one D2H sync per step) -- also soft-IoU via bmm
+  gt_maxseqlen 40, 72: still the device path (tiled soft-IoU sums; two-columns-per-lane assignment above 64 slots): "announced: -"
+  host assignment    : gt_maxseqlen = 136 (> 128 GT slots: soft-IoU via torch.bmm, scipy on the host with one D2H sync per step)
 each in its own process.   python tools/fallback_cost.py [--steps 10]"""
 import argparse
 import os
@@ -50,7 +50,8 @@ def main():
         child(o.child, o.steps)
         return
     rows = [("default (gt_maxseqlen 20)", 20, {}), ("per-step decoder (RSIS_DECODER_SEQ=0)", 20, {"RSIS_DECODER_SEQ": "0"}),
-            ("soft-IoU via torch.bmm (gt_maxseqlen 40)", 40, {}), ("host assignment + bmm (gt_maxseqlen 72)", 72, {})]
+            ("device path (gt_maxseqlen 40)", 40, {}), ("device path (gt_maxseqlen 72)", 72, {}),
+            ("host assignment + bmm (gt_maxseqlen 136)", 136, {})]
     base = None
     for name, gt, env in rows:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(gt), "--steps", str(o.steps)], capture_output=True, text=True,
