@@ -122,6 +122,84 @@ def host_sums(xs, w, b):
     return chain, seg
 
 
+def _sums_padded(xps, w, Ho, Wo, stride):
+    """the loop of host_sums for any square kernel and stride over sources that already carry their padding: out[b, co, y, x] = sum over
+    (source, channel, r, s) of w[co, c, r, s] * xp[b, c, y * stride + r, x * stride + s]; returns (chain, segmented) without a bias"""
+    B, Cout, ks = xps[0].shape[0], w.shape[0], w.shape[2]
+    chain = np.zeros((B, Cout, Ho, Wo), np.float32)
+    acc, tot = np.zeros_like(chain), np.zeros_like(chain)
+    chunk, c_off = 0, 0
+    for xp in xps:
+        for c in range(xp.shape[1]):
+            if c % CK == 0:
+                if chunk > 0 and chunk % ACC_FLUSH == 0:
+                    tot += acc
+                    acc[:] = 0
+                chunk += 1
+            for r in range(ks):
+                for s in range(ks):
+                    term = w[None, :, c_off + c, r, s, None, None] * xp[:, None, c, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
+                    chain += term
+                    acc += term
+        c_off += xp.shape[1]
+    seg = tot + acc
+    assert chain.dtype == np.float32 and seg.dtype == np.float32
+    return chain, seg
+
+
+def host_sums_conv(xs, w, b, stride=1, pad=1):
+    """host_sums for any square kernel, stride and padding (3x3 / stride 1 / pad 1: the same bits as host_sums).  The order is the one the
+    implicit-GEMM kernels walk as well: k = (channel over the concat, r, s) ascending."""
+    ks = w.shape[2]
+    H, W = xs[0].shape[2:]
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    chain, seg = _sums_padded([np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad))) for x in xs], w, Ho, Wo, stride)
+    if b is not None:
+        chain, seg = chain + b[None, :, None, None], seg + b[None, :, None, None]
+    return chain, seg
+
+
+def host_sums_dgrad(dy, w, stride, pad, Hx, Wx):
+    """the data gradient dx (B, Cin, Hx, Wx) of a conv with weight w (Cout, Cin, ks, ks) as the kernels form it: a stride-1 conv that
+    gathers from dy (B, Cout, Hy, Wx) with the ROTATED, TRANSPOSED weights wT[ci, co, r', s'] = w[co, ci, ks-1-r', ks-1-s'], the reduction
+    walked over the Cout rows of dy ascending (chunks of CK of THEM, as the direct kernel counts) and the taps row-major.  A strided
+    conv's gradient gathers from dy spread out with zeros (dy[yo, xo] at pixel (yo * stride, xo * stride)): the products with those
+    zeros are exact zeros and leave an fp32 running sum unchanged, so the order of the non-zero terms is the kernels' (the parity-class
+    kernel and the strided gathers skip exactly those terms).  Returns (chain, segmented), float32."""
+    B, Cout, Hy, Wy = dy.shape
+    ks = w.shape[2]
+    lo = ks - 1 - pad
+    up = np.zeros((B, Cout, Hx + ks - 1, Wx + ks - 1), np.float32)
+    ny, nx = min(Hy, (Hx + ks - 2 - lo) // stride + 1), min(Wy, (Wx + ks - 2 - lo) // stride + 1)
+    up[:, :, lo:lo + (ny - 1) * stride + 1:stride, lo:lo + (nx - 1) * stride + 1:stride] = dy[:, :, :ny, :nx]
+    wT = np.ascontiguousarray(w[:, :, ::-1, ::-1].transpose(1, 0, 2, 3))
+    return _sums_padded([up], wT, Hx, Wx, 1)
+
+
+# ---- the ConvLSTM cell in float64 and the bar of its gate pre-activations (test_gpu_infer_paths.py, test_gpu_train_paths.py)
+def cell64(w, b, xs, state, pad=1):
+    """clstm.py:43-58 in float64 (test_gpu_bf16._oracle_cell_rounded without the rounding); returns (h, c, gate pre-activations, in the
+    reference's row order [i | f | o | g])"""
+    import torch.nn.functional as F
+    srcs = [to_tensor(x).double() for x in xs] + ([state[0].double()] if state is not None else [])
+    cin = sum(s.shape[1] for s in srcs)
+    gates = F.conv2d(torch.cat(srcs, 1), to_tensor(w).double()[:, :cin], to_tensor(b).double(), padding=pad)
+    i, f, o, g = gates.chunk(4, 1)
+    i, f, o, g = torch.sigmoid(i), torch.sigmoid(f), torch.sigmoid(o), torch.tanh(g)
+    c = f * (state[1].double() if state is not None else 0.0) + i * g
+    return o * torch.tanh(c), c, gates
+
+
+def gate_bar(w, b, xs, state, gates64, m, model="segmented", pad=1):
+    """e = m * err_host + 2e-7: the tight bar of the gate pre-activations of this call.  err_host: the host model (`segmented` for an
+    inference call, `chain` for a training call below RSIS_FLUSH_MIN_CHUNKS chunks) of the gate conv over the sources the kernel walks."""
+    srcs = list(xs) + ([state[0].float().numpy()] if state is not None else [])
+    cin = sum(s.shape[1] for s in srcs)
+    wc = np.ascontiguousarray(w[:, :cin])
+    chain, seg = host_sums(srcs, wc, b) if (w.shape[2] == 3 and pad == 1) else host_sums_conv(srcs, wc, b, 1, pad)
+    return m * max_err(seg if model == "segmented" else chain, gates64) + 2e-7
+
+
 # ---- the fp32 ConvLSTM pointwise backward (test_gpu_decoder_bwd_ops.py, test_decoder_bwd_host.py): reference, bars, guarded buffers
 LSTM_BWD_K = 24               # allowed error in units of 2^-24 * lstm_bwd_scales(..): see test_decoder_bwd_host.py for the derivation
 LSTM_BWD_OUTS = ("da_i", "da_f", "da_o", "da_g", "dc_prev")

@@ -22,7 +22,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import ACC_FLUSH, CK, assert_close, f32_normal as _rng, host_sums as _host_sums, max_err as _err, mk_args, to_tensor as _t
+from helpers import (ACC_FLUSH, CK, assert_close, cell64 as _cell64, f32_normal as _rng, gate_bar, host_sums as _host_sums, max_err as _err,
+                     mk_args, to_tensor as _t)
 
 pytestmark = pytest.mark.gpu
 
@@ -140,24 +141,9 @@ LSTM_CASES = [
 ]
 
 
-def _cell64(w, b, xs, state):
-    """clstm.py:43-58 in float64 (test_gpu_bf16._oracle_cell_rounded without the rounding); returns (h, c, gate pre-activations, in the
-    reference's row order [i | f | o | g])"""
-    srcs = [_t(x).double() for x in xs] + ([state[0].double()] if state is not None else [])
-    cin = sum(s.shape[1] for s in srcs)
-    gates = F.conv2d(torch.cat(srcs, 1), _t(w).double()[:, :cin], _t(b).double(), padding=1)
-    i, f, o, g = gates.chunk(4, 1)
-    i, f, o, g = torch.sigmoid(i), torch.sigmoid(f), torch.sigmoid(o), torch.tanh(g)
-    c = f * (state[1].double() if state is not None else 0.0) + i * g
-    return o * torch.tanh(c), c, gates
-
-
 def _gate_bar(w, b, xs, state, gates64):
     """e: the tight bar of the gate pre-activations of this call (host segmented model of the gate conv over the sources the kernel walks)"""
-    srcs = list(xs) + ([state[0].float().numpy()] if state is not None else [])
-    cin = sum(s.shape[1] for s in srcs)
-    _chain, seg = _host_sums(srcs, np.ascontiguousarray(w[:, :cin]), b)
-    return M_TIGHT * _err(seg, gates64) + 2e-7
+    return gate_bar(w, b, xs, state, gates64, M_TIGHT)
 
 
 def _lstm_weights(case, seed=1):
