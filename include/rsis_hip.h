@@ -438,6 +438,25 @@ int rsis_rle_to_string(const unsigned int* counts, int m, char* out, int cap);
 int rsis_largest_component(const unsigned char* mask, unsigned char* out, int* labels, int* counts, int* best, int n, int h, int w,
                            void* stream);
 
+/* ---- eval --display figures (eval.py:30-95 display_masks: the kept instance masks painted over the image in their sequence colours,
+ * the class name at each mask's centre of mass; overlay.hip) ----
+ * masks[n][w][h] uint8 are COLUMN-major h x w masks, zero / non-zero: the seg / raw layout of rsis_mask_resize_threshold.  order[k]
+ * int32 (DEVICE) picks the k masks to draw and gives their paint order; an entry outside [0, n) cannot be checked without a copy and
+ * paints nothing (its moments are zero).  h, w <= 2^30.
+ * rsis_overlay_moments: moments[k][3] unsigned 64-bit = (set pixels, sum of row indices, sum of column indices) of mask order[j].
+ *   Integer sums in 64 bits (the column sum passes 2^32 at 2048 x 4096): nothing depends on the order of execution.  k == 0: nothing
+ *   is launched.
+ * rsis_overlay_masks: image[h][w][3] and out[h][w][3] uint8, ROW-major interleaved RGB; colors[k][3] uint8 (DEVICE).  Per pixel and
+ *   channel in fp32: v = image; for j = 0 .. k-1 in that order, where mask order[j] is non-zero at the pixel, v = fmaf(alpha,
+ *   (float)colors[j][c] - v, v); out = (uint8)(v + 0.5f).  k == 0 copies the image (masks / order / colors may then be null); out may
+ *   not alias image.
+ * RSIS_ERR_ARG, nothing launched: a null pointer with k > 0 (image / out: always), n < 1 with k > 0, h or w < 1, k < 0, alpha outside
+ *   [0, 1] (NaN included), out == image. */
+int rsis_overlay_moments(const unsigned char* masks, int n, const int* order, int k, int h, int w, unsigned long long* moments,
+                         void* stream);
+int rsis_overlay_masks(const unsigned char* image, const unsigned char* masks, int n, const int* order, const unsigned char* colors,
+                       int k, float alpha, unsigned char* out, int h, int w, void* stream);
+
 /* ---- COCO 'segm' evaluation on bit-packed masks (cocoeval.py:164-191 computeIoU, :236-314 evaluateImg of the reference's modified
  * pycocotools; IoU semantics of maskApi.c:77-96 rleIou).  A mask of `len` elements is `stride` >= ceil(len / 64) 64-bit words, element e
  * = bit e % 64 of word e / 64, every bit past len zero.  The grouped launches read their job tables (int64, 8 entries per job) from

@@ -165,6 +165,8 @@ SIGNATURES = {
     "rsis_mask_resize_threshold": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
     "rsis_rle_encode": (_i, [_vp, _i, _l, _vp, _i, _vp, _vp]),
     "rsis_largest_component": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rsis_overlay_moments": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "rsis_overlay_masks": (_i, [_vp, _vp, _i, _vp, _vp, _i, _f, _vp, _i, _i, _vp]),
     "rsis_rle_to_string": (_i, [_vp, _i, ctypes.c_char_p, _i]),
     "rsis_mask_pack_bits": (_i, [_vp, _i, _l, _vp, _l, _vp, _vp]),
     "rsis_rle_to_bits": (_i, [_vp, _l, _vp, _i, _vp, _vp, _l, _vp, _vp]),

@@ -79,6 +79,9 @@ int rsis_l_mask_resize_threshold(const float*, int, int, int, const unsigned cha
 int rsis_l_rle_encode(const unsigned char*, int, long, unsigned int*, int, int*, hipStream_t);
 int rsis_l_rle_to_string(const unsigned int*, int, char*, int);
 int rsis_l_largest_component(const unsigned char*, unsigned char*, int*, int*, int*, int, int, int, hipStream_t);
+int rsis_l_overlay_moments(const unsigned char*, int, const int*, int, int, int, unsigned long long*, hipStream_t);
+int rsis_l_overlay_masks(const unsigned char*, const unsigned char*, int, const int*, const unsigned char*, int, float, unsigned char*, int, int,
+                         hipStream_t);
 int rsis_l_mask_pack_bits(const unsigned char*, int, long, unsigned long long*, long, unsigned int*, hipStream_t);
 int rsis_l_rle_to_bits(const unsigned int*, long, const long long*, int, unsigned int*, unsigned long long*, long, unsigned int*, hipStream_t);
 long rsis_l_mask_intersect_blocks(long, long, long);
@@ -1002,6 +1005,24 @@ int rsis_largest_component(const unsigned char* mask, unsigned char* out, int* l
                            void* stream) {
   if (!mask || !out || !labels || !counts || !best || n < 1 || h < 1 || w < 1 || (long)h * w >= (1L << 31)) return RSIS_ERR_ARG;
   return rsis_l_largest_component(mask, out, labels, counts, best, n, h, w, (hipStream_t)stream);
+}
+
+#define RSIS_OVERLAY_MAX_SIDE (1 << 30)
+int rsis_overlay_moments(const unsigned char* masks, int n, const int* order, int k, int h, int w, unsigned long long* moments,
+                         void* stream) {
+  if (k < 0 || h < 1 || w < 1 || h > RSIS_OVERLAY_MAX_SIDE || w > RSIS_OVERLAY_MAX_SIDE) return RSIS_ERR_ARG;
+  if (k == 0) return RSIS_OK;
+  if (!masks || !order || !moments || n < 1 || k > 65535) return RSIS_ERR_ARG;
+  return rsis_l_overlay_moments(masks, n, order, k, h, w, moments, (hipStream_t)stream);
+}
+
+int rsis_overlay_masks(const unsigned char* image, const unsigned char* masks, int n, const int* order, const unsigned char* colors,
+                       int k, float alpha, unsigned char* out, int h, int w, void* stream) {
+  if (k < 0 || h < 1 || w < 1 || h > RSIS_OVERLAY_MAX_SIDE || w > RSIS_OVERLAY_MAX_SIDE || !(alpha >= 0.f && alpha <= 1.f))
+    return RSIS_ERR_ARG;
+  if (!image || !out || out == image) return RSIS_ERR_ARG;
+  if (k > 0 && (!masks || !order || !colors || n < 1)) return RSIS_ERR_ARG;
+  return rsis_l_overlay_masks(image, masks, n, order, colors, k, alpha, out, h, w, (hipStream_t)stream);
 }
 
 int rsis_loss_tail(const float* probs, const long long* y_class, const float* stop, const float* siou, const float* sw_mask,

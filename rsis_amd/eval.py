@@ -20,8 +20,23 @@ evaluates Pascal VOC (eval.py:191-218,280-295): the images come from dataloader/
 mask is resampled to its image's ORIGINAL size, the ground truth is <D>/VOCGT_<eval_split>.pkl (rsis_amd.pascal_precompute, or the
 reference's own file, python-2 pickle included) and each image's `ignore == 1` record gives the pixels cleared from its predictions.
 Nothing is written into the dataset directory (the reference's pascal_<split>.json is an artefact of pycocotools' file interface).
-Not built (out of scope): the Cityscapes reader, the matplotlib display path; a ground-truth FILE of another
-dataset is evaluated with `python -m rsis_amd.cocoeval`.
+
+    python -m rsis_amd.eval -dataset cityscapes -cityscapes_dir D ... | -dataset leaves -leaves_dir D ...
+
+(display_cityscapes.sh, display_leaves.sh) read the images through dataloader/cityscapes.py / leaves.py as eval_cityscapes / eval_leaves do,
+with the datasets' class names, every mask resampled to its image's original size and no ignore mask; a sample is named as the
+reference names it (eval.py:287-291: the Cityscapes path without its extension, the leaves path).  The reference's eval.py has no ground
+truth for these two datasets (it stops at an undefined `cocoGT` unless --no_run_coco_eval is given), so the COCO evaluation is skipped for
+them, said in one line on stderr; the predictions file is written as for Pascal.
+
+    python -m rsis_amd.eval ... --display [--no_display_text] [--display_route]
+
+additionally saves one figure per image (eval.py:342-359), <models_root>/<model_name>/<model_name>_figs_<eval_split>/<name>.png: the
+original image (with --synthetic: the de-normalised input) with the RAW mask (before the ignore pixels) of every record kept for display
+painted over it in its sequence colour and the class name at the mask's centre -- composited on the device from the byte masks of the
+post-processing, rsis_amd/display.py.  The records drawn are those of eval.py:329-338: per timestep the class of maximum confidence when
+its score reaches -class_th; for leaves every record of a timestep whose objectness exceeds -stop_th.  Without --display nothing about a
+run changes.  A ground-truth FILE of another dataset is evaluated with `python -m rsis_amd.cocoeval`.
 """
 import json
 import os
@@ -72,12 +87,17 @@ class Evaluate(object):
     def __init__(self, args):
         self.args = args
         self.split = args.eval_split
-        self.gt_records = self.ignore_rle = self.dataset = None
+        self.gt_records = self.ignore_rle = self.dataset = self.dataset_name = None
+        self.display = bool(getattr(args, "display", False))
+        self.figures = []                                           # with --display: (path, records drawn, label rectangles) per image
         if not getattr(args, "synthetic", False):
-            if args.dataset != "pascal":
-                raise Exception("only --synthetic inputs and -dataset pascal are wired in this build (the Cityscapes reader of the "
-                                "reference's src/dataloader is host-side I/O outside the hot path: SURVEY.md section 8)")
-            self._init_pascal()
+            if args.dataset == "pascal":
+                self._init_pascal()
+            elif args.dataset in ("cityscapes", "leaves"):
+                self._init_files(args.dataset)
+            else:
+                raise Exception("-dataset %s: only --synthetic inputs and -dataset pascal, cityscapes and leaves are wired in this build"
+                                % args.dataset)
             return
         self.encoder, self.decoder = load_models(self.args)
         self.class_names = ["<eos>"] + ["class%d" % i for i in range(1, self.args.num_classes)]
@@ -89,6 +109,7 @@ class Evaluate(object):
         from .dataloader.leaves import DeviceLoader
         from .dataloader.pascal import PascalVOC
         args = self.args
+        self.dataset_name = "pascal"
         self.dataset = PascalVOC(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
         self.sample_list = [s.rstrip() for s in self.dataset.get_sample_list()]
         self.class_names = self.dataset.get_classes()
@@ -100,6 +121,46 @@ class Evaluate(object):
         self.encoder, self.decoder = load_models(args)
         self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
                                    drop_last=False)
+
+    def _init_files(self, name):
+        """eval.py:191-218 for -dataset cityscapes / leaves: the reader and loader of eval_cityscapes.py / eval_leaves.py; no ground truth"""
+        from .dataloader.leaves import DeviceLoader, LeavesDataset
+        args = self.args
+        self.dataset_name = name
+        if name == "cityscapes":
+            from .dataloader.cityscapes import CityScapes
+            self.dataset = CityScapes(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+            self.sample_list = [os.path.splitext(f)[0] for f in self.dataset.get_sample_list()]  # eval.py:288
+        else:
+            self.dataset = LeavesDataset(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+            self.sample_list = list(self.dataset.get_sample_list())                             # eval.py:291
+        self.class_names = self.dataset.get_classes()
+        self.encoder, self.decoder = load_models(args)
+        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
+                                   drop_last=False)
+        if not getattr(args, "no_run_coco_eval", False):
+            print("-dataset %s has no ground-truth file in eval.py: the COCO evaluation is skipped" % name, file=sys.stderr)
+
+    def _raw_size(self, index):
+        """(height, width) of the original image of sample `index` (eval.py:293-295)"""
+        if hasattr(self.dataset, "raw_size"):
+            return self.dataset.raw_size(index)
+        from PIL import Image
+        with Image.open(self.dataset.get_sample_list()[index]) as im:
+            w, h = im.size
+        return h, w
+
+    def _display_image(self, index, x):
+        """the (h, w, 3) uint8 image under the figure of sample `index`, on the device: the original file (eval.py:285-293), or with
+        --synthetic the input tensor x (3, H, W) de-normalised"""
+        from . import display
+        if self.dataset is None:
+            return display.denormalize(x)
+        from PIL import Image
+        path = self.dataset.image_path(index) if self.dataset_name == "pascal" else self.dataset.get_sample_list()[index]
+        with Image.open(path) as im:
+            rgb = np.array(im.convert("RGB"), dtype=np.uint8)
+        return torch.as_tensor(rgb).to(x.device)
 
     def _ignore_mask(self, sample_idx):
         """the (h, w) uint8 ignore mask of one image, decoded from its record (column-major runs, the first one of zeros)"""
@@ -113,13 +174,22 @@ class Evaluate(object):
         """eval.py:254-345: one record per (instance, class) with score = class probability * objectness"""
         args = self.args
         predictions, shown, acc = [], [], 0
-        coco = self.coco = None if getattr(args, "no_run_coco_eval", False) else COCOEvalDevice()
+        no_gt = self.dataset_name in ("cityscapes", "leaves")       # eval.py has no ground truth for them: nothing to evaluate against
+        coco = self.coco = None if (getattr(args, "no_run_coco_eval", False) or no_gt) else COCOEvalDevice()
+        figs_dir = None
+        if self.display:
+            from . import display
+            figs_dir = display.figures_dir(args.models_root, args.model_name, self.split)       # eval.py:343-344
+            os.makedirs(figs_dir, exist_ok=True)
         if coco is not None and self.gt_records is not None:
             mine = set(self.sample_list)
             coco.add_gt([r for r in self.gt_records if r["image_id"] in mine])
         for inputs, y_mask, y_class, sw_mask, _sw_class in self.loader:
             x = inputs
-            out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)       # eval.py:262
+            if x.size(0) == 1 and no_gt:         # a lone tail image of the file readers is doubled, as eval_leaves.py does (test() needs B >= 2)
+                out_masks, out_scores, stop_probs = [t[:1] for t in test(args, self.encoder, self.decoder, torch.cat([x, x]))]
+            else:
+                out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)   # eval.py:262
             scores = out_scores.cpu().numpy()
             stops = stop_probs.cpu().numpy()
             classes = np.argmax(scores, axis=-1)
@@ -128,11 +198,17 @@ class Evaluate(object):
                 sample_idx = self.sample_list[s + acc]
                 ignore = None
                 if self.dataset is not None:                       # eval.py:280-295: the ORIGINAL size, the image's ignore pixels
-                    h, w = self.dataset.raw_size(s + acc)
-                    ignore = self._ignore_mask(sample_idx)
+                    h, w = self._raw_size(s + acc)
+                    if self.ignore_rle is not None:
+                        ignore = self._ignore_mask(sample_idx)
                 # all T masks of the image in one launch each: resample + threshold + area, then run-length encoding
-                segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True)
+                if self.display:
+                    segs, areas, raws, bits, dev_masks = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True,
+                                                                      want_masks=True)
+                else:
+                    segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True)
                 rows, cats, recscores = [], [], []                  # of the records that reach the predictions file
+                drawn = []                                          # the image's records for display, each with its mask row
                 for i in range(out_masks.shape[1]):
                     objectness = float(stops[s][i][0])
                     if objectness < args.stop_th:                  # eval.py:303-304
@@ -144,13 +220,24 @@ class Evaluate(object):
                         ann = create_annotation(args, sample_idx, _jsonable(segs[i]), cls_id, score, self.class_names, is_valid)
                         if ann is None:
                             continue
-                        if cls_id == max_class and score >= args.class_th:                       # eval.py:333
+                        if self.dataset_name == "leaves":                                        # eval.py:329-331
+                            if objectness > args.stop_th:
+                                shown.append(ann)
+                                drawn.append(dict(ann, mask_row=i))
+                        elif cls_id == max_class and score >= args.class_th:                     # eval.py:333
                             shown.append(create_annotation(args, sample_idx, _jsonable(raws[i]), cls_id, score, self.class_names,
                                                            is_valid))
+                            drawn.append(dict(shown[-1], mask_row=i))
                         predictions.append(ann)
                         rows.append(i)
                         cats.append(cls_id)
                         recscores.append(score)
+                if self.display:                                    # eval.py:342-359: the RAW masks over the original image
+                    from . import display
+                    fig = os.path.join(figs_dir, display.figure_name(sample_idx, self.dataset_name))
+                    rects = display.save_figure(fig, self._display_image(s + acc, x[s]), dev_masks[1], drawn,
+                                                no_display_text=args.no_display_text, display_route=args.display_route)
+                    self.figures.append((fig, drawn, rects))
                 if coco is not None:
                     # ground truth of the image from the loader's targets, in the detections' (column-major) element order
                     n_gt = int((sw_mask[s] > 0).sum()) if self.gt_records is None else 0     # (Pascal: the records of the file)
@@ -175,6 +262,8 @@ class Evaluate(object):
             json.dump(predictions, f)
         print("%d prediction records (%d above -class_th for display) from %d images -> %s" %
               (len(predictions), len(shown), len(self.sample_list), path))
+        if self.display:
+            print("%d figures -> %s" % (len(self.figures), os.path.dirname(self.figures[0][0]) if self.figures else "(none)"))
         if self.coco is not None:                                    # eval.py:375-398
             args = self.args
             cat_ids = list(range(1, len(self.class_names)))

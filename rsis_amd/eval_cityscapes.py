@@ -25,6 +25,8 @@ benchmark stores it, `<model_name>_gt/<sample>_gtFine_instanceIds.png` (16-bit, 
 instance k of class c >= 1 of the loader's targets has the value CITYSCAPES_CLASS_IDS[c - 1] * 1000 + k, the earlier instance keeps a
 contested pixel, the background is 7 (road: neither void nor an instance; 0 would make every false positive "ignored").
 `python -m rsis_amd.cityscapes_eval --results <..._results> --gt <..._gt>` gives the same JSON from the files.
+`--display` is parsed and ignored here, as in the reference's eval_cityscapes.py (it stores the flag and never reads it); the figures of
+`--display` (display_cityscapes.sh) come from `python -m rsis_amd.eval -dataset cityscapes ... --display`.
 """
 import os
 import sys

@@ -12,7 +12,8 @@ of src/CVPPP by hand) and `<model_name>_A1_results.csv` appears next to the A1 f
 Deviations from the reference script, all deliberate:
   * the last, short batch is evaluated sample by sample that exist (the reference indexes `range(batch_size)` past it and raises);
   * `-eval_split test` reads `-leaves_test_dir` and needs no ground truth (as the reference);
-  * no matplotlib display path.
+  * `--display` is parsed and ignored here, as in the reference's eval_leaves.py (it stores the flag and never reads it).
+The figures of `--display` (display_leaves.sh) come from `python -m rsis_amd.eval -dataset leaves ... --display`.
 """
 import os
 import sys

@@ -12,11 +12,13 @@ import torch
 from ._lib import check, lib, ptr, stream
 
 
-def encode_masks(prob, height, width, th, ignore=None, want_raw=True, want_bits=False):
+def encode_masks(prob, height, width, th, ignore=None, want_raw=True, want_bits=False, want_masks=False):
     """prob: (n, Hm, Wm) CUDA fp32 mask probabilities of one image -> (segs, areas, raws):
     segs / raws: lists of n COCO RLE dicts {'size': [height, width], 'counts': bytes} (raws: before the ignore mask; None when
     want_raw is False), areas: (n,) int64 numpy array of the set-pixel counts of segs.  With want_bits a fourth value follows: the
-    thresholded masks of segs bit-packed on the device, (words, areas, height * width) as rsis_amd.cocoeval takes them."""
+    thresholded masks of segs bit-packed on the device, (words, areas, height * width) as rsis_amd.cocoeval takes them.  With want_masks
+    one more value follows, last: the device byte tensors (seg, raw) of shape (n, width * height) -- COLUMN-major 0 / 1 masks, the ones
+    the RLEs of segs / raws were made of (raw is seg itself when no separate raw copy was written), as rsis_amd.display takes them."""
     L = lib()
     prob = prob.detach()
     if not prob.is_cuda or prob.dtype != torch.float32:
@@ -40,8 +42,12 @@ def encode_masks(prob, height, width, th, ignore=None, want_raw=True, want_bits=
     if want_bits:
         from .cocoeval import pack_bits
         words, barea = pack_bits(seg)
-        return segs, area.cpu().numpy().astype(np.int64), raws, (words, barea, hw)
-    return segs, area.cpu().numpy().astype(np.int64), raws
+        res = (segs, area.cpu().numpy().astype(np.int64), raws, (words, barea, hw))
+    else:
+        res = (segs, area.cpu().numpy().astype(np.int64), raws)
+    if want_masks:
+        res += ((seg, raw if raw is not None else seg),)
+    return res
 
 
 def _rle_dicts(L, masks, n, hw, height, width):
