@@ -79,7 +79,9 @@ long rsis_conv_packed_bytes_dgrad(int dtype, int Cout, int ks, int stride, int p
  * lstm_hid > 0: rows of W are [i|f|o|g] x hid (clstm.py:47) and are interleaved to 4*j+gate */
 int rsis_conv_pack_fwd(const float* W, void* Wp, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg,
                        const int* Coff, int lstm_hid, int dtype, void* stream);
-/* dgrad copy: produces the gradient of the sum(Cseg) input channels of the segments (in segment order) */
+/* dgrad copy: produces the gradient of the sum(Cseg) input channels of the segments (in segment order).  Both pack calls, the size
+ * queries and rsis_conv_pack_job_fill follow ONE layout rule: like rsis_conv_pack_fwd, this call now returns RSIS_ERR_UNSUPPORTED for a
+ * ConvLSTM weight (lstm_hid > 0) under RSIS_DTYPE_BF16 with ks != 3 (it used to pack it; no kernel reads such a copy) */
 int rsis_conv_pack_dgrad(const float* W, void* Wd, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg,
                          const int* Coff, int lstm_hid, int dtype, void* stream);
 

@@ -1,112 +1,8 @@
 // extern "C" entry points of librsis_hip.so (declared in include/rsis_hip.h).  Argument validation + dispatch only.
 #include "common.h"
 #include "../../include/rsis_hip.h"
+#include "launchers.h"
 #include <stdlib.h>
-
-// launchers implemented in the other translation units
-int rsis_launch_conv_igemm(ConvArgs& a, int ks, bool dgrad, int epi, int force_tile, hipStream_t st);
-int rsis_launch_conv_wgrad(WgradArgs& a, int ks, hipStream_t st);
-int rsis_launch_conv3x3_direct(ConvArgs& a, int epi, int force_variant, hipStream_t st);
-int rsis_launch_conv_wino(const float* x, const void* U, const float* bias, const float* addend, float* y, int B, int C, int Cout, int H, int W,
-                          hipStream_t st, int precise);
-int rsis_launch_conv_wino_group(int n, const float* const* x, const void* const* U, float* const* y, float* const* y1, const int* B, const int* C,
-                                const int* Cout, const int* C0, const int* H, const int* W, hipStream_t st);
-int rsis_launch_convlstm_direct_group(ConvArgs* jobs, int n, const int* force_variant, hipStream_t st);
-int rsis_launch_conv3x3_direct_group_plain(ConvArgs* jobs, int n, const int* force_variant, hipStream_t st);
-int rsis_l_lstm_bwd_group(const void* const*, const int*, int, hipStream_t);
-int rsis_launch_conv_bf16(ConvArgs& a, int ks, int epi, int force_variant, hipStream_t st);
-int rsis_launch_conv_blk(ConvArgs& a, int ks, int variant, hipStream_t st);
-int rsis_l_blk_from_nchw(const float*, void*, int, int, int, hipStream_t);
-int rsis_l_blk_to_nchw(const void*, float*, int, int, int, hipStream_t);
-long rsis_l_blk_bn_scratch(int);
-int rsis_l_blk_bn_fwd(const void*, const void*, void*, double*, const float*, const float*, float*, float*, float*, float*, int, int, int, float,
-                      float, int, int, hipStream_t);
-int rsis_l_blk_bn_bwd(const void*, const void*, const void*, double*, const float*, const float*, const float*, const float*, void*, void*,
-                      float*, float*, int, int, int, int, int, hipStream_t);
-int rsis_l_blk_subsample(const void*, void*, long, int, int, int, int, int, hipStream_t);
-int rsis_l_blk_upscatter(const void*, void*, long, int, int, int, int, int, hipStream_t);
-bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks);
-int rsis_launch_conv_wgrad_bf16(const WgradArgs& w, int ks, hipStream_t st);
-int rsis_launch_conv_wgrad_bf16_group(const WgradArgs* w, int n, int ks, hipStream_t st);
-bool rsis_wgrad_tiled_supported(const WgradArgs& w, int ks);
-int rsis_launch_conv_wgrad_tiled(const WgradArgs& w, int ks, hipStream_t st);
-int rsis_launch_conv_wgrad_tiled_group(const WgradArgs* w, int n, int ks, hipStream_t st);
-bool rsis_c1_supported(int Cin);
-int rsis_l_c1_fwd(const float*, const float*, int, const float*, float*, int, int, int, int, int, hipStream_t);
-int rsis_l_c1_dgrad(const float*, const float*, int, float*, int, int, int, int, int, hipStream_t);
-int rsis_l_c1_wgrad(const float*, const float*, float*, float*, int, int, int, int, int, hipStream_t);
-int rsis_l_sum_leading(const float*, float*, int, long, hipStream_t);
-int rsis_launch_conv_blk_dec(BlkConvJob*, int, int, const int*, hipStream_t);
-int rsis_l_blk_upsample_fwd(const BlkResizeJob*, int, hipStream_t);
-int rsis_l_blk_upsample_bwd(const BlkResizeJob*, int, hipStream_t);
-int rsis_l_blk_lstm_bwd(const BlkLstmBwdJob*, int, hipStream_t);
-int rsis_l_blk_sum_leading(const void*, void*, int, long, hipStream_t);
-int rsis_l_blk_channel_sum(const void*, float*, int, int, int, int, hipStream_t);
-int rsis_l_blk_c1_fwd(const void*, const float*, const float*, float*, int, int, int, int, hipStream_t);
-int rsis_l_blk_c1_dgrad(const float*, const float*, void*, int, int, int, int, hipStream_t);
-int rsis_l_blk_c1_wgrad(const float*, const void*, float*, float*, int, int, int, int, hipStream_t);
-int rsis_l_pack(int, const float*, void*, int, int, int, int, const int*, const int*, int, int, int, hipStream_t);
-
-int rsis_l_lstm_bwd(const float*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*, int, int, int,
-                    hipStream_t);
-int rsis_l_upsample_fwd(const float*, float*, long, int, int, int, int, hipStream_t);
-int rsis_l_upsample_bwd(const float*, float*, long, int, int, int, int, const float*, const int*, hipStream_t);
-int rsis_l_gmax_fwd(const float*, float*, int*, long, int, hipStream_t);
-int rsis_l_gmax_bwd(const float*, const int*, float*, long, int, hipStream_t);
-int rsis_l_bn_fwd(const float*, const float*, float*, unsigned char*, double*, const float*, const float*, float*, float*, float*, float*,
-                  int, int, int, float, float, int, int, hipStream_t);
-int rsis_l_bn_bwd(const float*, const float*, const float*, const unsigned char*, const float*, const float*, const float*, double*,
-                  float*, float*, float*, float*, int, int, int, int, float, hipStream_t);
-int rsis_l_maxpool_fwd(const float*, float*, unsigned char*, long, int, int, int, int, hipStream_t);
-int rsis_l_subsample(const float*, float*, long, int, int, int, int, int, hipStream_t);
-int rsis_l_maxpool_bwd(const float*, const unsigned char*, float*, long, int, int, int, int, int, hipStream_t);
-int rsis_l_channel_sum(const float*, float*, int, int, int, int, hipStream_t);
-int rsis_l_adam(float*, const float*, float*, float*, long, float, float, float, float, float, int, float, const int*, hipStream_t);
-int rsis_l_flat_rule(int, float*, const float*, float*, long, float, float, float, float, float, hipStream_t);
-int rsis_l_assign(const float*, long long*, int, int, int, hipStream_t);
-int rsis_l_gmax_bwd_add(const float*, const int*, float*, long, int, hipStream_t);
-int rsis_l_pack_batch(const rsis_pack_job*, int, int, hipStream_t);
-int rsis_l_pack_blocks(int mode, int krows, int ldw, int ks);
-int rsis_l_affine_nearest(const float*, float*, const float*, int, int, int, int, int, hipStream_t);
-long rsis_l_targets_work_ints(int);
-int rsis_l_targets_from_maps(const int*, const int*, int, int, int, int, float*, long long*, float*, float*, int*, hipStream_t);
-long rsis_l_instance_maps_work_ints(int);
-int rsis_l_instance_maps(const int*, const int*, int, int, int, int, int*, int*, int*, hipStream_t);
-int rsis_l_palette_to_ids(const unsigned char*, long, const unsigned char*, int, unsigned char*, hipStream_t);
-int rsis_l_idmap_rle_encode(const unsigned char*, int, int, const int*, int, unsigned int*, int, int*, hipStream_t);
-int rsis_l_mask_resize_threshold(const float*, int, int, int, const unsigned char*, float, unsigned char*, unsigned char*, unsigned int*,
-                                 int, int, hipStream_t);
-int rsis_l_rle_encode(const unsigned char*, int, long, unsigned int*, int, int*, hipStream_t);
-int rsis_l_rle_to_string(const unsigned int*, int, char*, int);
-int rsis_l_largest_component(const unsigned char*, unsigned char*, int*, int*, int*, int, int, int, hipStream_t);
-int rsis_l_overlay_moments(const unsigned char*, int, const int*, int, int, int, unsigned long long*, hipStream_t);
-int rsis_l_overlay_masks(const unsigned char*, const unsigned char*, int, const int*, const unsigned char*, int, float, unsigned char*, int, int,
-                         hipStream_t);
-int rsis_l_mask_pack_bits(const unsigned char*, int, long, unsigned long long*, long, unsigned int*, hipStream_t);
-int rsis_l_rle_to_bits(const unsigned int*, long, const long long*, int, unsigned int*, unsigned long long*, long, unsigned int*, hipStream_t);
-long rsis_l_mask_intersect_blocks(long, long, long);
-int rsis_l_mask_intersect_batch(const unsigned long long*, long, const long long*, int, int, unsigned int*, long, hipStream_t);
-int rsis_l_coco_iou_batch(const long long*, int, const unsigned int*, long, const int*, const unsigned int*, long, const int*, const unsigned int*,
-                          const int*, long, double*, long, hipStream_t);
-int rsis_l_coco_match_batch(const long long*, int, const double*, long, const int*, const int*, long, const double*, long, const double*, int,
-                            const double*, int, int*, int*, long, int*, long, hipStream_t);
-int rsis_l_rle_from_string(const char*, unsigned int*, int);
-long rsis_l_label_contingency_blocks(long);
-int rsis_l_label_contingency_batch(const unsigned char*, long, const long long*, int, int, unsigned int*, long, hipStream_t);
-int rsis_l_label_scores_batch(const unsigned int*, long, const long long*, int, double*, hipStream_t);
-long rsis_l_inst_overlap_blocks(long, long);
-int rsis_l_inst_presence_batch(const unsigned char*, long, const long long*, int, int, unsigned char*, long, hipStream_t);
-int rsis_l_inst_overlap_batch(const unsigned char*, long, const long long*, int, int, const unsigned short*, long, const unsigned long long*, long,
-                              unsigned int*, long, hipStream_t);
-int rsis_l_heads_fwd(const float* const*, const int*, int, int, const float*, const float*, int, const float*, const float*, float*, float*,
-                     hipStream_t, const unsigned long long* const* keys = nullptr, float* const* side_out = nullptr, int* const* arg_out = nullptr);
-int rsis_l_heads_bwd(const float* const*, const int*, int, int, const float*, int, const float*, const float*, const float*, const float*,
-                     float* const*, float*, float*, float*, float*, hipStream_t);
-int rsis_l_loss_tail(const float*, const long long*, const float*, const float*, const float*, const float*, const float*, int, int, float,
-                     float, float, float, float*, float*, float*, float*, const float*, hipStream_t);
-int rsis_l_softiou_sums(const float*, const float*, float*, int, int, int, long, hipStream_t);
-int rsis_l_softiou_bwd(const float*, const float*, const long long*, int, const float*, const float*, float*, int, int, int, long,
-                       hipStream_t);
 
 static inline int krows_of(int C, int ks) { return rsis_roundup(C * ks * ks, RSIS_KPAD); }
 static inline int log2i(int s) { int l = 0; while ((1 << l) < s) ++l; return l; }
@@ -121,11 +17,13 @@ static inline bool use_direct_f2(int ks, int stride, int pad) {
   return on && use_direct_s2(ks, stride, pad);
 }
 static inline bool use_direct_fwd(int ks, int stride, int pad) { return use_direct(ks, stride, pad) || use_direct_f2(ks, stride, pad); }
-static inline int direct_rows(int nseg, const int* Cseg) {
+// reduction chunks of ck channels over a concat of channel segments (a chunk never straddles two segments: each tail is zero-padded)
+static inline int seg_chunks(int nseg, const int* Cseg, int ck) {
   int q = 0;
-  for (int s = 0; s < nseg; ++s) q += (Cseg[s] + RSIS_CK - 1) / RSIS_CK;
-  return q * RSIS_CK * 9;
+  for (int s = 0; s < nseg; ++s) q += (Cseg[s] + ck - 1) / ck;
+  return q;
 }
+static inline int direct_rows(int nseg, const int* Cseg) { return seg_chunks(nseg, Cseg, RSIS_CK) * RSIS_CK * 9; }
 // bf16 kernels (conv_bf16.hip): 3x3 / s1 / p1 and 1x1 / p0 (a strided 1x1 runs as its stride-1 form on a sub-sampled input)
 // -- convs with ONE output channel (conv_out) keep their HBM-bound vector kernels (conv_c1.hip)
 static inline bool bf16_geom(int ks, int stride, int pad, int Cout) {
@@ -134,7 +32,6 @@ static inline bool bf16_geom(int ks, int stride, int pad, int Cout) {
 static inline bool use_bf16(int dtype, int ks, int stride, int pad, int Cout) {
   return dtype == RSIS_DTYPE_BF16 && bf16_geom(ks, stride, pad, Cout);
 }
-static inline int bf16_ckb(int ks) { return ks == 1 ? RSIS_CKB1 : RSIS_CKB3; }
 // -- RSIS_DTYPE_F32_WINO: Winograd F(2x2, 3x3) on the f32 MFMA (conv_wino.hip) for 3x3 / stride 1 / pad 1 convs with ONE source covering
 //    all input channels, both channel counts multiples of 32 (forward tiles 32 output channels over 8-channel chunks, the data gradient
 //    swaps the roles); anything else under that dtype is plain RSIS_DTYPE_F32
@@ -151,10 +48,8 @@ static inline bool use_wino(int dtype, int ks, int stride, int pad, int Cin, int
 }
 // cell rows of a bf16 packed copy whose reduction axis is the concat of nseg channel segments
 static inline int bf16_rows(int ks, int nseg, const int* Cseg) {
-  const int ckb = bf16_ckb(ks);
-  int q = 0;
-  for (int s = 0; s < nseg; ++s) q += (Cseg[s] + ckb - 1) / ckb;
-  return q * ks * ks * (ckb / 8);
+  const int ckb = bf16_ckb(ks * ks);
+  return seg_chunks(nseg, Cseg, ckb) * ks * ks * (ckb / 8);
 }
 // ---- bit-reproducible mode (rsis_set_deterministic; initial value from RSIS_DETERMINISTIC=1) ----
 static int g_deterministic = -1;
@@ -167,6 +62,20 @@ static inline bool conv_splitk_ok() {
   static const bool env_ok = !(getenv("RSIS_CONV_SPLITK") && getenv("RSIS_CONV_SPLITK")[0] == '0');
   return env_ok && !rsis_deterministic();
 }
+// ... and its geometric test, for deep-K 3x3 convs on tiny maps (sk5: 2048 x 9 deep on 8 x 8; the gates of ConvLSTM level 0): from
+// min_chunks reduction chunks on, while the unsplit grid -- pixel tiles x 64-row blocks -- stays below 160 blocks
+static inline bool splitk_geom(int B, int H, int W, int rows, int nq, int min_chunks) {
+  const long px_tiles = (long)B * rsis_cdiv(H, 8) * rsis_cdiv(W, W <= 8 ? 8 : 16);
+  return nq >= min_chunks && px_tiles * rsis_cdiv(rows, 64) < 160;
+}
+// zero every destination of a conv: the split-K atomics and the strided 1x1 scatter write into zeroed tensors
+static int zero_dsts(const ConvArgs& a, hipStream_t st) {
+  for (int i = 0; i < a.ndst; ++i)
+    if (rsis_zero_async(a.dst[i], sizeof(float) * (size_t)a.B * a.Cd[i] * a.oH * a.oW, st) != RSIS_OK) return RSIS_ERR_LAUNCH;
+  return RSIS_OK;
+}
+// a.ksplit = 0 tells the launcher "split allowed, every destination is zeroed": it decides whether and how far to split
+static int splitk_enable(ConvArgs& a, hipStream_t st) { a.ksplit = 0; return zero_dsts(a, st); }
 static inline int direct_variant(int tile) { const int v = tile % 10; return (tile > 0 && v >= 1 && v <= 9) ? v : 0; }
 
 extern "C" {
@@ -195,30 +104,62 @@ int rsis_conv_uses_wino(int ks, int stride, int pad, int Cin, int Cout, int nseg
   return wino_geom(ks, stride, pad, Cin, Cout, nseg, lstm_hid) ? 1 : 0;
 }
 
+// ---- the packed layout of a weight copy: ONE rule.  The size queries, the single-shot packs and the jobs of the batched repack all
+// derive from pack_plan() and keep no layout logic of their own; the kernel that reads a layout is chosen with the same predicates in
+// conv2d_fwd_impl / rsis_conv2d_dgrad / lstm_fill ----
+struct PackPlan { int status; PackMode mode; int krows; int ldw; long bytes; };     // status: RSIS_OK or RSIS_ERR_UNSUPPORTED
+static PackPlan pack_plan(bool dgrad, int dtype, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg, const int* Coff,
+                          int lstm_hid) {
+  PackPlan p = {RSIS_OK, PACK_IGEMM_FWD, 0, 0, 0};
+  int csum = 0;
+  for (int s = 0; s < nseg; ++s) csum += Cseg[s];
+  p.ldw = rsis_roundup(dgrad ? csum : Cout, RSIS_LDW_ALIGN);
+  // bf16 ConvLSTM gates: 3x3 only, either direction (the fused-cell epilogue of conv_bf16.hip; see lstm_fill)
+  if (lstm_hid > 0 && dtype == RSIS_DTYPE_BF16 && ks != 3) { p.status = RSIS_ERR_UNSUPPORTED; return p; }
+  if (dtype == RSIS_DTYPE_F32_WINO && (dgrad ? wino_geom_dgrad(ks, stride, pad, csum, Cout) : wino_geom(ks, stride, pad, csum, Cout, nseg, lstm_hid))) {
+    // the forward copy is the whole weight: a channel subset is refused
+    if (!dgrad && (csum != Ctot || (Coff && Coff[0] != 0))) { p.status = RSIS_ERR_UNSUPPORTED; return p; }
+    p.mode = dgrad ? PACK_WINO_DGRAD : PACK_WINO_FWD;
+    p.krows = dgrad ? (csum / 32) * (Cout / 8) : (Cout / 32) * (csum / 8);      // (32 outputs x 8 reduction channels) blocks, not rows
+    p.bytes = (long)p.krows * 32 * 8 * 16 * 4;
+    return p;
+  }
+  long cell = 4;                      // bytes per row and column: one f32, or a 16-byte cell of 8 bf16 reduction channels
+  if (use_bf16(dtype, ks, stride, pad, Cout)) {
+    p.mode = dgrad ? PACK_BF16_DGRAD : PACK_BF16_FWD;
+    p.krows = dgrad ? bf16_rows(ks, 1, &Cout) : bf16_rows(ks, nseg, Cseg);
+    cell = 16;
+  } else if (dgrad ? use_direct(ks, stride, pad) : use_direct_fwd(ks, stride, pad)) {
+    p.mode = dgrad ? PACK_DIRECT_DGRAD : PACK_DIRECT_FWD;
+    p.krows = dgrad ? direct_rows(1, &Cout) : direct_rows(nseg, Cseg);
+  } else if (dgrad && use_direct_s2(ks, stride, pad) && nseg == 1) {      // (the parity-class kernel writes one destination)
+    p.mode = PACK_DIRECT_DGRAD_S2;
+    p.krows = direct_rows(1, &Cout);
+  } else {
+    p.mode = dgrad ? PACK_IGEMM_DGRAD : PACK_IGEMM_FWD;
+    p.krows = krows_of(dgrad ? Cout : csum, ks);
+  }
+  p.bytes = (long)p.krows * p.ldw * cell;
+  return p;
+}
+
 long rsis_conv_packed_bytes_fwd(int dtype, int Cout, int ks, int stride, int pad, int nseg, const int* Cseg) {
   if (nseg < 1 || nseg > RSIS_MAX_SRC || !Cseg) return -1;
-  const long ldw = rsis_roundup(Cout, RSIS_LDW_ALIGN);
-  if (use_wino(dtype, ks, stride, pad, Cseg[0], Cout, nseg, 0)) return (long)Cout * Cseg[0] * 16 * 4;
-  if (use_bf16(dtype, ks, stride, pad, Cout)) return (long)bf16_rows(ks, nseg, Cseg) * ldw * 16;
-  if (use_direct_fwd(ks, stride, pad)) return (long)direct_rows(nseg, Cseg) * ldw * 4;
-  int c = 0;
-  for (int s = 0; s < nseg; ++s) c += Cseg[s];
-  return (long)krows_of(c, ks) * ldw * 4;
+  int csum = 0;
+  for (int s = 0; s < nseg; ++s) csum += Cseg[s];
+  return pack_plan(false, dtype, Cout, csum, ks, stride, pad, nseg, Cseg, nullptr, 0).bytes;
 }
 
 long rsis_conv_packed_bytes_dgrad(int dtype, int Cout, int ks, int stride, int pad, int c_count) {
-  const long ldw = rsis_roundup(c_count, RSIS_LDW_ALIGN);
-  if (dtype == RSIS_DTYPE_F32_WINO && wino_geom_dgrad(ks, stride, pad, c_count, Cout)) return (long)Cout * c_count * 16 * 4;
-  if (use_bf16(dtype, ks, stride, pad, Cout)) return (long)bf16_rows(ks, 1, &Cout) * ldw * 16;
-  if (use_direct(ks, stride, pad)) return (long)direct_rows(1, &Cout) * ldw * 4;
-  if (use_direct_s2(ks, stride, pad)) {      // direct layout for one destination, implicit-GEMM layout for several: room for either
-    const long a = (long)direct_rows(1, &Cout) * ldw, b = (long)krows_of(Cout, ks) * ldw;
-    return (a > b ? a : b) * 4;
-  }
-  return (long)krows_of(Cout, ks) * ldw * 4;
+  // no segment list here: room for the plan of one destination and for that of several (they differ for 3x3 / stride 2 only)
+  const int one[1] = {c_count}, two[2] = {c_count, 0};
+  const long a = pack_plan(true, dtype, Cout, c_count, ks, stride, pad, 1, one, nullptr, 0).bytes;
+  const long b = pack_plan(true, dtype, Cout, c_count, ks, stride, pad, 2, two, nullptr, 0).bytes;
+  return a > b ? a : b;
 }
 
-static int check_segments(int Ctot, int nseg, const int* Cseg, const int* Coff) {
+// argument checks of the calls that have a weight to pack (the pack kernels index the reference weight with 32-bit arithmetic)
+static int pack_args_check(int Cout, int Ctot, int ks, int nseg, const int* Cseg, const int* Coff, int lstm_hid) {
   if (nseg < 1 || nseg > RSIS_MAX_SRC || !Cseg) return RSIS_ERR_ARG;
   int base = 0;
   for (int s = 0; s < nseg; ++s) {
@@ -226,47 +167,39 @@ static int check_segments(int Ctot, int nseg, const int* Cseg, const int* Coff) 
     if (Cseg[s] < 1 || off < 0 || off + Cseg[s] > Ctot) return RSIS_ERR_ARG;
     base += Cseg[s];
   }
-  return RSIS_OK;
+  if (Cout < 1 || ks < 1 || (long)Cout * Ctot * ks * ks >= (1L << 31)) return RSIS_ERR_ARG;
+  return (lstm_hid > 0 && Cout != 4 * lstm_hid) ? RSIS_ERR_ARG : RSIS_OK;
 }
 
-// the pack kernels index the reference weight with 32-bit arithmetic
-static inline bool weight_too_big(int Cout, int Ctot, int ks) { return Cout < 1 || ks < 1 || (long)Cout * Ctot * ks * ks >= (1L << 31); }
-
+static int pack_one(bool dgrad, const float* W, void* out, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg,
+                    const int* Coff, int lstm_hid, int dtype, void* stream) {
+  if (!W || !out || pack_args_check(Cout, Ctot, ks, nseg, Cseg, Coff, lstm_hid)) return RSIS_ERR_ARG;
+  const PackPlan p = pack_plan(dgrad, dtype, Cout, Ctot, ks, stride, pad, nseg, Cseg, Coff, lstm_hid);
+  if (p.status) return p.status;
+  return rsis_l_pack(p.mode, W, out, Cout, Ctot, ks, nseg, Cseg, Coff, p.ldw, p.krows, lstm_hid, (hipStream_t)stream);
+}
 int rsis_conv_pack_fwd(const float* W, void* Wp, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg,
                        const int* Coff, int lstm_hid, int dtype, void* stream) {
-  if (!W || !Wp || check_segments(Ctot, nseg, Cseg, Coff) || weight_too_big(Cout, Ctot, ks)) return RSIS_ERR_ARG;
-  if (lstm_hid > 0 && Cout != 4 * lstm_hid) return RSIS_ERR_ARG;
-  if (lstm_hid > 0 && dtype == RSIS_DTYPE_BF16 && ks != 3) return RSIS_ERR_UNSUPPORTED;     // (see rsis_convlstm_fwd)
-  const int ldw = rsis_roundup(Cout, RSIS_LDW_ALIGN);
-  int csum = 0;
-  for (int s = 0; s < nseg; ++s) csum += Cseg[s];
-  if (use_wino(dtype, ks, stride, pad, csum, Cout, nseg, lstm_hid) && csum == Ctot && (!Coff || Coff[0] == 0))
-    return rsis_l_pack(7, W, Wp, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, (Cout / 32) * (Ctot / 8), 0, (hipStream_t)stream);
-  if (dtype == RSIS_DTYPE_F32_WINO && wino_geom(ks, stride, pad, csum, Cout, nseg, lstm_hid)) return RSIS_ERR_UNSUPPORTED;   // (a channel subset)
-  if (use_bf16(dtype, ks, stride, pad, Cout))
-    return rsis_l_pack(5, W, Wp, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, bf16_rows(ks, nseg, Cseg), lstm_hid, (hipStream_t)stream);
-  if (use_direct_fwd(ks, stride, pad))
-    return rsis_l_pack(2, W, Wp, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, direct_rows(nseg, Cseg), lstm_hid, (hipStream_t)stream);
-  return rsis_l_pack(0, W, Wp, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, krows_of(csum, ks), lstm_hid, (hipStream_t)stream);
+  return pack_one(false, W, Wp, Cout, Ctot, ks, stride, pad, nseg, Cseg, Coff, lstm_hid, dtype, stream);
 }
-
 int rsis_conv_pack_dgrad(const float* W, void* Wd, int Cout, int Ctot, int ks, int stride, int pad, int nseg, const int* Cseg,
                          const int* Coff, int lstm_hid, int dtype, void* stream) {
-  if (!W || !Wd || check_segments(Ctot, nseg, Cseg, Coff) || weight_too_big(Cout, Ctot, ks)) return RSIS_ERR_ARG;
-  if (lstm_hid > 0 && Cout != 4 * lstm_hid) return RSIS_ERR_ARG;
-  int csum = 0;
-  for (int s = 0; s < nseg; ++s) csum += Cseg[s];
-  const int ldw = rsis_roundup(csum, RSIS_LDW_ALIGN);
-  if (dtype == RSIS_DTYPE_F32_WINO && wino_geom_dgrad(ks, stride, pad, csum, Cout))
-    return rsis_l_pack(8, W, Wd, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, (csum / 32) * (Cout / 8), lstm_hid, (hipStream_t)stream);
-  if (use_bf16(dtype, ks, stride, pad, Cout))
-    return rsis_l_pack(6, W, Wd, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, bf16_rows(ks, 1, &Cout), lstm_hid, (hipStream_t)stream);
-  if (use_direct(ks, stride, pad))
-    return rsis_l_pack(3, W, Wd, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, direct_rows(1, &Cout), lstm_hid, (hipStream_t)stream);
-  if (use_direct_s2(ks, stride, pad) && nseg == 1)      // (the parity-class kernel writes one destination)
-    return rsis_l_pack(4, W, Wd, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, direct_rows(1, &Cout), lstm_hid, (hipStream_t)stream);
-  return rsis_l_pack(1, W, Wd, Cout, Ctot, ks, nseg, Cseg, Coff, ldw, krows_of(Cout, ks), lstm_hid, (hipStream_t)stream);
+  return pack_one(true, W, Wd, Cout, Ctot, ks, stride, pad, nseg, Cseg, Coff, lstm_hid, dtype, stream);
 }
+
+int rsis_conv_pack_job_fill(rsis_pack_job* j) {
+  if (!j || pack_args_check(j->Cout, j->Ctot, j->ks, j->nseg, j->Cseg, j->Coff, j->lstm_hid)) return -1;
+  const PackPlan p = pack_plan(j->dgrad != 0, j->dtype, j->Cout, j->Ctot, j->ks, j->stride, j->pad, j->nseg, j->Cseg, j->Coff, j->lstm_hid);
+  if (p.status) return -1;
+  j->imode = p.mode; j->krows = p.krows; j->ldw = p.ldw;
+  return rsis_l_pack_blocks(p.mode, p.krows, p.ldw, j->ks);
+}
+
+int rsis_conv_pack_batch(const rsis_pack_job* jobs_dev, int njobs, int total_blocks, void* stream) {
+  if (!jobs_dev || njobs < 1 || total_blocks < 1) return RSIS_ERR_ARG;
+  return rsis_l_pack_batch(jobs_dev, njobs, total_blocks, (hipStream_t)stream);
+}
+
 
 int rsis_conv_out_wgrad(const float* dy, const float* x, float* dW, float* db, int B, int Cin, int H, int W, void* stream) {
   if (!dy || !x || !dW || B < 1) return RSIS_ERR_ARG;
@@ -335,41 +268,6 @@ int rsis_idmap_rle_encode(const unsigned char* idmap, int h, int w, const int* i
   return rsis_l_idmap_rle_encode(idmap, h, w, ids, k, counts, cap, nruns, (hipStream_t)stream);
 }
 
-int rsis_conv_pack_job_fill(rsis_pack_job* j) {
-  if (!j || check_segments(j->Ctot, j->nseg, j->Cseg, j->Coff) || weight_too_big(j->Cout, j->Ctot, j->ks)) return -1;
-  if (j->lstm_hid > 0 && j->Cout != 4 * j->lstm_hid) return -1;
-  if (j->lstm_hid > 0 && j->dtype == RSIS_DTYPE_BF16 && j->ks != 3) return -1;                  // (see rsis_convlstm_fwd)
-  int csum = 0;
-  for (int s = 0; s < j->nseg; ++s) csum += j->Cseg[s];
-  const bool wino = j->dgrad ? (j->dtype == RSIS_DTYPE_F32_WINO && wino_geom_dgrad(j->ks, j->stride, j->pad, csum, j->Cout))
-                             : use_wino(j->dtype, j->ks, j->stride, j->pad, csum, j->Cout, j->nseg, j->lstm_hid);
-  if (wino && !j->dgrad && (csum != j->Ctot || j->Coff[0] != 0)) return -1;
-  if (wino) {
-    j->ldw = rsis_roundup(j->dgrad ? csum : j->Cout, RSIS_LDW_ALIGN);
-    j->imode = j->dgrad ? 8 : 7;
-    j->krows = j->dgrad ? (csum / 32) * (j->Cout / 8) : (j->Cout / 32) * (csum / 8);
-    return rsis_l_pack_blocks(j->imode, j->krows, j->ldw, j->ks);
-  }
-  if (!j->dgrad) {
-    j->ldw = rsis_roundup(j->Cout, RSIS_LDW_ALIGN);
-    if (use_bf16(j->dtype, j->ks, j->stride, j->pad, j->Cout)) { j->imode = 5; j->krows = bf16_rows(j->ks, j->nseg, j->Cseg); }
-    else if (use_direct_fwd(j->ks, j->stride, j->pad)) { j->imode = 2; j->krows = direct_rows(j->nseg, j->Cseg); }
-    else { j->imode = 0; j->krows = krows_of(csum, j->ks); }
-  } else {
-    j->ldw = rsis_roundup(csum, RSIS_LDW_ALIGN);
-    if (use_bf16(j->dtype, j->ks, j->stride, j->pad, j->Cout)) { j->imode = 6; j->krows = bf16_rows(j->ks, 1, &j->Cout); }
-    else if (use_direct(j->ks, j->stride, j->pad)) { j->imode = 3; j->krows = direct_rows(1, &j->Cout); }
-    else if (use_direct_s2(j->ks, j->stride, j->pad) && j->nseg == 1) { j->imode = 4; j->krows = direct_rows(1, &j->Cout); }
-    else { j->imode = 1; j->krows = krows_of(j->Cout, j->ks); }
-  }
-  return rsis_l_pack_blocks(j->imode, j->krows, j->ldw, j->ks);
-}
-
-int rsis_conv_pack_batch(const rsis_pack_job* jobs_dev, int njobs, int total_blocks, void* stream) {
-  if (!jobs_dev || njobs < 1 || total_blocks < 1) return RSIS_ERR_ARG;
-  return rsis_l_pack_batch(jobs_dev, njobs, total_blocks, (hipStream_t)stream);
-}
-
 static int fill_sources(ConvArgs& a, const float* const* src, const int* Csrc, int nsrc, int ks, bool allow_empty = false) {
   if (nsrc < (allow_empty ? 0 : 1) || nsrc > RSIS_MAX_SRC || (nsrc > 0 && (!src || !Csrc))) return RSIS_ERR_ARG;
   a.nsrc = nsrc;
@@ -415,31 +313,18 @@ static int conv2d_fwd_impl(const float* const* src, const int* Csrc, int nsrc, i
   if (use_bf16(dtype, ks, stride, pad, Cout)) {
     if (stride != 1) return RSIS_ERR_UNSUPPORTED;      // strided 1x1: run the stride-1 form on a sub-sampled input
     if (ks == 1 && nsrc != 1) return RSIS_ERR_UNSUPPORTED;
-    if (ks == 3) {     // deep-K convs on tiny maps (sk5): split over the channel chunks into a zeroed output
-      const bool splitk_ok = conv_splitk_ok();
-      int nq = 0;
-      for (int s = 0; s < nsrc; ++s) nq += (Csrc[s] + RSIS_CKB3 - 1) / RSIS_CKB3;
-      const long px_tiles = (long)B * rsis_cdiv(H, 8) * rsis_cdiv(W, W <= 8 ? 8 : 16);
-      if (allow_splitk && splitk_ok && !addend && nq >= 16 && px_tiles * rsis_cdiv(Cout, 64) < 160) {
-        if (rsis_zero_async(out, sizeof(float) * (size_t)B * Cout * Ho * Wo, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
-        a.ksplit = 0;
-      }
-    }
+    // deep-K 3x3 convs on tiny maps (sk5): split over the channel chunks into a zeroed output
+    if (ks == 3 && allow_splitk && conv_splitk_ok() && !addend && splitk_geom(B, H, W, Cout, seg_chunks(a.nsrc, a.C, RSIS_CKB3), 16) &&
+        splitk_enable(a, (hipStream_t)stream))
+      return RSIS_ERR_LAUNCH;
     return rsis_launch_conv_bf16(a, ks, 0, direct_variant(tile), (hipStream_t)stream);
   }
   if (use_direct(ks, stride, pad) && Cout == 1 && nsrc == 1 && !addend && rsis_c1_supported(Csrc[0]) && W % 4 == 0)   // conv_out: HBM-bound VALU kernel
     return rsis_l_c1_fwd(src[0], (const float*)Wp, a.ldw, bias, out, B, Csrc[0], H, W, 1, (hipStream_t)stream);
   if (use_direct(ks, stride, pad)) {
-    // deep-K convs on tiny maps (sk5: 2048x9 deep, 64 blocks) are split over the channel chunks: zero the output here and let
-    // the launcher decide (a.ksplit = 0 means "split allowed, output is zeroed")
-    int nq = 0;
-    for (int s = 0; s < nsrc; ++s) nq += (Csrc[s] + RSIS_CK - 1) / RSIS_CK;
-    const long px_tiles = (long)B * rsis_cdiv(H, 8) * rsis_cdiv(W, W <= 8 ? 8 : 16);
-    const bool splitk_ok = conv_splitk_ok();   // A/B switch / deterministic mode
-    if (allow_splitk && splitk_ok && nq >= 32 && px_tiles * rsis_cdiv(Cout, 64) < 160) {
-      if (rsis_zero_async(out, sizeof(float) * (size_t)B * Cout * Ho * Wo, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
-      a.ksplit = 0;
-    }
+    // deep-K convs on tiny maps (sk5: 2048x9 deep, 64 blocks) are split over the channel chunks (an addend does not stand in the way here)
+    if (allow_splitk && conv_splitk_ok() && splitk_geom(B, H, W, Cout, seg_chunks(a.nsrc, a.C, RSIS_CK), 32) && splitk_enable(a, (hipStream_t)stream))
+      return RSIS_ERR_LAUNCH;
     return rsis_launch_conv3x3_direct(a, 0, direct_variant(tile), (hipStream_t)stream);
   }
   if (use_direct_f2(ks, stride, pad))        // 3x3 / stride 2 forward: the direct kernel on a (2T+1)^2 patch (EPI_F2 = 3)
@@ -461,6 +346,25 @@ int rsis_conv2d_fwd_bn_eval(const float* const* src, const int* Csrc, int nsrc, 
   return conv2d_fwd_impl(src, Csrc, nsrc, B, H, W, Wp, Cout, ks, stride, pad, bias, addend, out, Ho, Wo, tile % 100, dtype, stream, &bn);
 }
 
+// ConvArgs of one data gradient: dy plays the gathered tensor, the destinations split the ctot (-> a.Cout) leading channels of the
+// packed copy's Cin_packed columns.  The callers have checked the pointers and ndst.
+static int dgrad_fill(ConvArgs& a, const float* dy, int B, int Cout, int Hy, int Wy, const void* Wd, int Cin_packed, int ks, int stride, int pad,
+                      float* const* dx, const int* Cdx, int ndst, int Hx, int Wx, const float* addend) {
+  a = ConvArgs{};
+  const float* srcs[1] = {dy};
+  const int cs[1] = {Cout};
+  const int rc = fill_sources(a, srcs, cs, 1, ks);
+  if (rc) return rc;
+  int ctot = 0;
+  for (int i = 0; i < ndst; ++i) { if (!dx[i] || Cdx[i] < 1) return RSIS_ERR_ARG; a.dst[i] = dx[i]; a.Cd[i] = Cdx[i]; ctot += Cdx[i]; }
+  if (ctot > Cin_packed) return RSIS_ERR_ARG;
+  a.ndst = ndst;
+  a.B = B; a.H = Hy; a.W = Wy; a.Ho = Hx; a.Wo = Wx; a.stride = stride; a.pad = pad; a.sshift = log2i(stride);
+  a.ostride = 1; a.oH = Hx; a.oW = Wx; a.ksplit = 1;
+  a.wp = (const float*)Wd; a.ldw = rsis_roundup(Cin_packed, RSIS_LDW_ALIGN); a.Cout = ctot; a.bias = nullptr; a.addend = addend;
+  return RSIS_OK;
+}
+
 int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const void* Wd, int Cin_packed, int ks, int stride,
                       int pad, float* const* dx, const int* Cdx, int ndst, int Hx, int Wx, const float* addend, int tile,
                       int dtype, void* stream) {
@@ -469,20 +373,12 @@ int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const vo
   const bool inplace = addend && ndst == 1 && stride > 1 && ks == 1 && pad == 0 && addend == dx[0];
   if (addend && !inplace && (ndst != 1 || stride != 1)) return RSIS_ERR_UNSUPPORTED;
   if (stride != 1 && stride != 2 && stride != 4) return RSIS_ERR_UNSUPPORTED;
-  ConvArgs a = {};
-  const float* srcs[1] = {dy};
-  const int cs[1] = {Cout};
-  int rc = fill_sources(a, srcs, cs, 1, ks);
+  ConvArgs a;
+  const int rc = dgrad_fill(a, dy, B, Cout, Hy, Wy, Wd, Cin_packed, ks, stride, pad, dx, Cdx, ndst, Hx, Wx, addend);
   if (rc) return rc;
-  int ctot = 0;
-  for (int i = 0; i < ndst; ++i) { if (!dx[i] || Cdx[i] < 1) return RSIS_ERR_ARG; a.dst[i] = dx[i]; a.Cd[i] = Cdx[i]; ctot += Cdx[i]; }
-  a.ndst = ndst;
-  a.B = B; a.H = Hy; a.W = Wy; a.Ho = Hx; a.Wo = Wx; a.stride = stride; a.pad = pad; a.sshift = log2i(stride);
-  if (ctot > Cin_packed) return RSIS_ERR_ARG;
-  a.ostride = 1; a.oH = Hx; a.oW = Wx; a.ksplit = 1;
-  a.wp = (const float*)Wd; a.ldw = rsis_roundup(Cin_packed, RSIS_LDW_ALIGN); a.Cout = ctot; a.bias = nullptr; a.addend = addend;
+  const int ctot = a.Cout;
   if (dtype == RSIS_DTYPE_F32_WINO && wino_geom_dgrad(ks, stride, pad, Cin_packed, Cout)) {
-    // the data gradient of a Winograd conv is the same kernel on the transposed, rotated weights (pack mode 8): dy plays the input.
+    // the data gradient of a Winograd conv is the same kernel on the transposed, rotated weights (PACK_WINO_DGRAD): dy plays the input.
     // One destination (any leading multiple of 32 channels of the concat) or two splitting it at a multiple of 32.
     if (ndst > 2 || ctot % 32 != 0 || Cdx[0] % 32 != 0 || Hx != Hy || Wx != Wy || (ndst == 2 && addend)) return RSIS_ERR_UNSUPPORTED;
     if (ndst == 1) return rsis_launch_conv_wino(dy, Wd, nullptr, addend, dx[0], B, Cout, ctot, Hy, Wy, (hipStream_t)stream, 0);
@@ -493,21 +389,14 @@ int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const vo
   if (use_bf16(dtype, ks, stride, pad, Cout)) {
     if (ks == 3) {
       if (Hx != Hy || Wx != Wy) return RSIS_ERR_ARG;
-      const bool splitk_ok = conv_splitk_ok();
-      const int nq = (Cout + RSIS_CKB3 - 1) / RSIS_CKB3;
-      const long px_tiles = (long)B * rsis_cdiv(Hx, 8) * rsis_cdiv(Wx, Wx <= 8 ? 8 : 16);
-      if (splitk_ok && !addend && nq >= 16 && px_tiles * rsis_cdiv(ctot, 64) < 160) {
-        for (int i = 0; i < ndst; ++i)
-          if (rsis_zero_async(dx[i], sizeof(float) * (size_t)B * Cdx[i] * Hx * Wx, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
-        a.ksplit = 0;
-      }
+      if (conv_splitk_ok() && !addend && splitk_geom(B, Hx, Wx, ctot, seg_chunks(a.nsrc, a.C, RSIS_CKB3), 16) && splitk_enable(a, (hipStream_t)stream))
+        return RSIS_ERR_LAUNCH;
       return rsis_launch_conv_bf16(a, 3, 0, direct_variant(tile), (hipStream_t)stream);
     }
     // 1x1: a GEMM over the dy grid; stride > 1 scatters its rows to every stride-th pixel of a zeroed (or, in place, the parked) dx
     if (stride > 1) {
       if (Hy != (Hx - 1) / stride + 1 || Wy != (Wx - 1) / stride + 1) return RSIS_ERR_ARG;
-      for (int i = 0; i < ndst && !inplace; ++i)
-        if (rsis_zero_async(dx[i], sizeof(float) * (size_t)B * Cdx[i] * Hx * Wx, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
+      if (!inplace && zero_dsts(a, (hipStream_t)stream)) return RSIS_ERR_LAUNCH;
       a.ostride = stride;
     } else if (Hx != Hy || Wx != Wy) return RSIS_ERR_ARG;
     a.Ho = Hy; a.Wo = Wy; a.stride = 1; a.sshift = 0;
@@ -517,16 +406,9 @@ int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const vo
     if (Hx != Hy || Wx != Wy) return RSIS_ERR_ARG;
     if (Cout == 1 && ndst == 1 && Cin_packed == Cdx[0] && rsis_c1_supported(Cdx[0]) && !addend)
       return rsis_l_c1_dgrad(dy, (const float*)Wd, a.ldw, dx[0], B, Cdx[0], Hx, Wx, 1, (hipStream_t)stream);
-    {  // deep-K data gradients on tiny maps (ConvLSTM level 0: 512 gate rows x 9 taps on 8x8): split over the channel chunks
-      const bool splitk_ok = conv_splitk_ok();
-      const int nq = (Cout + RSIS_CK - 1) / RSIS_CK;
-      const long px_tiles = (long)B * rsis_cdiv(Hx, 8) * rsis_cdiv(Wx, Wx <= 8 ? 8 : 16);
-      if (splitk_ok && !addend && nq >= 32 && px_tiles * rsis_cdiv(ctot, 64) < 160) {
-        for (int i = 0; i < ndst; ++i)
-          if (rsis_zero_async(dx[i], sizeof(float) * (size_t)B * Cdx[i] * Hx * Wx, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
-        a.ksplit = 0;
-      }
-    }
+    // deep-K data gradients on tiny maps (ConvLSTM level 0: 512 gate rows x 9 taps on 8x8): split over the channel chunks
+    if (conv_splitk_ok() && !addend && splitk_geom(B, Hx, Wx, ctot, seg_chunks(a.nsrc, a.C, RSIS_CK), 32) && splitk_enable(a, (hipStream_t)stream))
+      return RSIS_ERR_LAUNCH;
     return rsis_launch_conv3x3_direct(a, 0, direct_variant(tile), (hipStream_t)stream);
   }
   if (use_direct_s2(ks, stride, pad) && ndst == 1 && Cdx[0] == Cin_packed && Hy == (Hx + 1) / 2 && Wy == (Wx + 1) / 2) {
@@ -538,8 +420,7 @@ int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const vo
   if (ks == 1 && pad == 0 && stride > 1) {
     // 1x1 / stride-s data gradient: only the (s*ho, s*wo) input pixels receive a gradient -> zero dx, then run the plain
     // 1x1 GEMM over the dy grid and scatter its rows to those pixels (instead of gathering with 1/s^2 useful taps)
-    for (int i = 0; i < ndst && !inplace; ++i)
-      if (rsis_zero_async(dx[i], sizeof(float) * (size_t)B * Cdx[i] * Hx * Wx, (hipStream_t)stream) != RSIS_OK) return RSIS_ERR_LAUNCH;
+    if (!inplace && zero_dsts(a, (hipStream_t)stream)) return RSIS_ERR_LAUNCH;
     a.Ho = Hy; a.Wo = Wy; a.stride = 1; a.sshift = 0; a.ostride = stride;
     return rsis_launch_conv_igemm(a, ks, false, 0, tile, (hipStream_t)stream);
   }
@@ -860,8 +741,6 @@ int rsis_assign_min_cost(const float* scores, long long* perm, int B, int G, int
   return rsis_l_assign(scores, perm, B, G, T, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
 int rsis_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, void* stream) {
   if (!logits || !y || !S || B < 1 || T < 1 || G < 1 || T > 128 || G > 128 || N < 8 || N % 8 != 0) return RSIS_ERR_ARG;
   return rsis_l_softiou_sums(logits, y, S, B, T, G, N, (hipStream_t)stream);
@@ -1035,7 +914,6 @@ int rsis_loss_tail(const float* probs, const long long* y_class, const float* st
                           gout, (hipStream_t)stream);
 }
 
-
 // ---- the recurrent decoder on blk tensors (conv_blk_dec.hip, blk_dec.hip) ----
 int rsis_blk_conv3x3_batch(const rsis_blk_conv_job* jobs, int njobs, void* stream) {
   if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;
@@ -1183,17 +1061,9 @@ int rsis_conv2d_dgrad_batch(const rsis_dgrad_job* jobs, int njobs, void* stream)
                              q.dtype, stream);
       continue;
     }
-    ConvArgs a = {};
-    const float* srcs[1] = {q.dy};
-    const int cs[1] = {q.Cout};
-    rc = fill_sources(a, srcs, cs, 1, 3);
+    rc = dgrad_fill(grp[ng], q.dy, q.B, q.Cout, q.Hy, q.Wy, q.Wd, q.Cin_packed, q.ks, q.stride, q.pad, q.dx, q.Cdx, q.ndst, q.Hx, q.Wx, q.addend);
     if (rc) break;
-    for (int i = 0; i < q.ndst; ++i) { a.dst[i] = q.dx[i]; a.Cd[i] = q.Cdx[i]; }
-    a.ndst = q.ndst;
-    a.B = q.B; a.H = q.Hy; a.W = q.Wy; a.Ho = q.Hx; a.Wo = q.Wx; a.stride = 1; a.pad = 1; a.sshift = 0;
-    a.ostride = 1; a.oH = q.Hx; a.oW = q.Wx; a.ksplit = 1;
-    a.wp = (const float*)q.Wd; a.ldw = rsis_roundup(q.Cin_packed, RSIS_LDW_ALIGN); a.Cout = ctot; a.bias = nullptr; a.addend = nullptr;
-    force[ng] = direct_variant(q.tile); grp[ng++] = a;
+    force[ng++] = direct_variant(q.tile);
   }
   if (rc == RSIS_OK && nw > 0) rc = rsis_launch_conv_wino_group(nw, wx, wu, wy0, wy1, wb, wc, wco, wc0, wh, ww, (hipStream_t)stream);
   if (rc == RSIS_OK && ng == 1) rc = rsis_launch_conv3x3_direct(grp[0], 0, force[0], (hipStream_t)stream);
@@ -1202,12 +1072,6 @@ int rsis_conv2d_dgrad_batch(const rsis_dgrad_job* jobs, int njobs, void* stream)
 }
 
 // ---- upsample x2 (align corners) + conv_out as one op per direction (upconv_out.hip) ----
-bool rsis_upconv_supported(int C, int Hs, int Ws, int Ho, int Wo);
-int rsis_upconv_bwd_blocks(int T, int B, int Hs, int Ws);
-int rsis_l_upconv_fwd(const void* h, int h_blk, const float* w, const float* bias, float* out, int T, int B, int Hs, int Ws, int Ho, int Wo, hipStream_t st);
-int rsis_l_upconv_bwd(const float* dout, const void* h, int h_blk, const float* w, void* dh, float* dW, float* db, const float* dside, const int* arg,
-                      float* partial, int T, int B, int Hs, int Ws, int Ho, int Wo, hipStream_t st);
-extern "C" {
 int rsis_upconv_out_supported(int C, int Hs, int Ws, int Ho, int Wo) { return rsis_upconv_supported(C, Hs, Ws, Ho, Wo) ? 1 : 0; }
 int rsis_upconv_out_bwd_blocks(int T, int B, int Hs, int Ws) { return rsis_upconv_bwd_blocks(T, B, Hs, Ws); }
 int rsis_upconv_out_fwd(const void* h, int h_blk, const float* w, const float* bias, float* out, int T, int B, int C, int Hs, int Ws, int Ho, int Wo,
@@ -1222,4 +1086,4 @@ int rsis_upconv_out_bwd(const float* dout, const void* h, int h_blk, const float
   if (!rsis_upconv_supported(C, Hs, Ws, Ho, Wo)) return RSIS_ERR_UNSUPPORTED;
   return rsis_l_upconv_bwd(dout, h, h_blk, w, dh, dW, db, dside, arg, partial, T, B, Hs, Ws, Ho, Wo, (hipStream_t)stream);
 }
-}
+}  // extern "C"

@@ -6,6 +6,7 @@
 // the reference's operation order (separately rounded products and sums: no FMA contraction, the rounding decides which pixel
 // is read).  Bound: HBM (one read + one write of the tensor); one thread per output pixel, all channels.
 #include "common.h"
+#include "launchers.h"
 
 __global__ __launch_bounds__(256) void affine_nearest_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                              const float* __restrict__ mat, int C, int H, int W, int mat_stride) {

@@ -8,6 +8,7 @@
 // The first three come as GROUPED launches: the cells of one diagonal of the decoder's (level, timestep) wavefront are independent,
 // so their jobs share a grid (job table by value in the kernel arguments, block ranges per job).
 #include "common.h"
+#include "launchers.h"
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -9,6 +9,7 @@
 // threads x S adds) -- so the result does not depend on the order blocks run in: bit-reproducible without atomics.
 // The arithmetic is fp32 on the exact bf16 inputs, with ONE rounding to bf16 at each store.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

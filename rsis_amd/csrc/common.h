@@ -15,6 +15,23 @@
 #define RSIS_LDW_ALIGN 128  // packed-weight row stride is a multiple of this many floats
 #define RSIS_MAX_SRC 3      // channel-concatenated sources / split destinations per conv
 
+// Layouts of a packed weight copy (pack.hip): chosen by pack_plan() of api.hip, carried to the device in rsis_pack_job.imode.  The values
+// are part of that struct's contract and the ORDER is used: f32 rows < PACK_BF16_FWD <= bf16 cells < PACK_WINO_FWD <= Winograd blocks, and
+// from PACK_DIRECT_DGRAD on the f32 rows come in 72-row chunks.
+enum PackMode {
+  PACK_IGEMM_FWD = 0,         // implicit GEMM, forward
+  PACK_IGEMM_DGRAD = 1,       // implicit GEMM, data gradient
+  PACK_DIRECT_FWD = 2,        // direct 3x3, forward (stride 1 and 2)
+  PACK_DIRECT_DGRAD = 3,      // direct 3x3 / stride 1, data gradient (taps flipped)
+  PACK_DIRECT_DGRAD_S2 = 4,   // direct 3x3 / stride 2, data gradient into one destination (taps not flipped)
+  PACK_BF16_FWD = 5,          // bf16 cells of conv_bf16.hip, forward
+  PACK_BF16_DGRAD = 6,        // bf16 cells, data gradient
+  PACK_WINO_FWD = 7,          // Winograd F(2x2, 3x3) blocks of conv_wino.hip, forward
+  PACK_WINO_DGRAD = 8         // Winograd blocks, data gradient
+};
+// bf16 path: input channels per packed chunk of a conv with KK = ks * ks taps
+__host__ __device__ __forceinline__ int bf16_ckb(int KK) { return KK == 1 ? RSIS_CKB1 : RSIS_CKB3; }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

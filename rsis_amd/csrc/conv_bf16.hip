@@ -20,6 +20,7 @@
 // With 16x the f32 MFMA rate these layers are HBM-bound (the f32 kernels are MFMA-bound): what matters here is bytes in
 // flight per CU and one pass over the input, not MFMA utilisation.
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 #ifndef XCD_CHUNKED
 #define XCD_CHUNKED 1

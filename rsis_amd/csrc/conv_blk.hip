@@ -11,6 +11,7 @@
 // The MFMA loop, the LDS cell layout and the packed bf16 weights (pack.hip modes 5-7) are those of conv_bf16_kernel; the data
 // gradient is the same kernel on the flipped / transposed pack.  Stride 1, "same" padding, one source, C % 8 == 0, Cout % 8 == 0.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;

@@ -21,6 +21,7 @@
 // gates of hidden channels 2 r4 + hi: the two lanes (l31, hi = 0 / 1) exchange two values each (one wave shuffle pair) to own
 // channels 0-3 / 4-7 of the cell.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 #include <stdlib.h>
 

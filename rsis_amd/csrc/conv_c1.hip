@@ -4,6 +4,7 @@
 // Algorithmic bytes per launch: fwd/dgrad (Cin+1)*B*H*W*4, wgrad the same reads + 9*Cin floats out.  Measured at
 // 8 x 256^2 x 32 (75.5 MB): fwd 22.5 us, dgrad 18.7 us, wgrad 28.8 us (a streaming read of the input alone: 10.4 us).
 #include "common.h"
+#include "launchers.h"
 
 typedef const float __attribute__((address_space(1)))* gcf_t;
 typedef float __attribute__((address_space(1)))* gf_t;

@@ -16,6 +16,7 @@
 //   row only SCALAR work remains, so a gathered element costs ~6 VALU + 1 global_load.
 //   LDS tiles are k-major ([BK][BM] / [BK][BN]) so every ds_read_b32 of an MFMA operand is conflict-free.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 enum { EPI_PLAIN = 0, EPI_LSTM = 1, EPI_BN = 2 };     // EPI_BN: EPI_PLAIN + the folded eval-mode BatchNorm (inference; its own instantiations)

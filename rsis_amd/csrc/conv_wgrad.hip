@@ -8,6 +8,7 @@
 // Both operands are contiguous along px in NCHW, so global loads run along px and the LDS tiles are [row][BKW+1]
 // (padded) which makes both the stores and the MFMA operand ds_read_b32 conflict-free.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 #define BKW 32

@@ -21,6 +21,7 @@
 // One launch path: every weight gradient, a single one included, runs on the *_group_kernel of its body through wgb_dispatch, and
 // wgb_key alone says which instantiation a layer gets.
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

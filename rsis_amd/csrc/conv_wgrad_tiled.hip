@@ -33,6 +33,7 @@
 // One launch path: conv_wgrad_tiled_group_kernel.  A single weight gradient is a group of one job; what differs between a job on its
 // own and a group is the split plan (tiled_split_plan), nothing else.
 #include "common.h"
+#include "launchers.h"
 #include "limb_split.h"
 #include "wgrad_block_order.h"
 #include <stdlib.h>

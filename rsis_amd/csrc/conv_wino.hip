@@ -25,6 +25,7 @@
 // Accuracy (tools/exp/wino, 256 -> 256 on 16 x 16): max |y - float64| 1.1e-6 against 2.4e-6 for a sequential fp32 direct sum --
 // each of the 16 products is a 256-deep chain instead of one 2304-deep chain.
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -18,6 +18,7 @@
 //     to the global table, one atomic per RUN; at the end the block adds the non-zero cells of its window, at most one global atomic per
 //     cell and block.
 #include "common.h"
+#include "launchers.h"
 
 typedef unsigned long long u64;
 

@@ -11,6 +11,7 @@
 // Bitwise ORs and integer counts only: the result does not depend on the order of execution.  Bound: HBM (4 B read twice, 8 B
 // written per pixel).
 #include "common.h"
+#include "launchers.h"
 
 #define IM_WORDS 2048          // 65536 bits
 #define IM_LABELS 66           // labels 0..65 (65535 / 1000)

@@ -19,6 +19,7 @@
 //   label_scores_kernel      : one block per pair, table (one pass) -> marginals -> lo / hi of both images -> BestDice both ways (maxima are exact in
 //     any order; the two sums run sequentially in ascending label order in ONE thread) -> six float64 scores.
 #include "common.h"
+#include "launchers.h"
 
 typedef unsigned long long u64;
 

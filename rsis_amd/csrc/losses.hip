@@ -11,6 +11,7 @@
 //   d cost / d logit_n = (ca * y_n + cb * (1 - y_n)) * p_n (1 - p_n),  ca = -g / U,  cb = g * I / U^2,  U = sum p + sum y - I + e.
 // Both kernels are HBM-bound (252 MB in / 84 MB out at B=32, T=10, G=20, 256x256): bytes ~ (T + G) * N * 4 per image.
 #include "common.h"
+#include "launchers.h"
 
 typedef const f32x4 __attribute__((address_space(1)))* gcf4_t;
 typedef f32x4 __attribute__((address_space(1)))* gf4_t;

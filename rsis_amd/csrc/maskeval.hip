@@ -15,6 +15,7 @@
 //   coco_match_kernel     : the greedy matching of evaluateImg, one wave per (image, category, area range) cell and one lane per
 //     IoU threshold; the lanes of a wave read the same IoU (a broadcast) and write consecutive outputs.
 #include "common.h"
+#include "launchers.h"
 
 typedef unsigned long long u64;
 

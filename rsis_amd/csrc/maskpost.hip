@@ -8,6 +8,7 @@
 //     turns the counts into output slots for the change positions, and a last pass differences the positions in place.
 //   rsis_rle_to_string (host): the 6-bit varint text form of the counts.
 #include "common.h"
+#include "launchers.h"
 
 __device__ __forceinline__ void mp_coord(int o, float scale, int in, int& i0, int& i1, float& l1) {
   const float src = scale * o;

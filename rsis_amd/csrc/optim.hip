@@ -4,6 +4,7 @@
 // HBM-bound.  The range may start at any parameter offset of the flat buffers: a scalar head up to 16-byte alignment, a float4 body,
 // a scalar tail.
 #include "common.h"
+#include "launchers.h"
 
 enum { RULE_SGD = 0, RULE_RMSPROP = 1 };
 

@@ -10,6 +10,7 @@
 //   overlay_moments_kernel: (set pixels, sum of row indices, sum of column indices) per painted mask, integer sums in 64 bits: per-thread
 //     partials, wave shuffles, LDS, one 64-bit atomic add per block and moment -- nothing depends on the order of execution.
 #include "common.h"
+#include "launchers.h"
 
 #define OV_TY 128            // tile rows (contiguous mask bytes per column)
 #define OV_TX 32             // tile columns (contiguous RGB pixels per row)

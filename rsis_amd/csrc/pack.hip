@@ -11,6 +11,7 @@
 // co_p -> reference row: (co_p&3)*hid + (co_p>>2) for gate-interleaved ConvLSTM rows (clstm.py:47), identity otherwise.
 #include "common.h"
 #include "../../include/rsis_hip.h"
+#include "launchers.h"
 
 struct SegMap { int n; int C[3]; int off[3]; };
 
@@ -34,13 +35,13 @@ __device__ __forceinline__ int ref_row(int cop, int hid) { return hid > 0 ? (cop
 template <int KKC = 0>    // KKC: compile-time ks*ks (0 = use the run-time value) -- makes the row / KK divisions cheap
 __device__ __forceinline__ int pack_elem_idx(int mode, int row, int col, int Cout, int Ctot, int KKr, const SegMap& m, int hid) {
   const int KK = KKC ? KKC : KKr;
-  if (mode == 0) {                 // igemm fwd: Wp[cg*KK + rs][co_p]
+  if (mode == PACK_IGEMM_FWD) {    // igemm fwd: Wp[cg*KK + rs][co_p]
     if (col >= Cout) return -1;
     const int cg = row / KK, rs = row - cg * KK;
     const int ci = seg_channel(m, cg);
     return ci >= 0 ? (ref_row(col, hid) * Ctot + ci) * KK + rs : -1;
   }
-  if (mode == 1) {                 // igemm dgrad: Wd[co_p*KK + rs][cg]
+  if (mode == PACK_IGEMM_DGRAD) {  // igemm dgrad: Wd[co_p*KK + rs][cg]
     const int cop = row / KK, rs = row - cop * KK;
     const int ci = seg_channel(m, col);
     return (cop < Cout && ci >= 0) ? (ref_row(cop, hid) * Ctot + ci) * KK + rs : -1;
@@ -48,7 +49,7 @@ __device__ __forceinline__ int pack_elem_idx(int mode, int row, int col, int Cou
   const int qg = row / (RSIS_CK * 9), kin = row - qg * (RSIS_CK * 9);
   const int pair = kin >> 1, h = kin & 1;
   const int cc = pair / 9, rs = pair - cc * 9;
-  if (mode == 2) {                 // direct fwd: 8-channel chunks per segment, columns = co_p
+  if (mode == PACK_DIRECT_FWD) {   // direct fwd: 8-channel chunks per segment, columns = co_p
     if (col >= Cout) return -1;
     int qs = 0, r = -1;
 #pragma unroll
@@ -64,11 +65,11 @@ __device__ __forceinline__ int pack_elem_idx(int mode, int row, int col, int Cou
     }
     return r;
   }
-  // direct dgrad: rows = chunks of co_p, columns = cg.  mode 3 (stride 1) reads tap 8-rs (the transposed conv); mode 4 (stride 2,
+  // direct dgrad: rows = chunks of co_p, columns = cg.  PACK_DIRECT_DGRAD (stride 1) reads tap 8-rs (the transposed conv); _S2 (stride 2,
   // EPI_S2 of conv3x3_direct.hip) keeps the original tap order (each tap is routed to its parity class by the kernel)
   const int c = qg * RSIS_CK + 2 * cc + h;      // channel of dy (packed row order for ConvLSTM)
   const int ci = seg_channel(m, col);
-  return (c < Cout && ci >= 0) ? (ref_row(c, hid) * Ctot + ci) * 9 + (mode == 3 ? 8 - rs : rs) : -1;
+  return (c < Cout && ci >= 0) ? (ref_row(c, hid) * Ctot + ci) * 9 + (mode == PACK_DIRECT_DGRAD ? 8 - rs : rs) : -1;
 }
 template <int KKC = 0>
 __device__ __forceinline__ float pack_elem(int mode, const float* __restrict__ W, int row, int col, int Cout, int Ctot, int KKr,
@@ -90,8 +91,8 @@ __global__ void pack_kernel(int mode, const float* __restrict__ W, float* __rest
 // ---- bf16 layouts (conv_bf16.hip): 16-byte cells of 8 consecutive reduction channels, out[(kb * ldw + col) * 8 + e] ----
 //   kb = (q * KK + rs) * NCB + cb: chunk q of CKB channels (CKB = RSIS_CKB3 for 3x3, RSIS_CKB1 for 1x1; chunks never straddle
 //   a concat segment, the tail of a segment is zero), tap rs, 8-channel block cb of the chunk; NCB = CKB / 8.
-//   mode 5 (forward): reduction channel = input channel of the concat, col = co_p.
-//   mode 6 (data gradient): reduction channel = dy channel co_p, col = cg (index in the concat), 3x3 taps flipped.
+//   PACK_BF16_FWD: reduction channel = input channel of the concat, col = co_p.
+//   PACK_BF16_DGRAD: reduction channel = dy channel co_p, col = cg (index in the concat), 3x3 taps flipped.
 typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned pk_u32x4 __attribute__((ext_vector_type(4)));
@@ -99,14 +100,13 @@ __device__ __forceinline__ unsigned short to_bf16(float v) {
   const pk_f32x2 f = {v, 0.f};
   return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f, pk_bf16x2)) & 0xFFFFu);
 }
-__host__ __device__ __forceinline__ int bf16_ckb(int KK) { return KK == 1 ? RSIS_CKB1 : RSIS_CKB3; }
 
 __device__ __forceinline__ int pack_bf16_idx(int mode, int kb, int col, int e, int Cout, int Ctot, int KK, const SegMap& m, int hid) {
   const int CKB = bf16_ckb(KK), NCB = CKB / 8;
   const int q = kb / (KK * NCB), rem = kb - q * (KK * NCB);
   const int rs = rem / NCB, cb = rem - rs * NCB;
   const int cl = cb * 8 + e;                         // channel inside the chunk
-  if (mode == 5) {
+  if (mode == PACK_BF16_FWD) {
     if (col >= Cout) return -1;
     int qs = 0, r = -1;
 #pragma unroll
@@ -144,9 +144,9 @@ __global__ void pack_bf16_kernel(int mode, const float* __restrict__ W, unsigned
   }
 }
 
-// batched repack of the bf16 layouts.  Forward (mode 5): one block = one channel chunk (KK * NCB cell rows) x 64 columns; for a
+// batched repack of the bf16 layouts.  Forward (PACK_BF16_FWD): one block = one channel chunk (KK * NCB cell rows) x 64 columns; for a
 // column the chunk's KK * CKB source weights are one contiguous run of the reference weight, read with the lanes running along
-// it, converted, parked in LDS in cell order and written out as full 1 KB rows.  Data gradient (mode 6): 16 cell rows x 64
+// it, converted, parked in LDS in cell order and written out as full 1 KB rows.  Data gradient (PACK_BF16_DGRAD): 16 cell rows x 64
 // columns per block; the lanes run along the columns (= the reference weight's input channels), reads and writes coalesce.
 __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, unsigned short* lds16) {
   SegMap m;
@@ -157,7 +157,7 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
   const int nct = j.ldw / 64;
   const int c0 = (tb % nct) * 64;
   unsigned short* out = (unsigned short*)j.out;
-  if (j.imode == 5) {
+  if (j.imode == PACK_BF16_FWD) {
     const int R = KK * NCB;                          // cell rows of one chunk (18 or 8)
     const int q = tb / nct;
     const int run = KK * CKB;                        // source floats per column
@@ -170,7 +170,7 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
         const int ch = idx / KK, rs = idx - ch * KK;
         const int kb = q * R + rs * NCB + (ch >> 3);
         dst[u] = i < 64 * run ? ((rs * NCB + (ch >> 3)) * 64 + cl) * 8 + (ch & 7) : -1;
-        src[u] = i < 64 * run ? pack_bf16_idx(5, kb, c0 + cl, ch & 7, j.Cout, j.Ctot, KK, m, j.lstm_hid) : -1;
+        src[u] = i < 64 * run ? pack_bf16_idx(PACK_BF16_FWD, kb, c0 + cl, ch & 7, j.Cout, j.Ctot, KK, m, j.lstm_hid) : -1;
       }
       float v[4];
 #pragma unroll
@@ -193,7 +193,7 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
       int src[8];
       float f[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) src[e] = pack_bf16_idx(6, r0 + rr, c0 + cl, e, j.Cout, j.Ctot, KK, m, j.lstm_hid);
+      for (int e = 0; e < 8; ++e) src[e] = pack_bf16_idx(PACK_BF16_DGRAD, r0 + rr, c0 + cl, e, j.Cout, j.Ctot, KK, m, j.lstm_hid);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = j.W[src[e] < 0 ? 0 : src[e]];
       unsigned v[4];
@@ -211,8 +211,8 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
 // ---- Winograd F(2x2, 3x3) copies (conv_wino.hip): U = G g G^T, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], stored as
 //   out[((ot * nq + q) * 16 + xi) * 256 + cl * 32 + col]   ot = output-channel tile of 32, q = chunk of 8 reduction channels,
 //   xi = 4 i + j the position in the 4 x 4 Winograd domain -- one (ot, q) block of 4096 floats is what a block of the conv kernel
-//   DMAs per chunk.  mode 7 (forward): output channel = the weight's row co, reduction channel = its input channel ci, g = W[co][ci];
-//   mode 8 (data gradient): output channel = ci, reduction channel = co, g = W[co][ci] rotated by 180 degrees (the transposed conv);
+//   DMAs per chunk.  PACK_WINO_FWD: output channel = the weight's row co, reduction channel = its input channel ci, g = W[co][ci];
+//   PACK_WINO_DGRAD: output channel = ci, reduction channel = co, g = W[co][ci] rotated by 180 degrees (the transposed conv);
 //   here the output channels may be the concat of up to 3 channel segments and the rows gate-interleaved (the ConvLSTM gate convs).
 //   One tile = one (ot, q) block, one thread = one channel pair (9 loads, 16 coalesced stores).
 __device__ __forceinline__ void pack_tile_wino(int mode, const float* __restrict__ W, float* __restrict__ out, int Cout, int Ctot, int tb,
@@ -222,17 +222,17 @@ __device__ __forceinline__ void pack_tile_wino(int mode, const float* __restrict
   int csum = 0;
 #pragma unroll
   for (int s_ = 0; s_ < 3; ++s_) csum += s_ < m.n ? m.C[s_] : 0;
-  const int n_red = mode == 7 ? csum : Cout, nq = n_red >> 3;
+  const int n_red = mode == PACK_WINO_FWD ? csum : Cout, nq = n_red >> 3;
   const int ot = tb / nq, q = tb - ot * nq;
   const int cl = threadIdx.x >> 5, col = threadIdx.x & 31;
   const int o = ot * 32 + col, rch = q * 8 + cl;                 // output / reduction channel of the conv this copy serves
-  const int cop = mode == 7 ? o : rch, cg = mode == 7 ? rch : o; // packed row / concat index
+  const int cop = mode == PACK_WINO_FWD ? o : rch, cg = mode == PACK_WINO_FWD ? rch : o; // packed row / concat index
   const int ci = seg_channel(m, cg);
   const bool ok = ci >= 0 && cop < Cout;
   const float* g_ = W + ((size_t)ref_row(ok ? cop : 0, hid) * Ctot + (ok ? ci : 0)) * 9;
   float g[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) g[k] = g_[mode == 7 ? k : 8 - k];
+  for (int k = 0; k < 9; ++k) g[k] = g_[mode == PACK_WINO_FWD ? k : 8 - k];
 #pragma unroll
   for (int k = 0; k < 9; ++k) g[k] = ok ? g[k] : 0.f;
   float t[4][3];
@@ -274,7 +274,7 @@ __device__ __forceinline__ void pack_tile(const rsis_pack_job& j, int tb, float 
   const int l = threadIdx.x & 63, q = threadIdx.x >> 6, KK = j.ks * j.ks;
   const int c0 = (tb % nct) * PACK_TC;
   int r0, nrow;
-  if (j.imode >= 3) {
+  if (j.imode >= PACK_DIRECT_DGRAD) {
     // direct dgrad layouts: tile = one 72-row chunk (8 dy channels x 9 taps) x 128 columns (input channels).  For one dy channel the
     // reference weight is contiguous over (input channel, tap): the lanes walk that run, LDS re-orders it into packed rows.
     constexpr int R = RSIS_CK * 9;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void pack_tile(const rsis_pack_job& j, int tb, float 
       for (int u = 0; u < 2 * PER; ++u) {
         const int cu = c + u / PER, i = threadIdx.x + 256 * (u % PER);
         const int cl = i / 9, tap = i - cl * 9;                      // tap of the reference weight
-        const int rs = j.imode == 3 ? 8 - tap : tap;                 // its packed position
+        const int rs = j.imode == PACK_DIRECT_DGRAD ? 8 - tap : tap;                 // its packed position
         const int kin = ((cu >> 1) * 9 + rs) * 2 + (cu & 1);
         const bool ok = i < PACK_TC * 9;
         kin_[u] = ok ? kin : -1; cl_[u] = cl;
@@ -303,12 +303,12 @@ __device__ __forceinline__ void pack_tile(const rsis_pack_job& j, int tb, float 
   } else {
     r0 = (tb / nct) * PACK_T;
     nrow = min(PACK_T, j.krows - r0);
-    if (j.imode == 1) {          // igemm dgrad: columns already run along the reference weight's input channels
+    if (j.imode == PACK_IGEMM_DGRAD) {          // igemm dgrad: columns already run along the reference weight's input channels
       static_assert(PACK_TC == 64, "one column per lane");
       for (int rr0 = q; rr0 < nrow; rr0 += 16) {            // four rows per thread in flight
         int src[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) src[u] = rr0 + 4 * u < nrow ? pack_elem_idx<KKC>(1, r0 + rr0 + 4 * u, c0 + l, j.Cout, j.Ctot, KK, m, j.lstm_hid) : -1;
+        for (int u = 0; u < 4; ++u) src[u] = rr0 + 4 * u < nrow ? pack_elem_idx<KKC>(PACK_IGEMM_DGRAD, r0 + rr0 + 4 * u, c0 + l, j.Cout, j.Ctot, KK, m, j.lstm_hid) : -1;
         float v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = j.W[src[u] < 0 ? 0 : src[u]];
@@ -356,14 +356,14 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const rsis_pack_job* __
       next_begin = lo + 1 < njobs ? jobs[lo + 1].block_begin : total_tiles;
     }
     const int tb = b - j.block_begin;
-    if (j.imode >= 7) {
+    if (j.imode >= PACK_WINO_FWD) {
       SegMap wm;
       wm.n = j.nseg;
 #pragma unroll
       for (int s_ = 0; s_ < 3; ++s_) { wm.C[s_] = j.Cseg[s_]; wm.off[s_] = j.Coff[s_]; }
       pack_tile_wino(j.imode, j.W, (float*)j.out, j.Cout, j.Ctot, tb, wm, j.lstm_hid);
     }
-    else if (j.imode >= 5) pack_tile_bf16(j, tb, (unsigned short*)&tile[0][0]);
+    else if (j.imode >= PACK_BF16_FWD) pack_tile_bf16(j, tb, (unsigned short*)&tile[0][0]);
     else if (j.ks == 1) pack_tile<1>(j, tb, tile);
     else if (j.ks == 3) pack_tile<9>(j, tb, tile);
     else pack_tile<0>(j, tb, tile);
@@ -375,11 +375,11 @@ int rsis_l_pack_batch(const rsis_pack_job* jobs, int njobs, int total_blocks, hi
   hipLaunchKernelGGL(pack_batch_kernel, dim3((total_blocks + PACK_TPB - 1) / PACK_TPB), dim3(256), 0, st, jobs, njobs, total_blocks);
   return rsis_check_launch();
 }
-int rsis_l_pack_blocks(int mode, int krows, int ldw, int ks) {
-  if (mode >= 7) return krows;                              // Winograd copies: krows carries the number of (ot, q) blocks
-  if (mode == 5) return krows / (ks * ks * (bf16_ckb(ks * ks) / 8)) * (ldw / 64);     // one chunk x 64 columns per block
-  if (mode == 6) return (krows + 15) / 16 * (ldw / 64);
-  return (mode >= 3 ? krows / (RSIS_CK * 9) : (krows + PACK_T - 1) / PACK_T) * (ldw / PACK_TC);
+int rsis_l_pack_blocks(PackMode mode, int krows, int ldw, int ks) {
+  if (mode >= PACK_WINO_FWD) return krows;                              // Winograd copies: krows carries the number of (ot, q) blocks
+  if (mode == PACK_BF16_FWD) return krows / (ks * ks * (bf16_ckb(ks * ks) / 8)) * (ldw / 64);     // one chunk x 64 columns per block
+  if (mode == PACK_BF16_DGRAD) return (krows + 15) / 16 * (ldw / 64);
+  return (mode >= PACK_DIRECT_DGRAD ? krows / (RSIS_CK * 9) : (krows + PACK_T - 1) / PACK_T) * (ldw / PACK_TC);
 }
 
 static inline int pack_grid(long total) {
@@ -388,9 +388,8 @@ static inline int pack_grid(long total) {
   return (int)(g < 1 ? 1 : g);
 }
 
-// mode: 0 igemm fwd, 1 igemm dgrad, 2 direct fwd, 3 direct dgrad (stride 1), 4 direct dgrad (stride 2: taps not flipped),
-// 5 bf16 fwd, 6 bf16 dgrad (cell layouts of conv_bf16.hip), 7 Winograd fwd, 8 Winograd dgrad (conv_wino.hip)
-int rsis_l_pack(int mode, const float* W, void* out, int Cout, int Ctot, int ks, int nseg, const int* Cseg, const int* Coff,
+// one packed copy in a launch of its own (the modes: PackMode of common.h)
+int rsis_l_pack(PackMode mode, const float* W, void* out, int Cout, int Ctot, int ks, int nseg, const int* Cseg, const int* Coff,
                 int ldw, int krows, int hid, hipStream_t st) {
   SegMap m = {};
   m.n = nseg;
@@ -398,12 +397,11 @@ int rsis_l_pack(int mode, const float* W, void* out, int Cout, int Ctot, int ks,
   for (int s = 0; s < nseg; ++s) { m.C[s] = Cseg[s]; m.off[s] = Coff ? Coff[s] : base; base += Cseg[s]; }
   const long total = (long)krows * ldw;
   const dim3 g(pack_grid(total)), b(256);
-  if (mode == 7 || mode == 8) {      // Winograd copies (one source covering every input channel; krows = (ot, q) blocks)
+  if (mode >= PACK_WINO_FWD) {      // Winograd copies (one source covering every input channel; krows = (ot, q) blocks)
     hipLaunchKernelGGL(pack_wino_kernel, dim3(krows), b, 0, st, mode, W, (float*)out, Cout, Ctot, m, hid);
     return rsis_check_launch();
   }
-  if (mode < 0 || mode > 6) return RSIS_ERR_ARG;
-  if (mode >= 5) {     // bf16 cell layouts: krows = cell rows, out = bf16
+  if (mode >= PACK_BF16_FWD) {     // bf16 cell layouts: krows = cell rows, out = bf16
     hipLaunchKernelGGL(pack_bf16_kernel, dim3(pack_grid(total * 8)), b, 0, st, mode, W, (unsigned short*)out, Cout, Ctot, ks * ks, m, ldw,
                        krows, hid);
     return rsis_check_launch();

@@ -7,6 +7,7 @@
 //                           (idmap == id) -- the scheme of rle_encode_kernel (maskpost.hip): per chunk the threads count value changes, a
 //                           block scan places their positions, a second pass turns positions into lengths -- without the k x hw byte masks.
 #include "common.h"
+#include "launchers.h"
 
 __global__ __launch_bounds__(256) void palette_to_ids_kernel(const unsigned char* __restrict__ rgb, long npix,
                                                              const unsigned char* __restrict__ table, int ntab,

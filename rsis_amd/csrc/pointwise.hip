@@ -3,6 +3,7 @@
 // 3x3/2 max-pool fwd/bwd, per-channel bias-grad reduction and the flat fused Adam step (weight repacking: pack.hip).
 // All are HBM-roofline kernels: coalesced along W, grid-stride, float4 where the row length allows it.
 #include "common.h"
+#include "launchers.h"
 #include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------

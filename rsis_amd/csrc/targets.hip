@@ -9,6 +9,7 @@
 //               image also writes y_class / sw_mask / sw_class.
 // Integer counts only, so the result is the same whatever the order of the atomics.  Bound: HBM, the B * T * HW * 4 bytes of y_mask.
 #include "common.h"
+#include "launchers.h"
 #include <limits.h>
 
 #define TGT_IDS 256

@@ -18,6 +18,7 @@
 // latter, as rsis_conv_out_seq_*).  w is the reference layout [1][8][3][3].
 // HBM-bound: algorithmic bytes per launch = the three tensors once (fwd: h + out; bwd: dout + h + dh).
 #include "common.h"
+#include "launchers.h"
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 

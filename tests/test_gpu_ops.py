@@ -330,7 +330,7 @@ def test_repack_all_equals_lazy_packs():
     cfgs = [  # (Cout, Ctot, ks, stride, pad, segs, offs, lstm_hid)
         (64, 48, 3, 1, 1, [16, 32], None, 0), (256, 64, 1, 1, 0, [64], None, 0), (64, 3, 7, 2, 3, [3], None, 0),
         (40, 24, 3, 2, 1, [24], None, 0), (128, 56, 3, 1, 1, [24, 8], [0, 48], 32), (130, 129, 3, 1, 1, [129], None, 0),
-        (512, 256, 1, 2, 0, [256], None, 0)]
+        (512, 256, 1, 2, 0, [256], None, 0), (40, 24, 3, 2, 1, [16, 8], None, 0)]
     rng = np.random.default_rng(17)
     packs, weights, biases = [], [], []
     for Cout, Ctot, ks, stride, pad, segs, offs, hid in cfgs:
@@ -353,6 +353,28 @@ def test_repack_all_equals_lazy_packs():
         assert torch.equal(got_f, q.fwd(w, b)) and torch.equal(got_d, q.dgrad(w)), (Cout, Ctot, ks, stride)
         if hid:
             assert torch.equal(p.bias_p, q.bias_p)
+
+
+@pytest.mark.gpu
+def test_pack_dgrad_refuses_bf16_lstm_1x1():
+    """a bf16 ConvLSTM pack with ks != 3 is refused in BOTH directions (one layout rule; ops.PackedConv never asks for it: such cells
+    run under fp32): rsis_conv_pack_dgrad returns RSIS_ERR_UNSUPPORTED like rsis_conv_pack_fwd and launches nothing"""
+    from rsis_amd import _lib
+    L = _lib.lib()
+    hid, C, BF16, UNSUPPORTED = 8, 16, 1, 3
+    w = _rng_t(5, (4 * hid, C, 1, 1)).cuda()
+    n = L.rsis_conv_packed_bytes_dgrad(BF16, 4 * hid, 1, 1, 0, C) // 4
+    assert n > 0
+    out = torch.full((n,), 12345.0, device="cuda")
+    segs = _lib.int_array([C])
+    for call in (L.rsis_conv_pack_dgrad, L.rsis_conv_pack_fwd):
+        assert call(_lib.ptr(w), _lib.ptr(out), 4 * hid, C, 1, 1, 0, 1, segs, None, hid, BF16, _lib.stream()) == UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((out == 12345.0).all()), "a refused pack must not touch the output buffer"
+    # the same weight as a plain conv (lstm_hid 0) is packed
+    assert L.rsis_conv_pack_dgrad(_lib.ptr(w), _lib.ptr(out), 4 * hid, C, 1, 1, 0, 1, segs, None, 0, BF16, _lib.stream()) == 0
+    torch.cuda.synchronize()
+    assert not bool((out == 12345.0).all())
 
 
 @pytest.mark.gpu
