@@ -433,6 +433,11 @@ static int wgrad_route(WgradArgs& a, int ks, int lstm_hid, int dtype) {
     a.blk = 1;
     return rsis_wgrad_bf16_supported(a, ks) ? 1 : -1;
   }
+  if (dtype != RSIS_DTYPE_BF16) {         // fp32 operands, fp32 result: the staged limb kernels of conv_wgrad_bf16.hip, where their table (or RSIS_WGRAD_LIMBS=staged) says so
+    const int staged = rsis_wgrad_staged_limbs(a, ks);
+    if (staged < 0) return -1;
+    if (staged > 0) { a.limbs = 1; return 1; }
+  }
   if (use_direct(ks, a.stride, a.pad) && a.Cout == 1 && lstm_hid == 0 && rsis_c1_supported(a.Cs) && a.H == a.Ho && a.W == a.Wo && a.W % 4 == 0)
     return 0;
   // stride-1 "same" convs on tile-aligned maps: the LDS-DMA tiled kernel (conv_wgrad_tiled.hip); RSIS_WGRAD_TILED=0 forces the

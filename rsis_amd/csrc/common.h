@@ -215,6 +215,7 @@ struct WgradArgs {
   int chunk;         // px per split (multiple of BKW)
   int n_co_tiles, n_n_tiles;
   int blk;           // bf16 kernels only: dy and x are channel-blocked bf16 tensors (conv_blk.hip)
+  int limbs;         // bf16 kernels only: an fp32 job on their staged limb instantiations (rsis_wgrad_staged_limbs)
 };
 
 // ---- the recurrent decoder on channel-blocked bf16 tensors (conv_blk_dec.hip, blk_dec.hip; include/rsis_hip.h rsis_blk_*_batch) ----

@@ -20,8 +20,20 @@
 // when the tile is staged.  Split-K over spatial tiles / images with fp32 atomics into dW, as conv_wgrad_tiled.hip.
 // One launch path: every weight gradient, a single one included, runs on the *_group_kernel of its body through wgb_dispatch, and
 // wgb_key alone says which instantiation a layer gets.
+//
+// LIMBS = 1 of the two register-staged bodies (wgrad3_limb_group_kernel / wgrad1_limb_group_kernel) is an fp32 path: the operands
+// are not rounded but split into three exact bf16 limbs (limb_split.h) ONCE per staged element, while its cell is stored -- three
+// limb planes per stage -- and the MFMA loop runs the six limb products of the LIMB loop of conv_wgrad_tiled.hip on ready fragments,
+// with no split arithmetic in it (that loop splits every value after every ds_read: up to 18 times per element of a 3x3).  Which
+// fp32 jobs take it is a measured table over job classes (wgl_class / wgl_class_mask; today the 3x3 jobs on 32-wide tiles whose
+// source is a multiple of 32 channels), in deterministic mode none.  RSIS_WGRAD_LIMBS: unset = the tables; 0 / all = every job on the
+// f32 loop / the register-split loop of conv_wgrad_tiled.hip; reg = the tables with no staged class (A/B inside one build);
+// staged = every fp32 job rsis_wgrad_bf16_supported accepts runs here, and one it does not is RSIS_ERR_UNSUPPORTED.
 #include "common.h"
 #include "launchers.h"
+#include "limb_split.h"
+#include <stdlib.h>
+#include <string.h>
 
 typedef __attribute__((address_space(3))) void* lds_vp_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -72,16 +84,43 @@ struct Task8 {
     for (int k = 0; k < 4; ++k) c[k] = wg_pack2(v[2 * k], v[2 * k + 1]);
     return c;
   }
+  // LIMBS: the three exact bf16 limbs of the 8 values (limb_split.h) as three cells, one per limb plane of the stage
+  __device__ __forceinline__ void limb_cells(u32x4 (&c)[3]) const {
+    unsigned q[3][4];
+    rsis_limb_pack8_cells(v, q[0], q[1], q[2]);
+#pragma unroll
+    for (int l = 0; l < 3; ++l) c[l] = u32x4{q[l][0], q[l][1], q[l][2], q[l][3]};
+  }
 };
 
 // ------------------------------------------------------------------------------------------------
 // 3x3: block = BM dy rows x 32 input channels x 9 taps; wave = 32 rows x 32 channels x 9 taps, the 4 / (BM / 32) wave copies of a
 // row group take alternate 16-pixel reduction steps.
 // ------------------------------------------------------------------------------------------------
-template <int BM, int TW, int IN>
+// The stage of a body: static LDS, or -- the limb stages are larger than the 64 KB a kernel may declare -- the dynamic LDS of the launch.
+template <int BYTES, bool DYN>
+__device__ __forceinline__ char* wgb_stage_lds() {
+  if constexpr (DYN) {
+    extern __shared__ __attribute__((aligned(1024))) char wgb_dyn_lds[];
+    return wgb_dyn_lds;
+  } else {
+    __shared__ __attribute__((aligned(16))) char wgb_static_lds[BYTES];
+    return wgb_static_lds;
+  }
+}
+
+// LIMBS = 1 (fp32 weight gradients on three exact bf16 limbs per operand, six products per K16 step, as the LIMB loop of
+// conv_wgrad_tiled.hip -- but every staged element is split ONCE, while its cell is stored): the stage is three PLANES of the bf16
+// stage's layout, plane l = limb l of every element, and the MFMA loop reads ready limb fragments: per K16 step 3 dy reads, and
+// per patch row and plane the 3 reads + 8 v_alignbit_b32 of the bf16 loop, for 6 x 9 MFMAs.  The limb pair is the outer loop and
+// the tap the inner one: consecutive MFMAs never share an accumulator.  Three planes leave no room for the second buffer: ONE
+// stage, the next tile prefetched into registers under the MFMAs and split + stored between two barriers.
+template <int BM, int TW, int IN, int LIMBS = 0>
 __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
   constexpr int TP = 64, TH = TP / TW, GPR = TW / 8, NG = TP / 8, KSTEPS = NG / 2;
+  constexpr int NPL = LIMBS ? 3 : 1, NBUF = LIMBS ? 1 : 2;        // limb planes of a stage; stages
+  constexpr bool FLUSH = LIMBS && BM == 128;                      // (the chain of MFMA accumulations is cut per tile, see `tot`)
   constexpr int WGM = BM / 32, KSPW = 4 / WGM, NGG = KSTEPS / KSPW;
   constexpr int PH = TH + 2, XG = GPR + 2, PWP = XG * 8;          // patch: PH rows of XG 8-pixel groups (tile columns start at 8)
   constexpr int ARS = (TP + 8) * 2;                               // bytes per dy row (16 B padding)
@@ -91,8 +130,8 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
   constexpr int XT = 32 * PH * XG, NTX = (XT + 255) / 256;        // patch tasks (per thread)
   constexpr int RED_BYTES = 4 * 8 * 288 * 4;                      // epilogue transposition buffer: 8 rows x 288 n per wave
   static_assert(WGM * KSPW == 4 && KSTEPS % KSPW == 0 && (BM * NG) % 256 == 0, "config");
-  constexpr int LDS_BYTES = 2 * ST_BYTES > RED_BYTES ? 2 * ST_BYTES : RED_BYTES;
-  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
+  constexpr int LDS_BYTES = NBUF * NPL * ST_BYTES > RED_BYTES ? NBUF * NPL * ST_BYTES : RED_BYTES;      // (w3_lds_bytes)
+  char* const lds = wgb_stage_lds<LDS_BYTES, LIMBS != 0>();
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -106,25 +145,32 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
   if (t_begin >= t_end) return;
 
   // ---- loop-invariant parts of the staging tasks ----
+  // (LIMBS at two blocks per CU: 20 registers the MFMA loop has no room for.  Kept, they were spilled, and a reload between the
+  //  prefetch loads waits for every load before it: the tile's loads went out one round trip after the other.  There they are
+  //  computed again per tile, before the loads and before the stores, from a thread index the compiler cannot see through.)
   int a_off[NTA], a_y[NTA], a_x[NTA], a_lds[NTA];
-#pragma unroll
-  for (int i = 0; i < NTA; ++i) {
-    const int e = tid + i * 256;
-    const int row = e / NG, G = e % NG;
-    a_y[i] = G / GPR; a_x[i] = (G % GPR) * 8;
-    a_off[i] = co0 + row < Cout ? row * HW + a_y[i] * W + a_x[i] : -1;
-    a_lds[i] = row * ARS + G * 16;
-  }
   int x_off[NTX], x_y[NTX], x_x[NTX], x_lds[NTX];
-#pragma unroll
-  for (int i = 0; i < NTX; ++i) {
-    const int e = tid + i * 256;
-    const int cl = e / (PH * XG), rem = e - cl * (PH * XG);
-    const int py = rem / XG, xg = rem - py * XG;
-    x_y[i] = py - 1; x_x[i] = (xg - 1) * 8;
-    x_off[i] = (e < XT && ci0 + cl < Cs) ? cl * HW + x_y[i] * W + x_x[i] : (int)0x40000000;   // (flag: never valid)
-    x_lds[i] = cl * CHSB + (py * PWP + xg * 8) * 2;
+#define W3_TASKS(T)                                                                                                \
+  {                                                                                                                \
+    _Pragma("unroll") for (int i = 0; i < NTA; ++i) {                                                              \
+      const int e = (T) + i * 256;                                                                                 \
+      const int row = e / NG, G = e % NG;                                                                          \
+      a_y[i] = G / GPR; a_x[i] = (G % GPR) * 8;                                                                    \
+      a_off[i] = co0 + row < Cout ? row * HW + a_y[i] * W + a_x[i] : -1;                                           \
+      a_lds[i] = row * ARS + G * 16;                                                                               \
+    }                                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < NTX; ++i) {                                                              \
+      const int e = (T) + i * 256;                                                                                 \
+      const int cl = e / (PH * XG), rem = e - cl * (PH * XG);                                                      \
+      const int py = rem / XG, xg = rem - py * XG;                                                                 \
+      x_y[i] = py - 1; x_x[i] = (xg - 1) * 8;                                                                      \
+      x_off[i] = (e < XT && ci0 + cl < Cs) ? cl * HW + x_y[i] * W + x_x[i] : (int)0x40000000;   /* (flag: never valid) */ \
+      x_lds[i] = cl * CHSB + (py * PWP + xg * 8) * 2;                                                              \
+    }                                                                                                              \
   }
+  constexpr bool RETASK = LIMBS && BM < 128;
+#define W3_RETASK() if constexpr (RETASK) { int tv = tid; asm volatile("" : "+v"(tv)); W3_TASKS(tv) }
+  W3_TASKS(tid)
 
   // ---- per-lane LDS read bases (bytes) ----
   const int a_base = (wm * 32 + l31) * ARS + hi * 16;
@@ -141,6 +187,20 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+  // The bf16 MFMA does not round its sum into the accumulator to nearest as the f32 MFMA's fmaf chain does: over a chain of six
+  // MFMAs per K16 step the error grows with the chain's LENGTH, not its square root (measured: a wave that walked 12 K16 steps of a
+  // 1x1 was 4.6 x as far from float64 as one that walked 4; the f32 loop 1.4 x).  So a wave that walks every K16 step of a tile
+  // itself (BM = 128, and every 1x1 tile) starts each tile from zero accumulators and adds them to `tot` on the VALU, round to
+  // nearest: at most 24 MFMAs per chain.  BM = 64 / 32 deal the K16 steps over 2 / 4 wave copies -- chains half / a quarter as
+  // long per tile -- and at two blocks per CU have no registers for a second set of nine tiles.
+  [[maybe_unused]] f32x16 tot[FLUSH ? 9 : 1];
+  if constexpr (FLUSH) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) tot[t][r] = 0.f;
+  }
 
   // scalar tile cursor
   int tb = t_begin / (tiles_x * tiles_y);
@@ -165,18 +225,71 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
 #define W3_STORE(BUF)                                                                                              \
   {                                                                                                                \
     char* st = lds + (BUF) * ST_BYTES;                                                                             \
-    _Pragma("unroll") for (int i = 0; i < NTA; ++i) *(u32x4*)(st + a_lds[i]) = ra[i].cell();                       \
-    _Pragma("unroll") for (int i = 0; i < NTX; ++i)                                                                \
-      if (XT % 256 == 0 || tid + i * 256 < XT) *(u32x4*)(st + A_BYTES + x_lds[i]) = rxp[i].cell();                 \
+    if constexpr (LIMBS) {                                                                                         \
+      u32x4 c[3];                                                                                                  \
+      _Pragma("unroll") for (int i = 0; i < NTA; ++i) {                                                            \
+        ra[i].limb_cells(c);                                                                                       \
+        _Pragma("unroll") for (int l = 0; l < 3; ++l) *(u32x4*)(st + l * ST_BYTES + a_lds[i]) = c[l];              \
+      }                                                                                                            \
+      _Pragma("unroll") for (int i = 0; i < NTX; ++i)                                                              \
+        if (XT % 256 == 0 || tid + i * 256 < XT) {                                                                 \
+          rxp[i].limb_cells(c);                                                                                    \
+          _Pragma("unroll") for (int l = 0; l < 3; ++l) *(u32x4*)(st + l * ST_BYTES + A_BYTES + x_lds[i]) = c[l];  \
+        }                                                                                                          \
+    } else {                                                                                                       \
+      _Pragma("unroll") for (int i = 0; i < NTA; ++i) *(u32x4*)(st + a_lds[i]) = ra[i].cell();                     \
+      _Pragma("unroll") for (int i = 0; i < NTX; ++i)                                                              \
+        if (XT % 256 == 0 || tid + i * 256 < XT) *(u32x4*)(st + A_BYTES + x_lds[i]) = rxp[i].cell();               \
+    }                                                                                                              \
   }
 
   W3_LOAD() W3_STORE(0)
   __syncthreads();
   const int ntl = t_end - t_begin;
   for (int t = 0; t < ntl; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < ntl) W3_LOAD()
-    {
+    const int cur = LIMBS ? 0 : t & 1;
+    if (t + 1 < ntl) { W3_RETASK() W3_LOAD() }
+    if constexpr (LIMBS) {
+      const char* As = lds + a_base;
+      const char* Xs = lds + A_BYTES;
+#pragma unroll
+      for (int gg = 0; gg < NGG; ++gg) {
+        bf16x8 a[3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) a[l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + (gg * KSPW + wk) * 32));
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          bf16x8 w[3][3];                                           // [limb][tap s]
+#pragma unroll
+          for (int l = 0; l < 3; ++l) {
+            const char* row = Xs + l * ST_BYTES + bo[gg] + r * PWP * 2;
+            const unsigned d0 = *(const unsigned*)(row - 4);
+            const u32x4 m = *(const u32x4*)row;
+            const unsigned d5 = *(const unsigned*)(row + 16);
+            const u32x4 w0 = {__builtin_amdgcn_alignbit(m[0], d0, 16), __builtin_amdgcn_alignbit(m[1], m[0], 16),
+                              __builtin_amdgcn_alignbit(m[2], m[1], 16), __builtin_amdgcn_alignbit(m[3], m[2], 16)};
+            const u32x4 w2 = {__builtin_amdgcn_alignbit(m[1], m[0], 16), __builtin_amdgcn_alignbit(m[2], m[1], 16),
+                              __builtin_amdgcn_alignbit(m[3], m[2], 16), __builtin_amdgcn_alignbit(d5, m[3], 16)};
+            w[l][0] = __builtin_bit_cast(bf16x8, w0); w[l][1] = __builtin_bit_cast(bf16x8, m); w[l][2] = __builtin_bit_cast(bf16x8, w2);
+          }
+#pragma unroll
+          for (int q = 0; q < RSIS_LIMB_PRODUCTS; ++q)
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+              acc[r * 3 + s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[RSIS_LIMB_PA(q)], w[RSIS_LIMB_PB(q)][s], acc[r * 3 + s], 0, 0, 0);
+          // (32-wide tiles at two blocks per CU: the windows of the next row are not built above this row's MFMAs -- two rows of
+          //  them live at once spilled 21 registers, some of them reloaded between the prefetch loads)
+          if constexpr (BM < 128 && TW == 32) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __syncthreads();                                              // every wave has read tile t: the one stage is free
+      if constexpr (FLUSH) {
+#pragma unroll
+        for (int tt = 0; tt < 9; ++tt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { tot[tt][r] += acc[tt][r]; acc[tt][r] = 0.f; }
+      }
+    } else {
       const char* As = lds + cur * ST_BYTES + a_base;
       const char* Xs = lds + cur * ST_BYTES + A_BYTES;
 #pragma unroll
@@ -198,11 +311,17 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
         }
       }
     }
-    if (t + 1 < ntl) W3_STORE(cur ^ 1)
+    if (t + 1 < ntl) { W3_RETASK() W3_STORE(LIMBS ? 0 : cur ^ 1) }
     __syncthreads();
   }
 #undef W3_LOAD
 #undef W3_STORE
+#undef W3_TASKS
+#undef W3_RETASK
+  if constexpr (FLUSH) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = tot[t];
+  }
 
   // ---- epilogue: the KSPW wave copies of a row group first sum their partial tiles in LDS (fewer same-address atomics: they are
   // serialised by the L2), 8 rows x 288 columns at a time; the rows are then split over the copies and added to dW with the lanes
@@ -629,16 +748,19 @@ constexpr int w3t_nr(int bm, int tw) {
 // ------------------------------------------------------------------------------------------------
 // 1x1: D[co][ci] = sum_px dy[co][px] x[ci][px]; block tile BM x BN, waves WGM x WGN, TM x TN MFMA tiles per wave.
 // ------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WGM, int WGN, int TW, int IN>
+// LIMBS = 1: as in wgrad3_bf16_body -- three limb planes of the stage, split once per staged element, ONE stage; per K16 step
+// 3 (TM + TN) reads for 6 TM TN MFMAs, limb pair outermost.
+template <int BM, int BN, int WGM, int WGN, int TW, int IN, int LIMBS = 0>
 __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
   constexpr int TP = 64, TH = TP / TW, GPR = TW / 8, NG = TP / 8, KSTEPS = NG / 2;
+  constexpr int NPL = LIMBS ? 3 : 1, NBUF = LIMBS ? 1 : 2;
   constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
   constexpr int ARS = (TP + 8) * 2;
   constexpr int A_BYTES = BM * ARS, B_BYTES = BN * ARS, ST_BYTES = A_BYTES + B_BYTES;
   constexpr int NTA = BM * NG / 256, NTB = BN * NG / 256;
   static_assert(WGM * WGN == 4 && (BM * NG) % 256 == 0 && (BN * NG) % 256 == 0, "config");
-  __shared__ __attribute__((aligned(16))) char lds[2 * ST_BYTES];
+  char* const lds = wgb_stage_lds<NBUF * NPL * ST_BYTES, LIMBS != 0>();      // (w1_lds_bytes)
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -684,6 +806,17 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
   int trem = t_begin - tb * (tiles_x * tiles_y);
   int ty = trem / tiles_x, tx = trem - ty * tiles_x;
 
+  // LIMBS: every tile starts from zero accumulators, added to `tot` on the VALU (see wgrad3_bf16_body)
+  [[maybe_unused]] f32x16 tot[LIMBS ? TM : 1][LIMBS ? TN : 1];
+  if constexpr (LIMBS) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+  }
+
   Task8<IN == 1> ra[NTA], rb[NTB];
 #define W1_LOAD()                                                                                                  \
   {                                                                                                                \
@@ -702,17 +835,57 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
 #define W1_STORE(BUF)                                                                                              \
   {                                                                                                                \
     char* st = lds + (BUF) * ST_BYTES;                                                                             \
-    _Pragma("unroll") for (int i = 0; i < NTA; ++i) *(u32x4*)(st + a_lds[i]) = ra[i].cell();                       \
-    _Pragma("unroll") for (int i = 0; i < NTB; ++i) *(u32x4*)(st + A_BYTES + b_lds[i]) = rb[i].cell();             \
+    if constexpr (LIMBS) {                                                                                         \
+      u32x4 c[3];                                                                                                  \
+      _Pragma("unroll") for (int i = 0; i < NTA; ++i) {                                                            \
+        ra[i].limb_cells(c);                                                                                       \
+        _Pragma("unroll") for (int l = 0; l < 3; ++l) *(u32x4*)(st + l * ST_BYTES + a_lds[i]) = c[l];              \
+      }                                                                                                            \
+      _Pragma("unroll") for (int i = 0; i < NTB; ++i) {                                                            \
+        rb[i].limb_cells(c);                                                                                       \
+        _Pragma("unroll") for (int l = 0; l < 3; ++l) *(u32x4*)(st + l * ST_BYTES + A_BYTES + b_lds[i]) = c[l];    \
+      }                                                                                                            \
+    } else {                                                                                                       \
+      _Pragma("unroll") for (int i = 0; i < NTA; ++i) *(u32x4*)(st + a_lds[i]) = ra[i].cell();                     \
+      _Pragma("unroll") for (int i = 0; i < NTB; ++i) *(u32x4*)(st + A_BYTES + b_lds[i]) = rb[i].cell();           \
+    }                                                                                                              \
   }
 
   W1_LOAD() W1_STORE(0)
   __syncthreads();
   const int ntl = t_end - t_begin;
   for (int t = 0; t < ntl; ++t) {
-    const int cur = t & 1;
+    const int cur = LIMBS ? 0 : t & 1;
     if (t + 1 < ntl) W1_LOAD()
-    {
+    if constexpr (LIMBS) {
+      const char* As = lds + a_base;
+      const char* Bs = lds + A_BYTES + b_base;
+#pragma unroll
+      for (int g = 0; g < KSTEPS; ++g) {
+        bf16x8 a[TM][3], b[TN][3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+#pragma unroll
+          for (int i = 0; i < TM; ++i) a[i][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + i * 32 * ARS + g * 32));
+#pragma unroll
+          for (int j = 0; j < TN; ++j) b[j][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(Bs + l * ST_BYTES + j * 32 * ARS + g * 32));
+        }
+#pragma unroll
+        for (int q = 0; q < RSIS_LIMB_PRODUCTS; ++q)
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][RSIS_LIMB_PA(q)], b[j][RSIS_LIMB_PB(q)], acc[i][j], 0, 0, 0);
+      }
+      __syncthreads();                                              // every wave has read tile t: the one stage is free
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
+    } else {
       const char* As = lds + cur * ST_BYTES + a_base;
       const char* Bs = lds + cur * ST_BYTES + A_BYTES + b_base;
 #pragma unroll
@@ -728,11 +901,17 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
           for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
       }
     }
-    if (t + 1 < ntl) W1_STORE(cur ^ 1)
+    if (t + 1 < ntl) W1_STORE(LIMBS ? 0 : cur ^ 1)
     __syncthreads();
   }
 #undef W1_LOAD
 #undef W1_STORE
+  if constexpr (LIMBS) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
+  }
 
   // (buffer atomics, as in conv_wgrad_tiled.hip)
   const __amdgpu_buffer_rsrc_t rdw = __builtin_amdgcn_make_buffer_rsrc((void*)p.dw, 0, (unsigned)((size_t)Cout * p.ldo * 4), 0x00020000);
@@ -847,6 +1026,44 @@ __global__ __launch_bounds__(256) void wgrad1_bf16_group_kernel(const WgradBf16G
   if (!wgb_find(g, j, tile, split)) return;
   wgrad1_bf16_body<BM, BN, WGM, WGN, TW, IN>(g.job[j], tile, split);
 }
+// The staged limb kernels (LIMBS = 1 of the two register-staged bodies).  Their one stage of three limb planes is dynamic LDS:
+// 3x3 52-103 KB (BM = 32 / 64: two blocks per CU; BM = 128: one, and with it the whole register file), 1x1 55-111 KB.
+template <int BM, int TW>
+constexpr int w3l_lds_bytes() {
+  constexpr int PH = 64 / TW + 2, PWP = (TW / 8 + 2) * 8, CHSB = (PH * PWP * 2 + 31) / 32 * 32 + 16;
+  constexpr int st = 3 * (BM * (64 + 8) * 2 + 32 * CHSB);
+  return st > 4 * 8 * 288 * 4 ? st : 4 * 8 * 288 * 4;
+}
+template <int BM, int BN>
+constexpr int w1l_lds_bytes() { return 3 * (BM + BN) * (64 + 8) * 2; }
+template <int BM, int TW, int IN>
+__global__ __launch_bounds__(256, BM == 128 ? 1 : 2) void wgrad3_limb_group_kernel(const WgradBf16Group g) {
+  int j, tile, split;
+  if (!wgb_find(g, j, tile, split)) return;
+  wgrad3_bf16_body<BM, TW, IN, 1>(g.job[j], tile, split);
+}
+template <int BM, int BN, int IN>
+__global__ __launch_bounds__(256) void wgrad1_limb_group_kernel(const WgradBf16Group g) {
+  int j, tile, split;
+  if (!wgb_find(g, j, tile, split)) return;
+  wgrad1_bf16_body<BM, BN, 2, 2, 64, IN, 1>(g.job[j], tile, split);
+}
+template <int BM, int TW, int IN>
+static void w3l_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
+  constexpr int lds = w3l_lds_bytes<BM, TW>();
+  static_assert(lds <= 160 * 1024, "LDS of a CU");
+  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad3_limb_group_kernel<BM, TW, IN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  (void)once;
+  hipLaunchKernelGGL((wgrad3_limb_group_kernel<BM, TW, IN>), dim3(blocks), dim3(256), lds, st, g);
+}
+template <int BM, int BN, int IN>
+static void w1l_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
+  constexpr int lds = w1l_lds_bytes<BM, BN>();
+  static_assert(lds <= 160 * 1024, "LDS of a CU");
+  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad1_limb_group_kernel<BM, BN, IN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  (void)once;
+  hipLaunchKernelGGL((wgrad1_limb_group_kernel<BM, BN, IN>), dim3(blocks), dim3(256), lds, st, g);
+}
 
 // the split of a job that is launched on its own
 static void split_plan(WgradBf16Args& a, int TW, int TH, int ntile, int slots) {
@@ -870,6 +1087,44 @@ bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks) {
   return (long)w.Cout * img < (1L << 30) && (long)w.Cs * img < (1L << 30);
 }
 
+// ---- which fp32 jobs run on the staged limb kernels ----
+// A pure function of the job.  Classes: 3x3 jobs whose source is a multiple of the 32-channel slab, by dy rows (Cout > 64: 0-2,
+// Cout <= 64: 3-5) and by the tile width wgb_key gives the map (8 / 16 / 32: + 0 / 1 / 2); 1x1 bottleneck pairs (Cout >= 128 and
+// Cs >= 128: 6) and the other 1x1 jobs with Cout > 32 (7).  Maps that the 64-pixel tile does not divide, 3x3 sources that fill a
+// slab badly (the 8- / 16- / 24-channel decoder sources) and Cout <= 32 1x1 jobs have no class: unmeasured, they stay where they are.
+static int wgl_class(const WgradArgs& w, int ks) {
+  if (ks == 3) {
+    const int twi = w.W > 16 ? 2 : (w.W > 8 ? 1 : 0), tw = 8 << twi;
+    if (w.Cs % 32 || w.W % tw || w.H % (64 / tw)) return -1;
+    return (w.Cout > 64 ? 0 : 3) + twi;
+  }
+  if ((w.H * w.W) % 64 || w.Cout <= 32) return -1;
+  return w.Cout >= 128 && w.Cs >= 128 ? 6 : 7;
+}
+// the table: one bit per class, set only where both runs of the 256 x 256 training step with the class on the staged kernels gave a
+// lower sum over all weight-gradient launches than both runs without it (profiles/r11_a_wgrad_staged_per_class.txt, NOTES (85)):
+//   5 (Cout <= 64 on 32-wide tiles: layer 1 and the decoder's 64^2 / 32^2 sources)   7.47-7.49 ms against 7.60-7.64, 7.18-7.21 against 7.29-7.39
+//   2 (Cout > 64 on 32-wide tiles: layer 2)   a tie on its own (7.60 / 7.60 against 7.60-7.64), 7.40-7.44 on top of class 5 against
+//     7.47-7.49 without it: the two classes share one launch of the 64-row instantiation
+// Measured slower and off: 0 (8-wide, +0.2 ms), 1 (16-wide: layer 3, +0.25 ms -- the 64-row kernel is at the register-split loop's
+// time there, the 128-row one behind it), 6 (+1.3 ms) and 7 (+0.1 ms): the 1x1 stage splits only half as many values as the
+// register-split loop and pays for it with one block per CU.  3 and 4: the step has no such job, unmeasured.
+static unsigned wgl_class_mask() { return 1u << 5 | 1u << 2; }
+// RSIS_WGRAD_LIMBS, read once (conv_wgrad_tiled.hip reads `0` and `all`): unset = the table; 0 / all / reg = no staged class (the f32
+// loop / the register-split loop everywhere / the tables of conv_wgrad_tiled.hip alone); staged = every job rsis_wgrad_bf16_supported
+// accepts, in deterministic mode too, and -1 (the caller returns RSIS_ERR_UNSUPPORTED) for a job it does not.
+int rsis_wgrad_staged_limbs(const WgradArgs& w, int ks) {
+  static const int mode = [] {
+    const char* e = getenv("RSIS_WGRAD_LIMBS");
+    if (!e || !e[0]) return 0;
+    return strcmp(e, "staged") == 0 ? 2 : 1;
+  }();
+  if (mode == 2) return rsis_wgrad_bf16_supported(w, ks) ? 1 : -1;
+  if (mode == 1 || rsis_deterministic() || !rsis_wgrad_bf16_supported(w, ks)) return 0;      // (deterministic mode: the parent's routing, bit for bit)
+  const int cls = wgl_class(w, ks);
+  return cls >= 0 && ((wgl_class_mask() >> cls) & 1u);
+}
+
 // ---- launch (host side): jobs bucketed by kernel instantiation ----
 // The instantiation of a job -- the ONE statement of the rule, for a job launched on its own and for a job of a group alike.
 //   3x3: the widest 64-pixel tile the map fills; 64 dy rows per block unless the patch side is deep: half the splits (= half the
@@ -878,9 +1133,9 @@ bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks) {
 //   1x1: the reduction runs over the flattened map (the H*W pixels of a channel are contiguous; the caller has set W = H * W, H = 1),
 //   64 pixels per tile: whole 16-byte loads whenever H*W % 4 == 0.  Tiled in 2-D the 14-pixel rows of the 224 x 224 pyramid went
 //   dword by dword, 4x the VMEM instructions, and the texture-address rate -- not HBM -- bound the loop (256 -> 1024 @14^2: 43 -> 29 us).
-struct WgbKey { int ks, bm, bn, tw, v4, th; };
-static WgbKey wgb_key(const WgradBf16Args& a, int ks) {
-  WgbKey k = {ks, 0, 0, 0, 0, 0};
+struct WgbKey { int ks, bm, bn, tw, v4, th, limbs; };
+static WgbKey wgb_key(const WgradBf16Args& a, int ks, int limbs) {
+  WgbKey k = {ks, 0, 0, 0, 0, 0, a.blk ? 0 : limbs};      // limbs: an fp32 job on the staged limb kernels (LIMBS = 1 of the staged bodies)
   if (ks == 3) {
     k.tw = a.W > 16 ? 32 : (a.W > 8 ? 16 : 8);
     k.bm = a.Cout <= 32 ? 32 : ((a.Cout <= 64 || a.Cs <= 512) ? 64 : 128);
@@ -894,7 +1149,7 @@ static WgbKey wgb_key(const WgradBf16Args& a, int ks) {
   k.th = ks == 3 ? (a.blk ? w3t_th(k.bm, k.tw) : 64 / k.tw) : (a.blk ? 1 : 64 / k.tw);      // tile height (blk 3x3: the DMA kernel's tile)
   return k;
 }
-static inline bool wgb_same(const WgbKey& a, const WgbKey& b) { return a.ks == b.ks && a.bm == b.bm && a.bn == b.bn && a.tw == b.tw && a.v4 == b.v4; }
+static inline bool wgb_same(const WgbKey& a, const WgbKey& b) { return a.ks == b.ks && a.bm == b.bm && a.bn == b.bn && a.tw == b.tw && a.v4 == b.v4 && a.limbs == b.limbs; }
 
 // `alone`: the jobs are ONE job that rsis_launch_conv_wgrad_bf16 launches on its own -- split_plan, plain mode; otherwise every block
 // of the bucket walks ~L spatial tiles and the blocks are placed on the XCD lanes
@@ -977,6 +1232,10 @@ static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, bool a
 
 #define WGB3(BMv, TWv)                                                                                             \
   if (k.bm == BMv && k.tw == TWv) {                                                                                \
+    if (k.limbs && k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {      \
+      w3l_launch_group<BMv, TWv, 1>(g, blocks, st); });                                                            \
+    if (k.limbs) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                   \
+      w3l_launch_group<BMv, TWv, 0>(g, blocks, st); });                                                            \
     if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       w3t_launch_group<BMv, TWv, w3t_th(BMv, TWv), w3t_nr(BMv, TWv)>(g, blocks, st); });                           \
     if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
@@ -986,6 +1245,10 @@ static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, bool a
   }
 #define WGB1(BMv, BNv)                                                                                             \
   if (k.bm == BMv && k.bn == BNv) {                                                                                \
+    if (k.limbs && k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {      \
+      w1l_launch_group<BMv, BNv, 1>(g, blocks, st); });                                                            \
+    if (k.limbs) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                   \
+      w1l_launch_group<BMv, BNv, 0>(g, blocks, st); });                                                            \
     if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
       w1t_launch_group<BMv, BNv, W1T_TP, w1t_nr(BMv, BNv)>(g, blocks, st); });                                     \
     if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
@@ -1017,7 +1280,7 @@ static int wgb_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipStr
     a.ldo = w[j].ldo; a.n_off = w[j].n_off; a.interleave_hid = (short)w[j].interleave_hid; a.blk = (short)w[j].blk;
     if (ks == 1) { a.W = w[j].H * w[j].W; a.H = 1; }      // 1x1: the flattened map
     all[j] = a;
-    key[j] = wgb_key(a, ks);
+    key[j] = wgb_key(a, ks, w[j].limbs);
   }
   int rc = RSIS_OK;
   for (int j = 0; j < n && rc == RSIS_OK; ++j) {

@@ -29,6 +29,8 @@
 // the eight 64-cycle f32 MFMAs of a 16-pixel k-step by six 32-cycle ones.  Two consecutive step blocks g, g + 1 make one K16 step:
 // lane (r, h) uses the 4 + 4 pixels it already reads as elements j = 0..7 of its k = 8h + j fragment, A and B alike.  Which tile
 // configurations take this loop is a measured table (wg_limb_mask); RSIS_WGRAD_LIMBS=0 puts every job back on the f32 loop.
+// (A second limb path splits every element once, when it is staged: LIMBS = 1 of conv_wgrad_bf16.hip.  Jobs its table selects
+//  never reach this file; RSIS_WGRAD_LIMBS=reg keeps them here, =staged sends every job there -- see that file's header.)
 //
 // One launch path: conv_wgrad_tiled_group_kernel.  A single weight gradient is a group of one job; what differs between a job on its
 // own and a group is the split plan (tiled_split_plan), nothing else.
@@ -418,7 +420,7 @@ static unsigned wg_limb_mask(int ks, int tw) {
   return (tw == 16 || tw == 8 ? 1u << 2 : 0u) | 1u << 5;
 }
 // RSIS_WGRAD_LIMBS, read once: unset = the table; 0 = every job on the f32 loop (A/B, bisecting); all = every job on the limb loop
-// (the per-configuration measurement and tests/test_gpu_wgrad_limbs.py)
+// (the per-configuration measurement and tests/test_gpu_wgrad_limbs.py); reg / staged (rsis_wgrad_staged_limbs) = the table here
 static bool wg_use_limbs(int ks, int tw, int code, int rag) {
   static const int mode = [] {
     const char* e = getenv("RSIS_WGRAD_LIMBS");

@@ -20,6 +20,7 @@ int rsis_l_blk_to_nchw(const void* x, float* y, int B, int C, int HW, hipStream_
 int rsis_launch_conv_blk_dec(BlkConvJob* jobs, int n, int epi, const int* force_variant, hipStream_t st);
 int rsis_launch_conv_wgrad(WgradArgs& a, int ks, hipStream_t st);
 bool rsis_wgrad_bf16_supported(const WgradArgs& w, int ks);
+int rsis_wgrad_staged_limbs(const WgradArgs& w, int ks);      // fp32 job: 1 = the staged limb kernels take it, 0 = not, -1 = forced and refused
 int rsis_launch_conv_wgrad_bf16_group(const WgradArgs* w, int n, int ks, hipStream_t st);
 int rsis_launch_conv_wgrad_bf16(const WgradArgs& w, int ks, hipStream_t st);
 int rsis_launch_conv_wgrad_tiled_group(const WgradArgs* w, int n, int ks, hipStream_t st);

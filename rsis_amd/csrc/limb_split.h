@@ -33,3 +33,33 @@ RSIS_LIMB_HD inline void rsis_limb_split3(const float v, float& l0, float& l1, f
   l1 = rsis_limb_hi16(r1);
   l2 = r1 - l1;
 }
+
+// two fp32 encodings -> one dword of two bf16 values by truncation: the high half of `even` in the low half, of `odd` in the high half
+RSIS_LIMB_HD inline unsigned rsis_limb_pair(const float even, const float odd) {
+  unsigned e, o;
+  __builtin_memcpy(&e, &even, 4);
+  __builtin_memcpy(&o, &odd, 4);
+  return (e >> 16) | (o & 0xFFFF0000u);
+}
+
+// Eight consecutive fp32 values -> three 16-byte cells (the staged limb kernels of conv_wgrad_bf16.hip: split ONCE per staged element).
+// Cell l holds limb l of all eight values, high halves only, element 2m in the low half of dword m and element 2m + 1 in its high
+// half: a cell is one lane's bf16x8 MFMA fragment, as wg_limb_pack8 (conv_wgrad_tiled.hip) builds it in registers.
+RSIS_LIMB_HD inline void rsis_limb_pack8_cells(const float (&v)[8], unsigned (&c0)[4], unsigned (&c1)[4], unsigned (&c2)[4]) {
+  for (int m = 0; m < 4; ++m) {
+    float lo[3], hi[3];
+    rsis_limb_split3(v[2 * m], lo[0], lo[1], lo[2]);
+    rsis_limb_split3(v[2 * m + 1], hi[0], hi[1], hi[2]);
+    c0[m] = rsis_limb_pair(v[2 * m], v[2 * m + 1]);      // (limb 0 is the high half of v itself)
+    c1[m] = rsis_limb_pair(lo[1], hi[1]);
+    c2[m] = rsis_limb_pair(lo[2], hi[2]);
+  }
+}
+
+// limb pairs (A limb, B limb) of one K16 step, smallest weight first: the six products with i + j <= 2 (weight >= 2^-16), the same six
+// as wg_limb_pa / wg_limb_pb of conv_wgrad_tiled.hip.  Among the three of weight 2^-16 and the two of weight 2^-8 the order is
+// (0,2) (2,0) (1,1) | (0,1) (1,0) | (0,0): B limb 2 is used first and then dead, B limb 1 lives over two adjacent products -- the 3x3
+// kernel holds 12 registers of shifted windows per B limb, and with all three live to the end it spilled.
+#define RSIS_LIMB_PRODUCTS 6
+#define RSIS_LIMB_PA(q) ((q) == 1 ? 2 : ((q) == 2 || (q) == 4 ? 1 : 0))
+#define RSIS_LIMB_PB(q) ((q) == 0 ? 2 : ((q) == 2 || (q) == 3 ? 1 : 0))
