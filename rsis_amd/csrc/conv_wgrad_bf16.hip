@@ -18,7 +18,7 @@
 //     a wave is transposed through LDS before the fp32 atomics so that consecutive lanes hit consecutive dW addresses.
 // Ragged maps (the 7/14/28/56/112-pixel pyramid of 224 x 224 inputs) need no special case: out-of-map pixels are zero-filled
 // when the tile is staged.  Split-K over spatial tiles / images with fp32 atomics into dW, as conv_wgrad_tiled.hip.
-// One launch path: every weight gradient, a single one included, runs on the *_group_kernel of its body through wgb_dispatch, and
+// One launch path: every weight gradient, a single one included, runs on the *_group_kernel of its body through wgb_launch_bucket, and
 // wgb_key alone says which instantiation a layer gets.
 //
 // LIMBS = 1 of the two register-staged bodies (wgrad3_limb_group_kernel / wgrad1_limb_group_kernel) is an fp32 path: the operands
@@ -32,83 +32,15 @@
 #include "common.h"
 #include "launchers.h"
 #include "limb_split.h"
+#include "wgrad_lanes.h"
+#include "wgrad_parts.h"
 #include <stdlib.h>
 #include <string.h>
-
-typedef __attribute__((address_space(3))) void* lds_vp_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define RSIS_OOB 0x7FFFFFF0u
-
-struct WgradBf16Args {
-  const float* dy;   // [B][CoutDy][H][W]
-  const float* x;    // [B][Cs][H][W]
-  float* dw;         // [Cout][ldo]
-  int B, Cs, H, W, Cout;
-  int ldo, n_off;
-  short interleave_hid;
-  short blk;         // dy and x are channel-blocked bf16 tensors (wgrad3_tr_body / wgrad1_tr_body)
-  int n_co_tiles, n_n_tiles, n_sp_tiles, tiles_per_split;
-};
-
-__device__ __forceinline__ unsigned wg_pack2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-
-// One staging task = 8 consecutive pixels of one row of one channel -> one 16-byte bf16 cell.
-// V4: two dwordx4 loads (W % 4 == 0: each is entirely inside or outside the row); otherwise 8 dword loads + a validity mask.
-template <bool V4>
-struct Task8 {
-  float v[8];
-  __device__ __forceinline__ void load(const __amdgpu_buffer_rsrc_t r, int off_elems, bool ok_row, int gx, int W) {
-    if constexpr (V4) {
-      const unsigned o0 = (ok_row && gx >= 0 && gx + 3 < W) ? (unsigned)off_elems * 4u : RSIS_OOB;
-      const unsigned o1 = (ok_row && gx + 4 >= 0 && gx + 7 < W) ? (unsigned)(off_elems + 4) * 4u : RSIS_OOB;
-      const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o0, 0, 0));
-      const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o1, 0, 0));
-      v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool ok = ok_row && (unsigned)(gx + i) < (unsigned)W;
-        v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, ok ? (unsigned)(off_elems + i) * 4u : RSIS_OOB, 0, 0));
-      }
-    }
-  }
-  __device__ __forceinline__ u32x4 cell() const {
-    u32x4 c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = wg_pack2(v[2 * k], v[2 * k + 1]);
-    return c;
-  }
-  // LIMBS: the three exact bf16 limbs of the 8 values (limb_split.h) as three cells, one per limb plane of the stage
-  __device__ __forceinline__ void limb_cells(u32x4 (&c)[3]) const {
-    unsigned q[3][4];
-    rsis_limb_pack8_cells(v, q[0], q[1], q[2]);
-#pragma unroll
-    for (int l = 0; l < 3; ++l) c[l] = u32x4{q[l][0], q[l][1], q[l][2], q[l][3]};
-  }
-};
 
 // ------------------------------------------------------------------------------------------------
 // 3x3: block = BM dy rows x 32 input channels x 9 taps; wave = 32 rows x 32 channels x 9 taps, the 4 / (BM / 32) wave copies of a
 // row group take alternate 16-pixel reduction steps.
 // ------------------------------------------------------------------------------------------------
-// The stage of a body: static LDS, or -- the limb stages are larger than the 64 KB a kernel may declare -- the dynamic LDS of the launch.
-template <int BYTES, bool DYN>
-__device__ __forceinline__ char* wgb_stage_lds() {
-  if constexpr (DYN) {
-    extern __shared__ __attribute__((aligned(1024))) char wgb_dyn_lds[];
-    return wgb_dyn_lds;
-  } else {
-    __shared__ __attribute__((aligned(16))) char wgb_static_lds[BYTES];
-    return wgb_static_lds;
-  }
-}
-
 // LIMBS = 1 (fp32 weight gradients on three exact bf16 limbs per operand, six products per K16 step, as the LIMB loop of
 // conv_wgrad_tiled.hip -- but every staged element is split ONCE, while its cell is stored): the stage is three PLANES of the bf16
 // stage's layout, plane l = limb l of every element, and the MFMA loop reads ready limb fragments: per K16 step 3 dy reads, and
@@ -118,20 +50,15 @@ __device__ __forceinline__ char* wgb_stage_lds() {
 template <int BM, int TW, int IN, int LIMBS = 0>
 __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
-  constexpr int TP = 64, TH = TP / TW, GPR = TW / 8, NG = TP / 8, KSTEPS = NG / 2;
-  constexpr int NPL = LIMBS ? 3 : 1, NBUF = LIMBS ? 1 : 2;        // limb planes of a stage; stages
+  using Geo = W3Stage<BM, TW, LIMBS>;
+  constexpr int TH = Geo::TH, GPR = Geo::GPR, NG = Geo::NG, KSTEPS = Geo::KSTEPS;
+  constexpr int PH = Geo::PH, XG = Geo::XG, PWP = Geo::PWP, ARS = Geo::ARS, CHSB = Geo::CHSB;
+  constexpr int A_BYTES = Geo::A_BYTES, ST_BYTES = Geo::ST_BYTES, NTA = Geo::NTA, XT = Geo::XT, NTX = Geo::NTX;
+  constexpr int NPL = Geo::NPL, NPROD = LIMBS ? RSIS_LIMB_PRODUCTS : 1;
   constexpr bool FLUSH = LIMBS && BM == 128;                      // (the chain of MFMA accumulations is cut per tile, see `tot`)
   constexpr int WGM = BM / 32, KSPW = 4 / WGM, NGG = KSTEPS / KSPW;
-  constexpr int PH = TH + 2, XG = GPR + 2, PWP = XG * 8;          // patch: PH rows of XG 8-pixel groups (tile columns start at 8)
-  constexpr int ARS = (TP + 8) * 2;                               // bytes per dy row (16 B padding)
-  constexpr int CHSB = (PH * PWP * 2 + 31) / 32 * 32 + 16;        // bytes per patch channel: an odd number of 16-byte slots
-  constexpr int A_BYTES = BM * ARS, X_BYTES = 32 * CHSB, ST_BYTES = A_BYTES + X_BYTES;
-  constexpr int NTA = BM * NG / 256;                              // dy tasks per thread
-  constexpr int XT = 32 * PH * XG, NTX = (XT + 255) / 256;        // patch tasks (per thread)
-  constexpr int RED_BYTES = 4 * 8 * 288 * 4;                      // epilogue transposition buffer: 8 rows x 288 n per wave
-  static_assert(WGM * KSPW == 4 && KSTEPS % KSPW == 0 && (BM * NG) % 256 == 0, "config");
-  constexpr int LDS_BYTES = NBUF * NPL * ST_BYTES > RED_BYTES ? NBUF * NPL * ST_BYTES : RED_BYTES;      // (w3_lds_bytes)
-  char* const lds = wgb_stage_lds<LDS_BYTES, LIMBS != 0>();
+  static_assert(WGM * KSPW == 4 && KSTEPS % KSPW == 0, "config");
+  char* const lds = wgb_stage_lds<Geo::LDS_BYTES, LIMBS != 0>();
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -202,25 +129,22 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
       for (int r = 0; r < 16; ++r) tot[t][r] = 0.f;
   }
 
-  // scalar tile cursor
-  int tb = t_begin / (tiles_x * tiles_y);
-  int trem = t_begin - tb * (tiles_x * tiles_y);
-  int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+  WgCursor cs(t_begin, tiles_x, tiles_y);                          // (scalar; of the NEXT tile to load)
 
   Task8<IN == 1> ra[NTA], rxp[NTX];
 #define W3_LOAD()                                                                                                  \
   {                                                                                                                \
-    const int y0 = ty * TH, x0 = tx * TW;                                                                          \
-    const float* ab = p.dy + ((size_t)tb * Cout + co0) * HW;                                                       \
+    const int y0 = cs.ty * TH, x0 = cs.tx * TW;                                                                          \
+    const float* ab = p.dy + ((size_t)cs.tb * Cout + co0) * HW;                                                       \
     const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)ab, 0, (Cout - co0) * HW * 4, 0x00020000); \
     const int tsc = y0 * W + x0;                                                                                   \
     _Pragma("unroll") for (int i = 0; i < NTA; ++i)                                                                \
       ra[i].load(ra_, a_off[i] + tsc, a_off[i] >= 0 && y0 + a_y[i] < H, x0 + a_x[i], W);                           \
-    const float* xb = p.x + ((size_t)tb * Cs + ci0) * HW;                                                          \
+    const float* xb = p.x + ((size_t)cs.tb * Cs + ci0) * HW;                                                          \
     const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (Cs - ci0) * HW * 4, 0x00020000); \
     _Pragma("unroll") for (int i = 0; i < NTX; ++i)                                                                \
       rxp[i].load(rx_, x_off[i] + tsc, x_off[i] < 0x20000000 && (unsigned)(y0 + x_y[i]) < (unsigned)H, x0 + x_x[i], W); \
-    if (++tx == tiles_x) { tx = 0; if (++ty == tiles_y) { ty = 0; ++tb; } }                                        \
+    cs.next(tiles_x, tiles_y);                                                                                     \
   }
 #define W3_STORE(BUF)                                                                                              \
   {                                                                                                                \
@@ -249,67 +173,34 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
   for (int t = 0; t < ntl; ++t) {
     const int cur = LIMBS ? 0 : t & 1;
     if (t + 1 < ntl) { W3_RETASK() W3_LOAD() }
-    if constexpr (LIMBS) {
-      const char* As = lds + a_base;
-      const char* Xs = lds + A_BYTES;
+    const char* As = lds + cur * ST_BYTES + a_base;
+    const char* Xs = lds + cur * ST_BYTES + A_BYTES;
 #pragma unroll
-      for (int gg = 0; gg < NGG; ++gg) {
-        bf16x8 a[3];
+    for (int gg = 0; gg < NGG; ++gg) {
+      bf16x8 a[NPL];
 #pragma unroll
-        for (int l = 0; l < 3; ++l) a[l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + (gg * KSPW + wk) * 32));
+      for (int l = 0; l < NPL; ++l) a[l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + (gg * KSPW + wk) * 32));
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          bf16x8 w[3][3];                                           // [limb][tap s]
+      for (int r = 0; r < 3; ++r) {
+        bf16x8 w[NPL][3];                                           // [plane][tap s]
 #pragma unroll
-          for (int l = 0; l < 3; ++l) {
-            const char* row = Xs + l * ST_BYTES + bo[gg] + r * PWP * 2;
-            const unsigned d0 = *(const unsigned*)(row - 4);
-            const u32x4 m = *(const u32x4*)row;
-            const unsigned d5 = *(const unsigned*)(row + 16);
-            const u32x4 w0 = {__builtin_amdgcn_alignbit(m[0], d0, 16), __builtin_amdgcn_alignbit(m[1], m[0], 16),
-                              __builtin_amdgcn_alignbit(m[2], m[1], 16), __builtin_amdgcn_alignbit(m[3], m[2], 16)};
-            const u32x4 w2 = {__builtin_amdgcn_alignbit(m[1], m[0], 16), __builtin_amdgcn_alignbit(m[2], m[1], 16),
-                              __builtin_amdgcn_alignbit(m[3], m[2], 16), __builtin_amdgcn_alignbit(d5, m[3], 16)};
-            w[l][0] = __builtin_bit_cast(bf16x8, w0); w[l][1] = __builtin_bit_cast(bf16x8, m); w[l][2] = __builtin_bit_cast(bf16x8, w2);
-          }
+        for (int l = 0; l < NPL; ++l) wg3_windows(Xs + l * ST_BYTES + bo[gg] + r * PWP * 2, w[l]);
 #pragma unroll
-          for (int q = 0; q < RSIS_LIMB_PRODUCTS; ++q)
+        for (int q = 0; q < NPROD; ++q)
 #pragma unroll
-            for (int s = 0; s < 3; ++s)
-              acc[r * 3 + s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[RSIS_LIMB_PA(q)], w[RSIS_LIMB_PB(q)][s], acc[r * 3 + s], 0, 0, 0);
-          // (32-wide tiles at two blocks per CU: the windows of the next row are not built above this row's MFMAs -- two rows of
-          //  them live at once spilled 21 registers, some of them reloaded between the prefetch loads)
-          if constexpr (BM < 128 && TW == 32) __builtin_amdgcn_sched_barrier(0);
-        }
+          for (int s = 0; s < 3; ++s)
+            acc[r * 3 + s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[LIMBS ? RSIS_LIMB_PA(q) : 0], w[LIMBS ? RSIS_LIMB_PB(q) : 0][s], acc[r * 3 + s], 0, 0, 0);
+        // (LIMBS on 32-wide tiles at two blocks per CU: the windows of the next row are not built above this row's MFMAs -- two
+        //  rows of them live at once spilled 21 registers, some of them reloaded between the prefetch loads)
+        if constexpr (LIMBS && BM < 128 && TW == 32) __builtin_amdgcn_sched_barrier(0);
       }
-      __syncthreads();                                              // every wave has read tile t: the one stage is free
-      if constexpr (FLUSH) {
+    }
+    if constexpr (LIMBS) __syncthreads();                           // ONE stage: every wave has read tile t, the stage is free
+    if constexpr (FLUSH) {
 #pragma unroll
-        for (int tt = 0; tt < 9; ++tt)
+      for (int tt = 0; tt < 9; ++tt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) { tot[tt][r] += acc[tt][r]; acc[tt][r] = 0.f; }
-      }
-    } else {
-      const char* As = lds + cur * ST_BYTES + a_base;
-      const char* Xs = lds + cur * ST_BYTES + A_BYTES;
-#pragma unroll
-      for (int gg = 0; gg < NGG; ++gg) {
-        const bf16x8 a = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + (gg * KSPW + wk) * 32));
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const char* row = Xs + bo[gg] + r * PWP * 2;
-          const unsigned d0 = *(const unsigned*)(row - 4);
-          const u32x4 m = *(const u32x4*)row;
-          const unsigned d5 = *(const unsigned*)(row + 16);
-          const u32x4 w0 = {__builtin_amdgcn_alignbit(m[0], d0, 16), __builtin_amdgcn_alignbit(m[1], m[0], 16),
-                            __builtin_amdgcn_alignbit(m[2], m[1], 16), __builtin_amdgcn_alignbit(m[3], m[2], 16)};
-          const u32x4 w2 = {__builtin_amdgcn_alignbit(m[1], m[0], 16), __builtin_amdgcn_alignbit(m[2], m[1], 16),
-                            __builtin_amdgcn_alignbit(m[3], m[2], 16), __builtin_amdgcn_alignbit(d5, m[3], 16)};
-          acc[r * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, w0), acc[r * 3 + 0], 0, 0, 0);
-          acc[r * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, m), acc[r * 3 + 1], 0, 0, 0);
-          acc[r * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, w2), acc[r * 3 + 2], 0, 0, 0);
-        }
-      }
+        for (int r = 0; r < 16; ++r) { tot[tt][r] += acc[tt][r]; acc[tt][r] = 0.f; }
     }
     if (t + 1 < ntl) { W3_RETASK() W3_STORE(LIMBS ? 0 : cur ^ 1) }
     __syncthreads();
@@ -323,41 +214,7 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
     for (int t = 0; t < 9; ++t) acc[t] = tot[t];
   }
 
-  // ---- epilogue: the KSPW wave copies of a row group first sum their partial tiles in LDS (fewer same-address atomics: they are
-  // serialised by the L2), 8 rows x 288 columns at a time; the rows are then split over the copies and added to dW with the lanes
-  // running along n (consecutive addresses) ----
-  float* red = (float*)lds + wm * (8 * 288);
-  const int nvalid = min(32, Cs - ci0) * 9;                        // valid columns of this block's 288
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int k = 0; k < KSPW; ++k) {
-      if (wk == k) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float* d = red + (r + 4 * hi) * 288 + l31 * 9 + t;
-            if (k == 0) *d = acc[t][4 * q + r];
-            else *d += acc[t][4 * q + r];
-          }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int rr = wk; rr < 8; rr += KSPW) {
-      const int co = co0 + wm * 32 + 8 * q + rr;
-      if (co >= Cout) continue;
-      const int orow = p.interleave_hid > 0 ? (co & 3) * p.interleave_hid + (co >> 2) : co;
-      float* dst = p.dw + (size_t)orow * p.ldo + p.n_off + ci0 * 9;
-#pragma unroll
-      for (int c = 0; c < 5; ++c) {
-        const int n = c * 64 + lane;
-        if (n < nvalid) atomicAdd(dst + n, red[rr * 288 + n]);
-      }
-    }
-    __syncthreads();
-  }
+  WG3_REDUCE_TILES()
 #endif
 }
 
@@ -377,7 +234,6 @@ __device__ __forceinline__ void wgrad3_bf16_body(const WgradBf16Args& p, const i
 // ------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
-#define RSIS_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 // The transposing reads are inline asm: behind the intrinsic (__builtin_amdgcn_ds_read_tr16_b64_*) hipcc waits vmcnt(0) before the first
 // read of every tile -- for the DMA of the NEXT tile, issued a few instructions earlier -- and the ring degenerates to load-then-compute
 // (measured: 2.9 us per 128-pixel tile and block whatever NR; plain ds_read_b64 in the same place gets no such wait).  The asm reads are
@@ -398,18 +254,12 @@ __device__ __forceinline__ bf16x8 tr_cat(const s16x4 lo, const s16x4 hi) {
 template <int BM, int TW, int TH, int NR>
 __device__ __forceinline__ void wgrad3_tr_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
-  constexpr int TP = TW * TH, NK = TP / 16;
+  using Geo = W3Ring<BM, TW, TH, NR>;
+  constexpr int NK = Geo::NK, PW = Geo::PW, XPX = Geo::XPX, NA = Geo::NA, NX = Geo::NX;
+  constexpr int C_DMA = Geo::C_DMA, ST_BYTES = Geo::ST_BYTES, X_OFF = Geo::X_OFF;
   constexpr int WGM = BM / 32, KSPW = 4 / WGM, NGG = NK / KSPW;
-  constexpr int PW = TW + 2, PH = TH + 2, XPX = PH * PW;
-  constexpr int NA = WGM * NK;                       // DMA instructions of the dy tile (slab-major, 16 pixels each)
-  constexpr int NX = (XPX + 15) / 16;                // ... of the input patch (row-major with halo, PW pixels per row)
-  constexpr int C_DMA = (NA + NX + 3) / 4;           // per wave and stage (short waves issue all-OOB fillers: one vmcnt rule)
-  constexpr int ST_BYTES = 4 * C_DMA * 1024, X_OFF = NA * 1024;
-  constexpr int RED_BYTES = 4 * 8 * 288 * 4;
-  constexpr int LDS_BYTES = NR * ST_BYTES > RED_BYTES ? NR * ST_BYTES : RED_BYTES;
-  static_assert(WGM * KSPW == 4 && NK % KSPW == 0 && TW % 8 == 0 && NR >= 2 && NR <= 5, "config");
-  static_assert((NR - 2) * C_DMA < 64 && LDS_BYTES <= 160 * 1024, "vmcnt is 6 bits; LDS of a CU");
-  extern __shared__ __attribute__((aligned(1024))) char lds[];      // w3t_lds_bytes<BM, TW, TH, NR>() at launch
+  static_assert(WGM * KSPW == 4 && NK % KSPW == 0, "config");
+  char* const lds = wgb_stage_lds<Geo::LDS_BYTES, true>();
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -444,24 +294,20 @@ __device__ __forceinline__ void wgrad3_tr_body(const WgradBf16Args& p, const int
   const char* const x_base = (const char*)p.x + (size_t)(ci0 >> 3) * HW * 16;
   const int a_len = ((Cout - co0) >> 3) * HW * 16, x_len = ((Cs - ci0) >> 3) * HW * 16;
 
-  // scalar tile cursor (of the NEXT tile to fetch)
-  int tb = t_begin / (tiles_x * tiles_y);
-  int trem = t_begin - tb * (tiles_x * tiles_y);
-  int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+  WgCursor cs(t_begin, tiles_x, tiles_y);            // (scalar; of the NEXT tile to fetch)
 #define W3T_ISSUE(SLOT)                                                                                            \
   {                                                                                                                \
-    const int y0 = ty * TH, x0 = tx * TW;                                                                          \
-    const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)(a_base + tb * a_img), 0, a_len, 0x00020000); \
-    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)(x_base + tb * x_img), 0, x_len, 0x00020000); \
+    const int y0 = cs.ty * TH, x0 = cs.tx * TW;                                                                    \
+    const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)(a_base + cs.tb * a_img), 0, a_len, 0x00020000); \
+    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)(x_base + cs.tb * x_img), 0, x_len, 0x00020000); \
     char* const sd = lds + (SLOT) * ST_BYTES + wave * 1024;                                                        \
     _Pragma("unroll") for (int i = 0; i < C_DMA; ++i) {                                                            \
       const int gy = y0 + d_y[i], gx = x0 + d_x[i];                                                                \
       const bool ok = d_cb[i] >= 0 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;                    \
       const unsigned off = ok ? (unsigned)(d_cb[i] + gy * W + gx) * 16u : RSIS_OOB;                                \
-      if (d_a[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (lds_vp_t)(sd + i * 4096), 16, off, 0, 0, 0);      \
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_, (lds_vp_t)(sd + i * 4096), 16, off, 0, 0, 0);            \
+      wg_dma(d_a[i], ra_, rx_, sd, i * 4096, off);                                                                \
     }                                                                                                              \
-    if (++tx == tiles_x) { tx = 0; if (++ty == tiles_y) { ty = 0; ++tb; } }                                        \
+    cs.next(tiles_x, tiles_y);                                                                                     \
   }
 
   // ---- per-lane operand bases (bytes inside a stage) ----
@@ -487,13 +333,7 @@ __device__ __forceinline__ void wgrad3_tr_body(const WgradBf16Args& p, const int
   for (int i = 0; i < NR - 1; ++i)
     if (i < ntl) W3T_ISSUE(i)
   for (int t = 0; t < ntl; ++t) {
-    {   // tile t has landed once at most `ahead` younger tiles of this wave's DMA are still in flight
-      const int ahead = min(NR - 2, ntl - 1 - t);
-      if (NR >= 5 && ahead == 3) { RSIS_VMCNT(3 * C_DMA); }
-      else if (NR >= 4 && ahead == 2) { RSIS_VMCNT(2 * C_DMA); }
-      else if (NR >= 3 && ahead == 1) { RSIS_VMCNT(C_DMA); }
-      else { RSIS_VMCNT(0); }
-    }
+    wg_ring_wait<NR, C_DMA>(t, ntl);
     __builtin_amdgcn_s_barrier();                     // tile t is in LDS (every wave's share); slot (t - 1) % NR is free
     if (t + NR - 1 < ntl) W3T_ISSUE((t + NR - 1) % NR)
     // K steps of this wave, software-pipelined over the LDS queue: the reads of (step, patch row r) are re-issued for the next step
@@ -533,40 +373,7 @@ __device__ __forceinline__ void wgrad3_tr_body(const WgradBf16Args& p, const int
   }
 #undef W3T_ISSUE
   __syncthreads();
-
-  // ---- epilogue (as wgrad3_bf16_body) ----
-  float* red = (float*)lds + wm * (8 * 288);
-  const int nvalid = min(32, Cs - ci0) * 9;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int k = 0; k < KSPW; ++k) {
-      if (wk == k) {
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float* d = red + (r + 4 * hi) * 288 + l31 * 9 + t;
-            if (k == 0) *d = acc[t][4 * q + r];
-            else *d += acc[t][4 * q + r];
-          }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int rr = wk; rr < 8; rr += KSPW) {
-      const int co = co0 + wm * 32 + 8 * q + rr;
-      if (co >= Cout) continue;
-      const int orow = p.interleave_hid > 0 ? (co & 3) * p.interleave_hid + (co >> 2) : co;
-      float* dst = p.dw + (size_t)orow * p.ldo + p.n_off + ci0 * 9;
-#pragma unroll
-      for (int c = 0; c < 5; ++c) {
-        const int n = c * 64 + lane;
-        if (n < nvalid) atomicAdd(dst + n, red[rr * 288 + n]);
-      }
-    }
-    __syncthreads();
-  }
+  WG3_REDUCE_TILES()
 #endif
 }
 // ------------------------------------------------------------------------------------------------
@@ -577,14 +384,12 @@ __device__ __forceinline__ void wgrad3_tr_body(const WgradBf16Args& p, const int
 template <int BM, int BN, int TP, int NR>
 __device__ __forceinline__ void wgrad1_tr_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
-  constexpr int WGM = 2, WGN = 2, TM = BM / WGM / 32, TN = BN / WGN / 32, NK = TP / 16;
-  constexpr int SA = BM / 32, SB = BN / 32;            // channel slabs of the dy / x tiles
-  constexpr int ND = (SA + SB) * NK;                   // DMA instructions per stage (16 pixels x 4 channel blocks each)
-  constexpr int C_DMA = (ND + 3) / 4;
-  constexpr int ST_BYTES = 4 * C_DMA * 1024, B_OFF = SA * NK * 1024;
+  using Geo = W1Ring<BM, BN, TP, NR>;
+  constexpr int NK = Geo::NK, SA = Geo::SA, ND = Geo::ND, C_DMA = Geo::C_DMA, ST_BYTES = Geo::ST_BYTES, B_OFF = Geo::B_OFF;
+  constexpr int WGM = 2, WGN = 2, TM = BM / WGM / 32, TN = BN / WGN / 32;
   constexpr int NRD = 2 * (TM + TN);                   // LDS reads per K step
-  static_assert(TM >= 1 && TN >= 1 && NR >= 2 && NR <= 4 && (NR - 2) * C_DMA < 64 && NRD <= 15 && NR * ST_BYTES <= 160 * 1024, "config");
-  extern __shared__ __attribute__((aligned(1024))) char lds[];      // NR * ST_BYTES at launch
+  static_assert(TM >= 1 && TN >= 1 && NRD <= 15, "config");
+  char* const lds = wgb_stage_lds<Geo::LDS_BYTES, true>();
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -612,20 +417,19 @@ __device__ __forceinline__ void wgrad1_tr_body(const WgradBf16Args& p, const int
   const char* const x_base = (const char*)p.x + (size_t)(n0 >> 3) * HW * 16;
   const int a_len = ((Cout - co0) >> 3) * HW * 16, x_len = ((Cs - n0) >> 3) * HW * 16;
 
-  int tb = t_begin / tiles_x, tx = t_begin - tb * tiles_x;
+  WgCursor cs(t_begin, tiles_x, 1);
 #define W1T_ISSUE(SLOT)                                                                                            \
   {                                                                                                                \
-    const int x0 = tx * TP;                                                                                        \
-    const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)(a_base + tb * a_img), 0, a_len, 0x00020000); \
-    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)(x_base + tb * x_img), 0, x_len, 0x00020000); \
+    const int x0 = cs.tx * TP;                                                                                     \
+    const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)(a_base + cs.tb * a_img), 0, a_len, 0x00020000); \
+    const __amdgpu_buffer_rsrc_t rx_ = __builtin_amdgcn_make_buffer_rsrc((void*)(x_base + cs.tb * x_img), 0, x_len, 0x00020000); \
     char* const sd = lds + (SLOT) * ST_BYTES + wave * 1024;                                                        \
     _Pragma("unroll") for (int i = 0; i < C_DMA; ++i) {                                                            \
       const int gx = x0 + d_px[i];                                                                                 \
       const unsigned off = (d_cb[i] >= 0 && gx < HW) ? (unsigned)(d_cb[i] + gx) * 16u : RSIS_OOB;                  \
-      if (d_a[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (lds_vp_t)(sd + i * 4096), 16, off, 0, 0, 0);      \
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_, (lds_vp_t)(sd + i * 4096), 16, off, 0, 0, 0);            \
+      wg_dma(d_a[i], ra_, rx_, sd, i * 4096, off);                                                                \
     }                                                                                                              \
-    if (++tx == tiles_x) { tx = 0; ++tb; }                                                                         \
+    cs.next(tiles_x, 1);                                                                                           \
   }
 
   const int q16 = lane & 15, grp = lane >> 4;
@@ -646,12 +450,7 @@ __device__ __forceinline__ void wgrad1_tr_body(const WgradBf16Args& p, const int
   for (int i = 0; i < NR - 1; ++i)
     if (i < ntl) W1T_ISSUE(i)
   for (int t = 0; t < ntl; ++t) {
-    {
-      const int ahead = min(NR - 2, ntl - 1 - t);
-      if (NR >= 4 && ahead == 2) { RSIS_VMCNT(2 * C_DMA); }
-      else if (NR >= 3 && ahead == 1) { RSIS_VMCNT(C_DMA); }
-      else { RSIS_VMCNT(0); }
-    }
+    wg_ring_wait<NR, C_DMA>(t, ntl);
     __builtin_amdgcn_s_barrier();
     if (t + NR - 1 < ntl) W1T_ISSUE((t + NR - 1) % NR)
     const unsigned sa = lds0 + (t % NR) * ST_BYTES + a_lane, sbb = lds0 + (t % NR) * ST_BYTES + b_lane;
@@ -689,42 +488,14 @@ __device__ __forceinline__ void wgrad1_tr_body(const WgradBf16Args& p, const int
 #undef W1T_READ
   }
 #undef W1T_ISSUE
-
-  // (buffer atomics, as wgrad1_bf16_body)
-  const __amdgpu_buffer_rsrc_t rdw = __builtin_amdgcn_make_buffer_rsrc((void*)p.dw, 0, (unsigned)((size_t)Cout * p.ldo * 4), 0x00020000);
-  const int ihid = p.interleave_hid;
-  const unsigned ldb = (unsigned)p.ldo * 4u;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * TN * 32 + j * 32 + l31;
-    if (n >= Cs) continue;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row0 = co0 + wm * TM * 32 + i * 32 + 4 * hi;
-      const int rows_left = Cout - row0;
-      const unsigned vo = (unsigned)((ihid > 0 ? row0 >> 2 : row0) * p.ldo + p.n_off + n) * 4u;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int k = (r & 3) + 8 * (r >> 2);
-        const unsigned ro = (unsigned)(ihid > 0 ? (r & 3) * ihid + 2 * (r >> 2) : k) * ldb;
-        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc[i][j][r], rdw, k < rows_left ? vo + ro : 0x7FFFFFF0u, 0, 0);
-      }
-    }
-  }
+  wg_atomic_tiles<TM, TN>(acc, p.dw, Cout, p.ldo, p.n_off, p.interleave_hid, co0 + wm * TM * 32 + 4 * hi, n0 + wn * TN * 32 + l31, Cs);
 #endif
 }
-template <int BM, int BN, int TP, int NR>
-constexpr int w1t_lds_bytes() { return NR * 4 * (((BM / 32 + BN / 32) * (TP / 16) + 3) / 4) * 1024; }
 #ifndef W1T_TP
 #define W1T_TP 64
 #endif
 constexpr int w1t_nr(int bm, int bn) { return (bm + bn) >= 256 ? 2 : 3; }
 
-template <int BM, int TW, int TH, int NR>
-constexpr int w3t_lds_bytes() {
-  constexpr int st = 4 * ((BM / 32 * (TW * TH / 16) + ((TH + 2) * (TW + 2) + 15) / 16 + 3) / 4) * 1024;
-  return NR * st > 4 * 8 * 288 * 4 ? NR * st : 4 * 8 * 288 * 4;
-}
 // tile height / ring depth of the (BM, TW) instantiations: the deepest tile whose ring fits 64 KB of static LDS, two blocks per CU
 #ifndef W3T_TH_32_32      // (tuning builds override the three configurations that carry the step: -DW3T_TH_32_32=.. -DW3T_NR_32_32=.. ...)
 #define W3T_TH_32_32 4
@@ -753,14 +524,12 @@ constexpr int w3t_nr(int bm, int tw) {
 template <int BM, int BN, int WGM, int WGN, int TW, int IN, int LIMBS = 0>
 __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const int bx, const int by) {
 #if __HIP_DEVICE_COMPILE__
-  constexpr int TP = 64, TH = TP / TW, GPR = TW / 8, NG = TP / 8, KSTEPS = NG / 2;
-  constexpr int NPL = LIMBS ? 3 : 1, NBUF = LIMBS ? 1 : 2;
-  constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
-  constexpr int ARS = (TP + 8) * 2;
-  constexpr int A_BYTES = BM * ARS, B_BYTES = BN * ARS, ST_BYTES = A_BYTES + B_BYTES;
-  constexpr int NTA = BM * NG / 256, NTB = BN * NG / 256;
-  static_assert(WGM * WGN == 4 && (BM * NG) % 256 == 0 && (BN * NG) % 256 == 0, "config");
-  char* const lds = wgb_stage_lds<NBUF * NPL * ST_BYTES, LIMBS != 0>();      // (w1_lds_bytes)
+  using Geo = W1Stage<BM, BN, LIMBS>;
+  constexpr int TH = Geo::TP / TW, GPR = TW / 8, NG = Geo::NG, KSTEPS = Geo::KSTEPS;
+  constexpr int ARS = Geo::ARS, A_BYTES = Geo::A_BYTES, ST_BYTES = Geo::ST_BYTES, NTA = Geo::NTA, NTB = Geo::NTB;
+  constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32, NPL = Geo::NPL, NPROD = LIMBS ? RSIS_LIMB_PRODUCTS : 1;
+  static_assert(WGM * WGN == 4, "config");
+  char* const lds = wgb_stage_lds<Geo::LDS_BYTES, LIMBS != 0>();
 
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -774,23 +543,9 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
   if (t_begin >= t_end) return;
 
   int a_off[NTA], a_y[NTA], a_x[NTA], a_lds[NTA];
-#pragma unroll
-  for (int i = 0; i < NTA; ++i) {
-    const int e = tid + i * 256;
-    const int row = e / NG, G = e % NG;
-    a_y[i] = G / GPR; a_x[i] = (G % GPR) * 8;
-    a_off[i] = co0 + row < Cout ? row * HW + a_y[i] * W + a_x[i] : -1;
-    a_lds[i] = row * ARS + G * 16;
-  }
+  wg_row_tasks<NTA, NG, GPR, ARS>(tid, co0, Cout, HW, W, a_off, a_y, a_x, a_lds);
   int b_off[NTB], b_y[NTB], b_x[NTB], b_lds[NTB];
-#pragma unroll
-  for (int i = 0; i < NTB; ++i) {
-    const int e = tid + i * 256;
-    const int row = e / NG, G = e % NG;
-    b_y[i] = G / GPR; b_x[i] = (G % GPR) * 8;
-    b_off[i] = n0 + row < Cs ? row * HW + b_y[i] * W + b_x[i] : -1;
-    b_lds[i] = row * ARS + G * 16;
-  }
+  wg_row_tasks<NTB, NG, GPR, ARS>(tid, n0, Cs, HW, W, b_off, b_y, b_x, b_lds);
   const int a_base = (wm * TM * 32 + l31) * ARS + hi * 16;
   const int b_base = (wn * TN * 32 + l31) * ARS + hi * 16;
 
@@ -802,9 +557,7 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  int tb = t_begin / (tiles_x * tiles_y);
-  int trem = t_begin - tb * (tiles_x * tiles_y);
-  int ty = trem / tiles_x, tx = trem - ty * tiles_x;
+  WgCursor cs(t_begin, tiles_x, tiles_y);
 
   // LIMBS: every tile starts from zero accumulators, added to `tot` on the VALU (see wgrad3_bf16_body)
   [[maybe_unused]] f32x16 tot[LIMBS ? TM : 1][LIMBS ? TN : 1];
@@ -820,17 +573,17 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
   Task8<IN == 1> ra[NTA], rb[NTB];
 #define W1_LOAD()                                                                                                  \
   {                                                                                                                \
-    const int y0 = ty * TH, x0 = tx * TW;                                                                          \
+    const int y0 = cs.ty * TH, x0 = cs.tx * TW;                                                                          \
     const int tsc = y0 * W + x0;                                                                                   \
-    const float* ab = p.dy + ((size_t)tb * Cout + co0) * HW;                                                       \
+    const float* ab = p.dy + ((size_t)cs.tb * Cout + co0) * HW;                                                       \
     const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)ab, 0, (Cout - co0) * HW * 4, 0x00020000); \
     _Pragma("unroll") for (int i = 0; i < NTA; ++i)                                                                \
       ra[i].load(ra_, a_off[i] + tsc, a_off[i] >= 0 && y0 + a_y[i] < H, x0 + a_x[i], W);                           \
-    const float* xb = p.x + ((size_t)tb * Cs + n0) * HW;                                                           \
+    const float* xb = p.x + ((size_t)cs.tb * Cs + n0) * HW;                                                           \
     const __amdgpu_buffer_rsrc_t rb_ = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (Cs - n0) * HW * 4, 0x00020000); \
     _Pragma("unroll") for (int i = 0; i < NTB; ++i)                                                                \
       rb[i].load(rb_, b_off[i] + tsc, b_off[i] >= 0 && y0 + b_y[i] < H, x0 + b_x[i], W);                           \
-    if (++tx == tiles_x) { tx = 0; if (++ty == tiles_y) { ty = 0; ++tb; } }                                        \
+    cs.next(tiles_x, tiles_y);                                                                                     \
   }
 #define W1_STORE(BUF)                                                                                              \
   {                                                                                                                \
@@ -857,49 +610,34 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
   for (int t = 0; t < ntl; ++t) {
     const int cur = LIMBS ? 0 : t & 1;
     if (t + 1 < ntl) W1_LOAD()
-    if constexpr (LIMBS) {
-      const char* As = lds + a_base;
-      const char* Bs = lds + A_BYTES + b_base;
+    const char* As = lds + cur * ST_BYTES + a_base;
+    const char* Bs = lds + cur * ST_BYTES + A_BYTES + b_base;
 #pragma unroll
-      for (int g = 0; g < KSTEPS; ++g) {
-        bf16x8 a[TM][3], b[TN][3];
+    for (int g = 0; g < KSTEPS; ++g) {
+      bf16x8 a[TM][NPL], b[TN][NPL];
 #pragma unroll
-        for (int l = 0; l < 3; ++l) {
+      for (int l = 0; l < NPL; ++l) {
 #pragma unroll
-          for (int i = 0; i < TM; ++i) a[i][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + i * 32 * ARS + g * 32));
+        for (int i = 0; i < TM; ++i) a[i][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + l * ST_BYTES + i * 32 * ARS + g * 32));
 #pragma unroll
-          for (int j = 0; j < TN; ++j) b[j][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(Bs + l * ST_BYTES + j * 32 * ARS + g * 32));
-        }
-#pragma unroll
-        for (int q = 0; q < RSIS_LIMB_PRODUCTS; ++q)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][RSIS_LIMB_PA(q)], b[j][RSIS_LIMB_PB(q)], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < TN; ++j) b[j][l] = __builtin_bit_cast(bf16x8, *(const u32x4*)(Bs + l * ST_BYTES + j * 32 * ARS + g * 32));
       }
-      __syncthreads();                                              // every wave has read tile t: the one stage is free
+#pragma unroll
+      for (int q = 0; q < NPROD; ++q)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][LIMBS ? RSIS_LIMB_PA(q) : 0], b[j][LIMBS ? RSIS_LIMB_PB(q) : 0], acc[i][j], 0, 0, 0);
+    }
+    if constexpr (LIMBS) {
+      __syncthreads();                                              // ONE stage: every wave has read tile t, the stage is free
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
-    } else {
-      const char* As = lds + cur * ST_BYTES + a_base;
-      const char* Bs = lds + cur * ST_BYTES + A_BYTES + b_base;
-#pragma unroll
-      for (int g = 0; g < KSTEPS; ++g) {
-        bf16x8 a[TM], b[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a[i] = __builtin_bit_cast(bf16x8, *(const u32x4*)(As + i * 32 * ARS + g * 32));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b[j] = __builtin_bit_cast(bf16x8, *(const u32x4*)(Bs + j * 32 * ARS + g * 32));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
     }
     if (t + 1 < ntl) W1_STORE(LIMBS ? 0 : cur ^ 1)
     __syncthreads();
@@ -913,27 +651,7 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
       for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j];
   }
 
-  // (buffer atomics, as in conv_wgrad_tiled.hip)
-  const __amdgpu_buffer_rsrc_t rdw = __builtin_amdgcn_make_buffer_rsrc((void*)p.dw, 0, (unsigned)((size_t)Cout * p.ldo * 4), 0x00020000);
-  const int ihid = p.interleave_hid;
-  const unsigned ldb = (unsigned)p.ldo * 4u;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * TN * 32 + j * 32 + l31;
-    if (n >= Cs) continue;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row0 = co0 + wm * TM * 32 + i * 32 + 4 * hi;
-      const int rows_left = Cout - row0;
-      const unsigned vo = (unsigned)((ihid > 0 ? row0 >> 2 : row0) * p.ldo + p.n_off + n) * 4u;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int k = (r & 3) + 8 * (r >> 2);
-        const unsigned ro = (unsigned)(ihid > 0 ? (r & 3) * ihid + 2 * (r >> 2) : k) * ldb;
-        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc[i][j][r], rdw, k < rows_left ? vo + ro : 0x7FFFFFF0u, 0, 0);
-      }
-    }
-  }
+  wg_atomic_tiles<TM, TN>(acc, p.dw, Cout, p.ldo, p.n_off, p.interleave_hid, co0 + wm * TM * 32 + 4 * hi, n0 + wn * TN * 32 + l31, Cs);
 #endif
 }
 
@@ -942,140 +660,58 @@ __device__ __forceinline__ void wgrad1_bf16_body(const WgradBf16Args& p, const i
 //  to 150-190 VGPRs + 144 AGPRs, one wave per SIMD, and a loop whose every s_waitcnt / barrier stalls the whole SIMD; held to 256
 //  registers (no AGPRs, at most 9 spilled in three fp32-operand variants) two blocks share a CU and the bf16 224^2 step went
 //  19.66 -> 18.80 ms.  LDS allows two blocks in every variant.)
-// The launch is a GROUP: the weight gradients of many layers in one grid (rsis_conv2d_wgrad_batch; see conv_wgrad_tiled.hip), the
-// jobs travelling by value in the kernel arguments.  A single weight gradient (rsis_conv2d_wgrad, and every job of the
-// deterministic mode) is a group of one job in the PLAIN mode below.
-//
-// XCD placement of a grouped launch.  A (job, range of consecutive splits) ITEM -- all dW tiles of one job over one range of its
-// spatial tiles -- runs on ONE XCD: its blocks re-read the same dy / x pixels once per dW tile (4-16 times each), and only inside
-// one L2 are those re-reads hits.  With consecutive block indices spread round-robin over the eight XCDs every XCD fetched the pixels
-// again: the bf16 1x1 group read 6.1 GB where 1.5 GB are needed and ran AT the fabric's rate (6 TB/s; rocprofv3 --pmc FETCH_SIZE per
-// kernel, tools/step_traffic.py) -- with the MFMA 16x faster than in fp32 these launches are what the memory system lets them be.
-// Hardware sends block b to XCD b % 8, so the grid is eight interleaved LANES: lane x is the blocks b = 8 k + x and holds a list of
-// items (k ranges); the host balances the lanes by work (longest item first).  (The exact-f32 weight gradients are MFMA-bound: the
-// same placement halved their reads and changed their time by nothing, NOTES.md (21).)
-#define RSIS_WGB_MAXJ 32
-#define RSIS_WGB_LANE_ITEMS 28
-struct WgradBf16Group {
-  int n;
-  int lane_n[8];                                  // lane_n[0] < 0: the plain mode, see wgb_find
-  int lane_start[8][RSIS_WGB_LANE_ITEMS + 1];     // first k of each item of a lane, ascending; [lane_n] = the lane's block count
-  unsigned short lane_split0[8][RSIS_WGB_LANE_ITEMS];   // an item covers the consecutive splits split0, split0 + 1, ... of its job
-  unsigned char lane_job[8][RSIS_WGB_LANE_ITEMS];
-  WgradBf16Args job[RSIS_WGB_MAXJ];
-};
-static_assert(sizeof(WgradBf16Group) <= 4000, "kernel arguments are limited to 4 KB");
-
-// block -> (job, tile, split); false: a padding block of a short lane
-// Plain mode (a launch of ONE job on its own): no lanes -- a job with fewer than eight splits, as every job of the deterministic mode,
-// would leave XCDs idle behind padding blocks -- but exactly tiles * splits blocks, block b = (tile b % tiles, split b / tiles): the
-// order of a (tiles, splits) grid.
-__device__ __forceinline__ bool wgb_find(const WgradBf16Group& g, int& job, int& tile, int& split) {
-  if (g.lane_n[0] < 0) {                                          // (uniform: a scalar branch)
-    const int ntile = g.job[0].n_co_tiles * g.job[0].n_n_tiles;
-    job = 0; tile = blockIdx.x % ntile; split = blockIdx.x / ntile;
-    return true;
-  }
-  const int x = blockIdx.x & 7, k = blockIdx.x >> 3;
-  const int nl = g.lane_n[x];
-  if (k >= g.lane_start[x][nl]) return false;
-  int i = 0;
-  while (i + 1 < nl && g.lane_start[x][i + 1] <= k) ++i;        // (uniform: scalar code)
-  job = g.lane_job[x][i];
-  const int kl = k - g.lane_start[x][i], ntile = g.job[job].n_co_tiles * g.job[job].n_n_tiles;
-  tile = kl % ntile;
-  split = g.lane_split0[x][i] + kl / ntile;
-  return true;
-}
+// The launch is a GROUP of jobs placed on the eight XCD lanes, a single weight gradient a group of one in the plain mode: wgrad_lanes.h.
+struct WgbBlockIdx { __device__ __forceinline__ unsigned operator()() const { return blockIdx.x; } };      // wgb_find's block index
 template <int BM, int TW, int IN>
 __global__ __launch_bounds__(256, 2) void wgrad3_bf16_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad3_bf16_body<BM, TW, IN>(g.job[j], tile, split);
 }
+// (the rings are dynamic LDS, up to 80 KB: two blocks per CU)
 template <int BM, int TW, int TH, int NR>
 __global__ __launch_bounds__(256, 2) void wgrad3_tr_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad3_tr_body<BM, TW, TH, NR>(g.job[j], tile, split);
-}
-// the ring is dynamic LDS (up to 80 KB: two blocks per CU); sizes above 64 KB are an opt-in per kernel
-template <int BM, int TW, int TH, int NR>
-static void w3t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
-  constexpr int lds = w3t_lds_bytes<BM, TW, TH, NR>();
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad3_tr_group_kernel<BM, TW, TH, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad3_tr_group_kernel<BM, TW, TH, NR>), dim3(blocks), dim3(256), lds, st, g);
 }
 template <int BM, int BN, int TP, int NR>
 __global__ __launch_bounds__(256, 2) void wgrad1_tr_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad1_tr_body<BM, BN, TP, NR>(g.job[j], tile, split);
-}
-template <int BM, int BN, int TP, int NR>
-static void w1t_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
-  constexpr int lds = w1t_lds_bytes<BM, BN, TP, NR>();
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad1_tr_group_kernel<BM, BN, TP, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad1_tr_group_kernel<BM, BN, TP, NR>), dim3(blocks), dim3(256), lds, st, g);
 }
 template <int BM, int BN, int WGM, int WGN, int TW, int IN>
 __global__ __launch_bounds__(256) void wgrad1_bf16_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad1_bf16_body<BM, BN, WGM, WGN, TW, IN>(g.job[j], tile, split);
 }
 // The staged limb kernels (LIMBS = 1 of the two register-staged bodies).  Their one stage of three limb planes is dynamic LDS:
 // 3x3 52-103 KB (BM = 32 / 64: two blocks per CU; BM = 128: one, and with it the whole register file), 1x1 55-111 KB.
-template <int BM, int TW>
-constexpr int w3l_lds_bytes() {
-  constexpr int PH = 64 / TW + 2, PWP = (TW / 8 + 2) * 8, CHSB = (PH * PWP * 2 + 31) / 32 * 32 + 16;
-  constexpr int st = 3 * (BM * (64 + 8) * 2 + 32 * CHSB);
-  return st > 4 * 8 * 288 * 4 ? st : 4 * 8 * 288 * 4;
-}
-template <int BM, int BN>
-constexpr int w1l_lds_bytes() { return 3 * (BM + BN) * (64 + 8) * 2; }
 template <int BM, int TW, int IN>
 __global__ __launch_bounds__(256, BM == 128 ? 1 : 2) void wgrad3_limb_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad3_bf16_body<BM, TW, IN, 1>(g.job[j], tile, split);
 }
 template <int BM, int BN, int IN>
 __global__ __launch_bounds__(256) void wgrad1_limb_group_kernel(const WgradBf16Group g) {
   int j, tile, split;
-  if (!wgb_find(g, j, tile, split)) return;
+  if (!wgb_find(g, WgbBlockIdx{}, j, tile, split)) return;
   wgrad1_bf16_body<BM, BN, 2, 2, 64, IN, 1>(g.job[j], tile, split);
 }
-template <int BM, int TW, int IN>
-static void w3l_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
-  constexpr int lds = w3l_lds_bytes<BM, TW>();
-  static_assert(lds <= 160 * 1024, "LDS of a CU");
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad3_limb_group_kernel<BM, TW, IN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad3_limb_group_kernel<BM, TW, IN>), dim3(blocks), dim3(256), lds, st, g);
-}
-template <int BM, int BN, int IN>
-static void w1l_launch_group(const WgradBf16Group& g, int blocks, hipStream_t st) {
-  constexpr int lds = w1l_lds_bytes<BM, BN>();
-  static_assert(lds <= 160 * 1024, "LDS of a CU");
-  static const hipError_t once = hipFuncSetAttribute((const void*)wgrad1_limb_group_kernel<BM, BN, IN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)once;
-  hipLaunchKernelGGL((wgrad1_limb_group_kernel<BM, BN, IN>), dim3(blocks), dim3(256), lds, st, g);
-}
 
-// the split of a job that is launched on its own
-static void split_plan(WgradBf16Args& a, int TW, int TH, int ntile, int slots) {
-  a.n_sp_tiles = a.B * rsis_cdiv(a.H, TH) * rsis_cdiv(a.W, TW);
-  // Every split adds a dW-sized pass of fp32 atomics, and those run at ~0.3 T atomics/s whatever the layer: measured on the
-  // trunk shapes at batch 32 (tools/exp/bf16_shape_sweep.py), one block per CU (256 slots) beats two (512) on every layer --
-  // 4.4 vs 5.7 ms per step -- although the main loop alone is no faster (2.7 vs 2.6 ms): the second block only buys atomics.
-  int nsplit = ntile >= slots ? 1 : slots / ntile;
-  if (nsplit > 256) nsplit = 256;
-  if (nsplit > a.n_sp_tiles / 2) nsplit = a.n_sp_tiles / 2;
-  if (nsplit < 1 || rsis_deterministic()) nsplit = 1;
-  a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
+// The one launcher: DYN_LDS = Geo::DYN_BYTES of the kernel's body, the same constant the body lays its stage out by; sizes above
+// 64 KB are an opt-in per kernel, made once.
+typedef void (*WgbLaunchFn)(const WgradBf16Group&, int, hipStream_t);
+template <auto Kernel, int DYN_LDS>
+static void wgb_launch(const WgradBf16Group& g, int blocks, hipStream_t st) {
+  if constexpr (DYN_LDS > 0) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DYN_LDS);
+    (void)once;
+  }
+  hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(256), DYN_LDS, st, g);
 }
 
 // stride 1, "same" padding, 32-bit offsets inside one image slab
@@ -1151,121 +787,55 @@ static WgbKey wgb_key(const WgradBf16Args& a, int ks, int limbs) {
 }
 static inline bool wgb_same(const WgbKey& a, const WgbKey& b) { return a.ks == b.ks && a.bm == b.bm && a.bn == b.bn && a.tw == b.tw && a.v4 == b.v4 && a.limbs == b.limbs; }
 
-// `alone`: the jobs are ONE job that rsis_launch_conv_wgrad_bf16 launches on its own -- split_plan, plain mode; otherwise every block
-// of the bucket walks ~L spatial tiles and the blocks are placed on the XCD lanes
-template <typename LaunchFn>
-static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, bool alone, LaunchFn launch) {
-  const int TH = k.th;
-  long total = 0;
-  for (int j = 0; j < n; ++j) {
-    WgradBf16Args& a = jobs[j];
-    a.n_co_tiles = rsis_cdiv(a.Cout, k.bm);
-    a.n_n_tiles = rsis_cdiv(a.Cs, k.bn);
-    a.n_sp_tiles = a.B * rsis_cdiv(a.H, TH) * rsis_cdiv(a.W, k.tw);
-    total += (long)a.n_co_tiles * a.n_n_tiles * a.n_sp_tiles;
-  }
-  if (alone) {
-    WgradBf16Group g = {};
-    const int ntile = jobs[0].n_co_tiles * jobs[0].n_n_tiles;
-    split_plan(jobs[0], k.tw, TH, ntile, 256);
-    g.n = 1;
-    g.lane_n[0] = -1;
-    g.job[0] = jobs[0];
-    launch(g, ntile * rsis_cdiv(jobs[0].n_sp_tiles, jobs[0].tiles_per_split));
-    return rsis_check_launch();
-  }
-  static const int env_tb = getenv("RSIS_WGB_GROUP_BLOCKS") ? atoi(getenv("RSIS_WGB_GROUP_BLOCKS")) : 0;     // tuning knob
-  // (swept at the bench geometry, 224^2 / batch 32, with two blocks per CU resident: 640 18.77 ms per step, 768 18.51, 896 18.43,
-  //  1024 18.79, 1280 18.53, 1536 18.52, 1792 18.52 -- twice each, reproducible to 0.02; 1024 happens to cut the layer-3 jobs badly)
-  const long target_blocks = env_tb > 0 ? env_tb : 896;
-  long L = (total + target_blocks - 1) / target_blocks;
-  if (L < 2) L = 2;
-  if (rsis_deterministic()) L = 1L << 40;
-  int j0 = 0;
-  while (j0 < n) {
-    WgradBf16Group g = {};
-    // items of this launch: a job with up to 8 splits is one item per split, a job with more is 8 items of consecutive splits
-    struct Item { int job, split, blocks; long work; };
-    Item items[8 * RSIS_WGB_LANE_ITEMS];
-    int ni = 0, nj = 0;
-    while (j0 + nj < n && nj < RSIS_WGB_MAXJ) {
-      WgradBf16Args a = jobs[j0 + nj];
-      int nsplit = rsis_cdiv(a.n_sp_tiles, L);
-      if (nsplit < 1) nsplit = 1;
-      if (nsplit > 60000) nsplit = 60000;
-      a.tiles_per_split = rsis_cdiv(a.n_sp_tiles, nsplit);
-      nsplit = rsis_cdiv(a.n_sp_tiles, a.tiles_per_split);
-      const int nit = nsplit < 8 ? nsplit : 8;
-      if (ni + nit > 8 * RSIS_WGB_LANE_ITEMS) break;            // (nj >= 1 here: one job is at most 8 items)
-      const int ntile = a.n_co_tiles * a.n_n_tiles;
-      for (int it = 0; it < nit; ++it) {
-        const int s0 = (int)((long)nsplit * it / nit), s1 = (int)((long)nsplit * (it + 1) / nit);
-        const long tiles = (long)(s1 < nsplit ? (long)s1 * a.tiles_per_split : a.n_sp_tiles) - (long)s0 * a.tiles_per_split;
-        items[ni++] = Item{nj, s0, ntile * (s1 - s0), (long)ntile * tiles};
-      }
-      g.job[nj++] = a;
-    }
-    g.n = nj;
-    for (int x = 1; x < ni; ++x)           // longest item first onto the least loaded lane that still has a free slot
-      for (int y = x; y > 0 && items[y].work > items[y - 1].work; --y) { const Item t = items[y]; items[y] = items[y - 1]; items[y - 1] = t; }
-    long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int blocks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < ni; ++i) {
-      int best = -1;
-      for (int x = 0; x < 8; ++x)
-        if (g.lane_n[x] < RSIS_WGB_LANE_ITEMS && (best < 0 || load[x] < load[best])) best = x;
-      const int e = g.lane_n[best]++;
-      g.lane_start[best][e] = blocks[best];
-      g.lane_job[best][e] = (unsigned char)items[i].job;
-      g.lane_split0[best][e] = (unsigned short)items[i].split;
-      blocks[best] += items[i].blocks;
-      load[best] += items[i].work;
-    }
-    int maxb = 0;
-    for (int x = 0; x < 8; ++x) { g.lane_start[x][g.lane_n[x]] = blocks[x]; if (blocks[x] > maxb) maxb = blocks[x]; }
-    launch(g, 8 * maxb);
-    if (rsis_check_launch() != RSIS_OK) return RSIS_ERR_LAUNCH;
-    j0 += nj;
-  }
-  return RSIS_OK;
-}
-
+// the kernel and the geometry of a key
 #define WGB3(BMv, TWv)                                                                                             \
   if (k.bm == BMv && k.tw == TWv) {                                                                                \
-    if (k.limbs && k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {      \
-      w3l_launch_group<BMv, TWv, 1>(g, blocks, st); });                                                            \
-    if (k.limbs) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                   \
-      w3l_launch_group<BMv, TWv, 0>(g, blocks, st); });                                                            \
-    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
-      w3t_launch_group<BMv, TWv, w3t_th(BMv, TWv), w3t_nr(BMv, TWv)>(g, blocks, st); });                           \
-    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
-      hipLaunchKernelGGL((wgrad3_bf16_group_kernel<BMv, TWv, 1>), dim3(blocks), dim3(256), 0, st, g); });          \
-    return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                                \
-      hipLaunchKernelGGL((wgrad3_bf16_group_kernel<BMv, TWv, 0>), dim3(blocks), dim3(256), 0, st, g); });          \
+    using Ring = W3Ring<BMv, TWv, w3t_th(BMv, TWv), w3t_nr(BMv, TWv)>;                                             \
+    if (k.limbs) return k.v4 == 1 ? wgb_launch<wgrad3_limb_group_kernel<BMv, TWv, 1>, W3Stage<BMv, TWv, 1>::DYN_BYTES> \
+                                  : wgb_launch<wgrad3_limb_group_kernel<BMv, TWv, 0>, W3Stage<BMv, TWv, 1>::DYN_BYTES>; \
+    if (k.v4 == 2) return wgb_launch<wgrad3_tr_group_kernel<BMv, TWv, w3t_th(BMv, TWv), w3t_nr(BMv, TWv)>, Ring::DYN_BYTES>; \
+    return k.v4 == 1 ? wgb_launch<wgrad3_bf16_group_kernel<BMv, TWv, 1>, W3Stage<BMv, TWv, 0>::DYN_BYTES>          \
+                     : wgb_launch<wgrad3_bf16_group_kernel<BMv, TWv, 0>, W3Stage<BMv, TWv, 0>::DYN_BYTES>;         \
   }
 #define WGB1(BMv, BNv)                                                                                             \
   if (k.bm == BMv && k.bn == BNv) {                                                                                \
-    if (k.limbs && k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {      \
-      w1l_launch_group<BMv, BNv, 1>(g, blocks, st); });                                                            \
-    if (k.limbs) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                   \
-      w1l_launch_group<BMv, BNv, 0>(g, blocks, st); });                                                            \
-    if (k.v4 == 2) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
-      w1t_launch_group<BMv, BNv, W1T_TP, w1t_nr(BMv, BNv)>(g, blocks, st); });                                     \
-    if (k.v4 == 1) return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                 \
-      hipLaunchKernelGGL((wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 1>), dim3(blocks), dim3(256), 0, st, g); });      \
-    return wgb_launch_bucket(jobs, n, k, alone, [&](const WgradBf16Group& g, int blocks) {                                \
-      hipLaunchKernelGGL((wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 0>), dim3(blocks), dim3(256), 0, st, g); });      \
+    using Ring = W1Ring<BMv, BNv, W1T_TP, w1t_nr(BMv, BNv)>;                                                       \
+    if (k.limbs) return k.v4 == 1 ? wgb_launch<wgrad1_limb_group_kernel<BMv, BNv, 1>, W1Stage<BMv, BNv, 1>::DYN_BYTES> \
+                                  : wgb_launch<wgrad1_limb_group_kernel<BMv, BNv, 0>, W1Stage<BMv, BNv, 1>::DYN_BYTES>; \
+    if (k.v4 == 2) return wgb_launch<wgrad1_tr_group_kernel<BMv, BNv, W1T_TP, w1t_nr(BMv, BNv)>, Ring::DYN_BYTES>; \
+    return k.v4 == 1 ? wgb_launch<wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 1>, W1Stage<BMv, BNv, 0>::DYN_BYTES> \
+                     : wgb_launch<wgrad1_bf16_group_kernel<BMv, BNv, 2, 2, 64, 0>, W1Stage<BMv, BNv, 0>::DYN_BYTES>; \
   }
-static int wgb_dispatch(WgradBf16Args* jobs, int n, const WgbKey& k, bool alone, hipStream_t st) {
+static WgbLaunchFn wgb_launcher(const WgbKey& k) {
   if (k.ks == 3) {
     WGB3(32, 32) WGB3(64, 32) WGB3(128, 32) WGB3(32, 16) WGB3(64, 16) WGB3(128, 16) WGB3(32, 8) WGB3(64, 8) WGB3(128, 8)
   } else {
     WGB1(64, 64) WGB1(64, 128) WGB1(128, 64) WGB1(128, 128)
   }
-  return RSIS_ERR_ARG;
+  return nullptr;
 }
 #undef WGB3
 #undef WGB1
+// Count tiles, plan, launch (wgrad_lanes.h).  `alone`: ONE job that rsis_launch_conv_wgrad_bf16 launches on its own -- split_plan,
+// plain mode; otherwise XCD lanes, in as many launches as the group's tables need.
+static int wgb_launch_bucket(WgradBf16Args* jobs, int n, const WgbKey& k, bool alone, hipStream_t st) {
+  const WgbLaunchFn launch = wgb_launcher(k);
+  if (!launch) return RSIS_ERR_ARG;
+  const long total = wgb_count_tiles(jobs, n, k.bm, k.bn, k.tw, k.th);
+  static const int env_tb = getenv("RSIS_WGB_GROUP_BLOCKS") ? atoi(getenv("RSIS_WGB_GROUP_BLOCKS")) : 0;     // tuning knob
+  // (swept at the bench geometry, 224^2 / batch 32, with two blocks per CU resident: 640 18.77 ms per step, 768 18.51, 896 18.43,
+  //  1024 18.79, 1280 18.53, 1536 18.52, 1792 18.52 -- twice each, reproducible to 0.02; 1024 happens to cut the layer-3 jobs badly)
+  const long target_blocks = env_tb > 0 ? env_tb : 896;
+  WgradBf16Group g;
+  for (int j0 = 0; j0 < n;) {
+    const WgbPlan pl = alone ? wgb_plan_alone(g, jobs[j0], rsis_deterministic())
+                             : wgb_plan_lanes(g, jobs + j0, n - j0, total, target_blocks, rsis_deterministic());
+    launch(g, pl.blocks, st);
+    if (rsis_check_launch() != RSIS_OK) return RSIS_ERR_LAUNCH;
+    j0 += pl.jobs;
+  }
+  return RSIS_OK;
+}
 
 // n weight gradients that rsis_wgrad_bf16_supported accepts, all with the same kernel size
 static int wgb_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipStream_t st) {
@@ -1289,7 +859,7 @@ static int wgb_launch_jobs(const WgradArgs* w, int n, int ks, bool alone, hipStr
     int m = 0;
     for (int i = j; i < n; ++i)
       if (key[i].ks >= 0 && wgb_same(key[i], k)) { bucket[m++] = all[i]; key[i].ks = -1; }
-    rc = wgb_dispatch(bucket, m, k, alone, st);
+    rc = wgb_launch_bucket(bucket, m, k, alone, st);
   }
   free(all); free(key);
   return rc;

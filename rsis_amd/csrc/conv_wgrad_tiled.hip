@@ -38,15 +38,16 @@
 #include "launchers.h"
 #include "limb_split.h"
 #include "wgrad_block_order.h"
+#include "wgrad_parts.h"
 #include <stdlib.h>
 #include <string.h>
 
-typedef __attribute__((address_space(3))) void* lds_vp_t;
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
 
 // limb pairs (A limb, B limb) of one K16 step, smallest weight first.  The first WG_LIMB_PRODUCTS are issued: 6 = the pairs with
-// i + j <= 2; 9 would be the exact product
+// i + j <= 2; 9 would be the exact product.  (RSIS_LIMB_PA / PB of limb_split.h issue the same six in ANOTHER order, for the staged
+// kernels' register budget; the order is the bits of a dW, so the two lists stay apart on purpose.)
 #define WG_LIMB_PRODUCTS 6
 [[maybe_unused]] __device__ constexpr int wg_limb_pa[9] = {2, 1, 0, 1, 0, 0, 2, 1, 2};
 [[maybe_unused]] __device__ constexpr int wg_limb_pb[9] = {0, 1, 2, 0, 1, 0, 1, 2, 2};
@@ -76,8 +77,6 @@ struct WgradTiledArgs {
   int ldo, n_off, interleave_hid;
   int n_co_tiles, n_n_tiles, n_sp_tiles, tiles_per_split;
 };
-
-#define RSIS_OOB 0x7FFFFFF0u
 
 // KSP = 2: the block's four waves form a WGM x WGN grid TWICE; the two copies take alternate halves of every stage's reduction
 // depth and both add their partial tile with the (already atomic) epilogue -- lets a 32-row tile be only 64 columns wide.
@@ -348,28 +347,7 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
 #undef WG_LAND
 
   // ---- epilogue: fp32 atomics into dW (reference layout) ----
-  // (buffer atomics: a row of the tile is a per-lane base + a scalar multiple of ldo; the gate-interleaved rows 4 j + g of the
-  //  ConvLSTM weights go to row g * hid + j; rows >= Cout get an out-of-range offset and are dropped)
-  const __amdgpu_buffer_rsrc_t rdw = __builtin_amdgcn_make_buffer_rsrc((void*)p.dw, 0, (unsigned)((size_t)Cout * p.ldo * 4), 0x00020000);
-  const int ihid = p.interleave_hid;
-  const unsigned ldb = (unsigned)p.ldo * 4u;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * TN * 32 + j * 32 + l31;
-    if (n >= Nn) continue;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row0 = co0 + wm * TM * 32 + i * 32 + 4 * hi;       // (a multiple of 4)
-      const int rows_left = Cout - row0;
-      const unsigned vo = (unsigned)((ihid > 0 ? row0 >> 2 : row0) * p.ldo + p.n_off + n) * 4u;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int k = (r & 3) + 8 * (r >> 2);
-        const unsigned ro = (unsigned)(ihid > 0 ? (r & 3) * ihid + 2 * (r >> 2) : k) * ldb;
-        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc[i][j][r], rdw, k < rows_left ? vo + ro : 0x7FFFFFF0u, 0, 0);
-      }
-    }
-  }
+  wg_atomic_tiles<TM, TN>(acc, p.dw, Cout, p.ldo, p.n_off, p.interleave_hid, co0 + wm * TM * 32 + 4 * hi, n0 + wn * TN * 32 + l31, Nn);
 #endif
 }
 

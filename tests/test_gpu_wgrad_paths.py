@@ -5,8 +5,14 @@ alone, and this build must reproduce the parent build's bits on every launch pat
 
   * fp32 on aligned maps: one case per tile width of each kernel size; on ragged maps: RAG 1 and RAG 2; a ConvLSTM gate conv
     (two sources, gate-interleaved dy rows);
-  * bf16 operands on fp32 storage (DTYPE_BF16): 3x3 and 1x1, W % 4 (1x1: H * W % 4) both ways;
-  * blk operands (DTYPE_BF16_BLK): the DMA kernels at 8-, 16- and 32-wide tiles, and the 1x1.
+  * bf16 operands on fp32 storage (DTYPE_BF16): the _C3 + _C1 shapes of tests/test_gpu_wgrad_staged.py, which reach every
+    (ks, BM, TW | BN, V4) instantiation of the register-staged kernels (test_every_instantiation_has_a_case there; the same wgb_key
+    rule routes DTYPE_BF16 jobs);
+  * blk operands (DTYPE_BF16_BLK): the DMA kernels at 8-, 16- and 32-wide tiles and every (BM, TW) -- the W3T_SHAPES of
+    tests/test_gpu_blk.py with whole 8-channel blocks, without its 112^2 and 56^2 maps -- and the 1x1 at every (BM, BN).
+
+Every family runs twice: job by job through rsis_conv2d_wgrad (the plain mode of wgb_find: one job, no lanes) and as ONE
+rsis_conv2d_wgrad_batch call (the lane mode: a job's tiles found through the lane tables).
 
 The parent's dW is a dump that the parent build writes with this file as a script
 (`RSIS_HIP_LIB=<parent library> python tests/test_gpu_wgrad_paths.py gpu_jobs/wgrad_paths_parent_dw.pt`), a measurement, not a
@@ -22,6 +28,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_gpu_wgrad_staged import _C1, _C3  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 # family -> [(B, [Cin segs], H, W, Cout, ks, lstm_hid)]; every conv is stride 1, "same" padding
@@ -29,8 +39,13 @@ CASES = {
     "fp32_aligned": [(2, [16], 16, 16, 32, 3, 0), (2, [32], 16, 16, 128, 3, 0), (2, [256], 16, 16, 64, 1, 0), (2, [64], 8, 32, 96, 1, 0)],
     "fp32_ragged": [(2, [8], 9, 11, 16, 3, 0), (2, [16], 28, 28, 32, 3, 0)],
     "fp32_convlstm": [(2, [24, 8], 16, 16, 32, 3, 8)],
-    "bf16": [(2, [16], 16, 16, 32, 3, 0), (2, [64], 14, 14, 64, 3, 0), (2, [64], 16, 16, 128, 1, 0), (3, [40], 7, 7, 24, 1, 0)],
-    "blk": [(3, [40], 14, 14, 24, 3, 0), (5, [16], 7, 7, 8, 3, 0), (2, [64], 28, 28, 48, 3, 0), (2, [64], 16, 16, 64, 1, 0)],
+    "bf16": _C3 + _C1,
+    "blk": [(3, [40], 14, 14, 24, 3, 0), (5, [16], 7, 7, 8, 3, 0), (2, [64], 28, 28, 48, 3, 0), (2, [64], 16, 16, 64, 1, 0),
+            # W3T_SHAPES of tests/test_gpu_blk.py with Cin % 8 == 0 and Cout % 8 == 0 (the first two are the two cases above)
+            (2, [520], 28, 28, 72, 3, 0), (2, [520], 14, 14, 72, 3, 0), (3, [520], 7, 7, 72, 3, 0), (8, [128], 7, 7, 128, 3, 0),
+            (3, [48], 33, 20, 16, 3, 0), (2, [72], 5, 11, 136, 3, 0),
+            # one 1x1 per (BM, BN)
+            (2, [64], 8, 8, 64, 1, 0), (2, [64], 8, 8, 136, 1, 0), (2, [136], 8, 8, 64, 1, 0), (2, [136], 8, 8, 136, 1, 0)],
 }
 FAMILIES = list(CASES)
 PARENT_DUMP = os.path.join(ROOT, "gpu_jobs", "wgrad_paths_parent_dw.pt")
@@ -46,10 +61,11 @@ def _blk(t):
     return t.reshape(B, C // 8, 8, H, W).permute(0, 1, 3, 4, 2).contiguous().to(torch.bfloat16)
 
 
-def _run():
-    """deterministic-mode dW of every case, on top of pre-filled contents, through rsis_conv2d_wgrad: {family: [dW, ...]}"""
+def _run(grouped=False):
+    """deterministic-mode dW of every case, on top of pre-filled contents, through rsis_conv2d_wgrad or (grouped) one
+    rsis_conv2d_wgrad_batch call per family: {family: [dW, ...]}"""
     from rsis_amd import ops
-    from rsis_amd._lib import check, lib, ptr, stream
+    from rsis_amd._lib import WgradJob, check, lib, ptr, stream
     L = lib()
     out = {}
     prev_mode = ops.set_deterministic(True)
@@ -57,6 +73,7 @@ def _run():
         for f, family in enumerate(FAMILIES):
             dtype = {"bf16": ops.DTYPE_BF16, "blk": ops.DTYPE_BF16_BLK}.get(family, ops.DTYPE_F32)
             out[family] = []
+            jobs, keep = [], []
             for k, (B, segs, H, W, Cout, ks, hid) in enumerate(CASES[family]):
                 seed = 100 * f + 10 * k
                 Ctot = sum(segs)
@@ -69,19 +86,36 @@ def _run():
                 for i, c in enumerate(segs):
                     x = _rng_t(33000 + seed + i, (B, c, H, W))
                     xd = (_blk(x) if family == "blk" else x).cuda()
-                    check(L.rsis_conv2d_wgrad(ptr(dy), ptr(xd), ptr(dW), B, c, H, W, Cout, H, W, ks, 1, ks // 2, Ctot, c_off, hid, dtype, stream()),
-                          "rsis_conv2d_wgrad")
+                    if grouped:
+                        j = WgradJob()
+                        (j.dy, j.x, j.dW, j.B, j.Cs, j.H, j.W, j.Cout, j.Ho, j.Wo, j.ks, j.stride, j.pad, j.Ctot, j.c_off, j.lstm_hid, j.dtype) = (
+                            dy.data_ptr(), xd.data_ptr(), dW.data_ptr(), B, c, H, W, Cout, H, W, ks, 1, ks // 2, Ctot, c_off, hid, dtype)
+                        jobs.append(j)
+                        keep.append(xd)
+                    else:
+                        check(L.rsis_conv2d_wgrad(ptr(dy), ptr(xd), ptr(dW), B, c, H, W, Cout, H, W, ks, 1, ks // 2, Ctot, c_off, hid, dtype,
+                                                  stream()), "rsis_conv2d_wgrad")
                     c_off += c
-                torch.cuda.synchronize()
-                out[family].append(dW.cpu())
+                keep.append(dy)
+                out[family].append(dW)
+            if grouped:
+                check(L.rsis_conv2d_wgrad_batch((WgradJob * len(jobs))(*jobs), len(jobs), stream()), "rsis_conv2d_wgrad_batch")
+            torch.cuda.synchronize()
+            out[family] = [t.cpu() for t in out[family]]
     finally:
         ops.set_deterministic(prev_mode)
     return out
 
 
+def _run_all():
+    out = _run()
+    out.update({"grouped_" + f: v for f, v in _run(True).items()})
+    return out
+
+
 @pytest.fixture(scope="module")
 def runs():
-    return _run(), _run()
+    return _run_all(), _run_all()
 
 
 @pytest.mark.parametrize("family", FAMILIES)
@@ -94,11 +128,27 @@ def test_single_launch_reproduces_the_parent_build(runs, family):
         assert torch.isfinite(a).all() and torch.equal(a, b), "%s case %r: the deterministic dW differs from the parent build's" % (family, c)
 
 
+@pytest.mark.parametrize("family", FAMILIES)
+def test_grouped_launch_reproduces_the_parent_build(runs, family):
+    if not os.path.exists(PARENT_DUMP):
+        pytest.skip("no dump of the parent build's dW at gpu_jobs/wgrad_paths_parent_dw.pt")
+    parent = torch.load(PARENT_DUMP)
+    assert len(parent["grouped_" + family]) == len(CASES[family])
+    for c, a, b in zip(CASES[family], runs[0]["grouped_" + family], parent["grouped_" + family]):
+        assert torch.isfinite(a).all() and torch.equal(a, b), "%s case %r: the grouped deterministic dW differs from the parent build's" % (family, c)
+
+
 @pytest.mark.parametrize("family", ["bf16", "blk"])
 def test_bf16_single_launch_is_deterministic(runs, family):
     for c, a, b in zip(CASES[family], runs[0][family], runs[1][family]):
         assert torch.isfinite(a).all() and torch.equal(a, b), "%s case %r: two deterministic calls differ" % (family, c)
 
 
+@pytest.mark.parametrize("family", ["bf16", "blk"])
+def test_bf16_grouped_launch_is_deterministic(runs, family):
+    for c, a, b in zip(CASES[family], runs[0]["grouped_" + family], runs[1]["grouped_" + family]):
+        assert torch.isfinite(a).all() and torch.equal(a, b), "%s case %r: two deterministic grouped calls differ" % (family, c)
+
+
 if __name__ == "__main__":
-    torch.save(_run(), sys.argv[1])
+    torch.save(_run_all(), sys.argv[1])

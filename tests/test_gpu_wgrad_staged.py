@@ -9,7 +9,8 @@ conv_wgrad_tiled.hip on the same inputs.  Bars, stated from the project's existi
     test_conv2d_wgrad_fp32_on_ragged_maps);
   * a single +inf in x: exactly the dW elements whose reduction contains it are non-finite, under RSIS_WGRAD_LIMBS=0 and =staged
     alike, and the rest stay inside the bars;
-  * RSIS_WGRAD_LIMBS=staged in deterministic mode: two calls give equal bits;
+  * RSIS_WGRAD_LIMBS=staged in deterministic mode: two calls give equal bits, and they are the parent build's bits (against a dump
+    the parent build wrote, single and grouped; skipped when there is none);
   * the default against RSIS_WGRAD_LIMBS=reg, both in deterministic mode: equal bits on every case (deterministic mode does not
     reroute);
   * under RSIS_WGRAD_LIMBS=staged a stride-2 3x3 and a Cout == 1 job return RSIS_ERR_UNSUPPORTED (no silent fallback), so every call
@@ -44,7 +45,7 @@ if ROOT not in sys.path:
 pytestmark = pytest.mark.gpu
 
 ERR_UNSUPPORTED = 3
-WGB_MAXJ = 32       # RSIS_WGB_MAXJ of conv_wgrad_bf16.hip: jobs per grouped launch
+WGB_MAXJ = 32       # RSIS_WGB_MAXJ of wgrad_lanes.h: jobs per grouped launch
 
 # (B, [Cin segs], H, W, Cout, ks, lstm_hid); stride 1, "same" padding
 _C3 = [
@@ -275,10 +276,38 @@ def test_deterministic_mode_does_not_reroute(runs, mode):
         assert torch.equal(_bits(a), _bits(b)), "case %d %r: the default and RSIS_WGRAD_LIMBS=reg differ in deterministic mode" % (k, CASES[k])
 
 
+PARENT_DUMP = os.path.join(ROOT, "gpu_jobs", "wgrad_staged_parent_dw.pt")
+
+
+@pytest.mark.parametrize("mode", ["single", "grouped"])
+def test_staged_reproduces_the_parent_build(runs, mode):
+    """RSIS_WGRAD_LIMBS=staged in deterministic mode against the bits of the parent build (one contributor per dW element, so the
+    bits are a function of the kernel alone).  The dump is a measurement the parent build writes with this file as a script
+    (`RSIS_WGRAD_LIMBS=staged RSIS_HIP_LIB=<parent library> python tests/test_gpu_wgrad_staged.py gpu_jobs/wgrad_staged_parent_dw.pt dump`),
+    not a golden."""
+    if not os.path.exists(PARENT_DUMP):
+        pytest.skip("no dump of the parent build's dW at gpu_jobs/wgrad_staged_parent_dw.pt")
+    parent = torch.load(PARENT_DUMP)
+    assert len(parent[mode]) == len(CASES)
+    for k, (a, b) in enumerate(zip(runs["staged"]["det_a_" + mode], parent[mode])):
+        assert torch.equal(_bits(a), _bits(b)), "case %d %r: RSIS_WGRAD_LIMBS=staged differs from the parent build" % (k, CASES[k])
+
+
+def _dump():
+    """the deterministic-mode dW of CASES, single and grouped (written under RSIS_WGRAD_LIMBS=staged by the parent build)"""
+    from rsis_amd import ops
+    assert os.environ.get("RSIS_WGRAD_LIMBS") == "staged", "the dump is of the staged kernels: run under RSIS_WGRAD_LIMBS=staged"
+    prev = ops.set_deterministic(True)
+    try:
+        return {"single": _run(CASES, False), "grouped": _run(CASES, True)}
+    finally:
+        ops.set_deterministic(prev)
+
+
 def test_staged_refuses_what_its_kernels_do_not_take(runs):
     assert runs["staged"]["refused"] == [ERR_UNSUPPORTED] * 4, runs["staged"]["refused"]
     assert runs["reg"]["refused"] == [0] * 4 and runs["table"]["refused"] == [0] * 4      # (the other modes route them as before)
 
 
 if __name__ == "__main__":
-    torch.save(_run_all(), sys.argv[1])
+    torch.save(_dump() if sys.argv[2:] == ["dump"] else _run_all(), sys.argv[1])
