@@ -12,17 +12,24 @@ alone, and this build must reproduce the parent build's bits on every launch pat
     tests/test_gpu_blk.py with whole 8-channel blocks, without its 112^2 and 56^2 maps -- and the 1x1 at every (BM, BN).
 
 Every family runs twice: job by job through rsis_conv2d_wgrad (the plain mode of wgb_find: one job, no lanes) and as ONE
-rsis_conv2d_wgrad_batch call (the lane mode: a job's tiles found through the lane tables).
+rsis_conv2d_wgrad_batch call.  Everything here runs in deterministic mode, where rsis_conv2d_wgrad_batch (api.hip: the
+`!rsis_deterministic()` condition in front of "grouped below") launches every job on its own: the batch call is one PLAIN-mode launch
+per job, one split, like the single run beside it -- it checks the batch entry's routing, not the lane tables.  The lane mode of
+wgb_find (default mode) is tests/test_gpu_wgrad_lanes.py.
 
 The parent's dW is a dump that the parent build writes with this file as a script
 (`RSIS_HIP_LIB=<parent library> python tests/test_gpu_wgrad_paths.py gpu_jobs/wgrad_paths_parent_dw.pt`), a measurement, not a
-golden; the comparison skips when there is none.  The bf16 kernels also have to give equal bits in two calls of this build."""
+golden; the comparison skips when there is none.  The bf16 kernels also have to give equal bits in two calls of this build, and
+their deterministic results, single and batch, lie within the ROUNDING bar of tests/wgrad_lane_cases.py around float64: one block walks
+every tile of its job here, so |err_ij| <= n 2^-23 (|prev_ij| + A_ij), the worst case of any fp32 summation of exactly representable
+terms (A: the float64 weight gradient of |dy|, |x| rounded to bf16; n = B H W)."""
 import os
 import sys
 
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -148,6 +155,43 @@ def test_bf16_single_launch_is_deterministic(runs, family):
 def test_bf16_grouped_launch_is_deterministic(runs, family):
     for c, a, b in zip(CASES[family], runs[0]["grouped_" + family], runs[1]["grouped_" + family]):
         assert torch.isfinite(a).all() and torch.equal(a, b), "%s case %r: two deterministic grouped calls differ" % (family, c)
+
+
+def _wgrad64(dy, x, Cout, ks):
+    w = torch.zeros(Cout, x.shape[1], ks, ks, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w, None, stride=1, padding=ks // 2).backward(dy)
+    return w.grad
+
+
+@pytest.fixture(scope="module")
+def float64_terms():
+    """{family: [(prev + g, n 2^-23 (|prev| + A)), ...]} of the bf16 and blk families, float64, on the inputs of _run rounded to bf16 (round
+    to nearest even; the blk operands are those values already)"""
+    out = {}
+    for f, family in enumerate(FAMILIES):
+        if family not in ("bf16", "blk"):
+            continue
+        out[family] = []
+        for k, (B, segs, H, W, Cout, ks, hid) in enumerate(CASES[family]):
+            seed = 100 * f + 10 * k
+            gy = _rng_t(31000 + seed, (B, Cout, H, W)).bfloat16().double()            # (reference row order: g * hid + j)
+            prev = _rng_t(32000 + seed, (Cout, sum(segs), ks, ks)).double()
+            x = torch.cat([_rng_t(33000 + seed + i, (B, c, H, W)) for i, c in enumerate(segs)], 1).bfloat16().double()
+            g, A = _wgrad64(gy, x, Cout, ks), _wgrad64(gy.abs(), x.abs(), Cout, ks)
+            out[family].append((prev + g, B * H * W * 2.0 ** -23 * (prev.abs() + A)))
+    return out
+
+
+@pytest.mark.parametrize("mode", ["single", "batch"])
+@pytest.mark.parametrize("family", ["bf16", "blk"])
+def test_bf16_deterministic_results_against_float64(runs, float64_terms, family, mode):
+    from helpers import assert_close
+    got = runs[0][family if mode == "single" else "grouped_" + family]
+    assert len(got) == len(CASES[family])
+    for c, a, (ref, bar) in zip(CASES[family], got, float64_terms[family]):
+        err = a.double() - ref
+        assert_close("%s %s case %r: |err| / ROUNDING (max |err| %.3e)" % (family, mode, c, float(err.abs().max())), err / bar,
+                     torch.zeros_like(err), 1.0)
 
 
 if __name__ == "__main__":
