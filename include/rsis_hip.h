@@ -469,6 +469,13 @@ int rsis_overlay_masks(const unsigned char* image, const unsigned char* masks, i
  * rsis_rle_to_bits: n masks from run counts (rsis_rle_encode's, or rsis_rle_from_string's): desc[k] = {first count, number of counts,
  *   first word, words} indexes counts[counts_len] / bits[bits_len]; ends[counts_len] is workspace.  sum(counts of k) must not exceed
  *   64 * words.
+ * rsis_poly_to_bits: n masks from COCO polygon segmentations, bit for bit what maskApi.c:161-201 rleFrPoly gives for each part and
+ *   :44-70 rleMerge (intersect = 0) for the parts of a record.  All tables in DEVICE memory: xy[2 * nverts] float64 (x, y) pairs,
+ *   parts[p] = {first vertex, vertices}, recs[r] = {first part, parts, h, w, first word, words, 0, 0} (h * w < 2^31, words >=
+ *   ceil(h * w / 64)); element x * h + y of record r is bit e % 64 of word bits[first word + e / 64].  scratch[bits_len] is workspace
+ *   (distinct from bits; the call zeroes what it uses), area[r] = set elements.  A record or part whose entries do not fit the
+ *   stated lengths is skipped.  Coordinates must be finite with |5 * coordinate| < 2^30 (the caller checks).  One block per record; its
+ *   time grows with the number of walk points, 5 * the sum over edges of max(|dx|, |dy|), and with parts * words.
  * rsis_mask_intersect_blocks / _batch: jobs[j] = {dt_off, gt_off, D, G, stride, out_off, block_begin, 0}: D detection and G ground-truth
  *   masks of `stride` words (even, as are the offsets: 16-byte cells) at bits + dt_off / gt_off; inter[out_off + d * G + g] = number of
  *   elements set in both.  Job j owns blocks [block_begin_j, block_begin_j + rsis_mask_intersect_blocks(D, G, stride)); inter[inter_len]
@@ -484,6 +491,8 @@ int rsis_overlay_masks(const unsigned char* image, const unsigned char* masks, i
 int rsis_mask_pack_bits(const unsigned char* masks, int n, long len, unsigned long long* bits, long stride, unsigned int* area, void* stream);
 int rsis_rle_to_bits(const unsigned int* counts, long counts_len, const long long* desc, int n, unsigned int* ends, unsigned long long* bits,
                      long bits_len, unsigned int* area, void* stream);
+int rsis_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n,
+                      unsigned long long* scratch, unsigned long long* bits, long bits_len, unsigned int* area, void* stream);
 long rsis_mask_intersect_blocks(long D, long G, long stride);
 int rsis_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks,
                               unsigned int* inter, long inter_len, void* stream);

@@ -1,11 +1,12 @@
 """COCO 'segm' evaluation on the device -- counterpart of the second half of reference src/eval.py (eval.py:365-398) and of the
 (modified) pycocotools COCOeval it calls (src/coco/PythonAPI/pycocotools/cocoeval.py), for iouType = 'segm' with masks as compressed
-RLE or as device tensors.  pycocotools itself is not used.
+RLE, as the polygons / uncompressed RLE of a standard COCO annotation file, or as device tensors.  pycocotools itself is not used.
 
-    python -m rsis_amd.cocoeval --gt GT.json --dt PRED.json [-max_dets N] [--ignore_cats] [--all_classes]
+    python -m rsis_amd.cocoeval --gt GT.json --dt PRED.json [-max_dets N] [--ignore_cats] [--all_classes] [--all_images]
 
-Where the work runs (rsis_amd/csrc/maskeval.hip): masks become 64-bit words on the device (rsis_mask_pack_bits from the uint8 output
-of rsis_mask_resize_threshold, rsis_rle_to_bits from run counts); ONE grouped launch counts the intersections of every (detection
+Where the work runs (rsis_amd/csrc/maskeval.hip, polymask.hip): masks become 64-bit words on the device (rsis_mask_pack_bits from the
+uint8 output of rsis_mask_resize_threshold, rsis_rle_to_bits from run counts, rsis_poly_to_bits from polygons: the rasterisation of
+maskApi.c rleFrPoly + rleMerge, bit for bit); ONE grouped launch counts the intersections of every (detection
 mask, ground-truth mask) pair of every image (rsis_mask_intersect_batch) -- once per pair of distinct masks, however many records
 (categories) share a mask; one launch forms the float64 IoU matrices of all (image, category) cells, one runs the greedy matching
 of all (image, category, area range) cells.  The host sorts (numpy, stable, vectorised over all records), and accumulates the few
@@ -89,6 +90,80 @@ def rle_to_bits(counts_list, lengths, device="cuda"):
     return [bits[int(boff[k]):int(boff[k + 1])] for k in range(n)], area
 
 
+def segmentation_kind(seg):
+    """The form of a COCO `segmentation`: 'rle' ({'size', 'counts': compressed text}), 'counts' ({'size', 'counts': list of run
+    lengths}: uncompressed RLE, how an annotation file stores crowd regions) or 'polygons' (a list of parts, each a flat list
+    [x0, y0, x1, y1, ...] of at least 3 points).  Anything else -- a bare box, a part with an odd count or fewer than 3 points, a
+    coordinate that is not finite or too large for the 5x integer grid of the rasteriser -- raises ValueError."""
+    if isinstance(seg, dict):
+        if "counts" not in seg or "size" not in seg or len(seg["size"]) != 2:
+            raise ValueError("an RLE segmentation needs 'size': [h, w] and 'counts'")
+        c = seg["counts"]
+        if isinstance(c, (list, tuple)):
+            return "counts"
+        if isinstance(c, (str, bytes)):
+            return "rle"
+        raise ValueError("RLE 'counts' must be compressed text or a list of run lengths, not %s" % type(c).__name__)
+    if not isinstance(seg, (list, tuple)) or len(seg) == 0:
+        raise ValueError("a segmentation is an RLE dict or a non-empty list of polygon parts")
+    for part in seg:
+        if not isinstance(part, (list, tuple, np.ndarray)):
+            raise ValueError("a polygon segmentation is a list of parts, each a list [x0, y0, x1, y1, ...] (a bare box is not a mask)")
+        if len(part) < 6 or len(part) % 2:
+            raise ValueError("a polygon part needs at least 3 points and an even number of coordinates, not %d numbers" % len(part))
+        try:
+            v = np.asarray(part, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("polygon coordinates must be numbers")
+        if v.ndim != 1 or not np.isfinite(v).all() or (np.abs(5.0 * v) >= 2.0 ** 30).any():
+            raise ValueError("polygon coordinates must be finite with |5 * coordinate| < 2^30")
+    return "polygons"
+
+
+def poly_to_bits(parts_per_record, sizes, device="cuda"):
+    """parts_per_record: n records, each a list of polygon parts [x0, y0, x1, y1, ...]; sizes: their images' (h, w) -> (list of n
+    (words,) int64 device rows, area (n,) int32 device tensor), the form rle_to_bits returns.  A record's mask is the union of its
+    parts, each rasterised as the COCO mask API does (rsis_amd/csrc/polymask.hip); one launch for all records of the call."""
+    n = len(parts_per_record)
+    if len(sizes) != n:
+        raise ValueError("poly_to_bits: one (h, w) per record")
+    if n == 0:
+        return [], torch.empty((0,), dtype=torch.int32, device=device)
+    xy, ptab, rtab, nv, npart, boff = [], [], [], 0, 0, 0
+    for parts, (h, w) in zip(parts_per_record, sizes):
+        if segmentation_kind(parts) != "polygons":
+            raise ValueError("poly_to_bits: every record must be a list of polygon parts")
+        h, w = int(h), int(w)
+        if h < 1 or w < 1 or h * w >= 2 ** 31:
+            raise ValueError("poly_to_bits: image size %d x %d" % (h, w))
+        for part in parts:
+            v = np.asarray(part, dtype=np.float64)
+            xy.append(v)
+            ptab.append((nv, len(v) // 2))
+            nv += len(v) // 2
+        rtab.append((npart, len(parts), h, w, boff, words_of(h * w), 0, 0))
+        npart += len(parts)
+        boff += words_of(h * w)
+    xd = torch.from_numpy(np.concatenate(xy)).to(device)
+    pd = torch.from_numpy(np.array(ptab, np.int64)).to(device)
+    rd = torch.from_numpy(np.array(rtab, np.int64)).to(device)
+    scratch = torch.empty((boff,), dtype=torch.int64, device=device)
+    bits = torch.empty((boff,), dtype=torch.int64, device=device)
+    area = torch.empty((n,), dtype=torch.int32, device=device)
+    check(lib().rsis_poly_to_bits(ptr(xd), nv, ptr(pd), npart, ptr(rd), n, ptr(scratch), ptr(bits), boff, ptr(area), stream()),
+          "rsis_poly_to_bits")
+    return [bits[r[4]:r[4] + r[5]] for r in rtab], area
+
+
+def _image_sizes(images):
+    """`images` of COCOEvalDevice / add_gt: a list of COCO image dicts (id, height, width) or {image id: (h, w)} -> {id: (h, w)}"""
+    if not images:
+        return {}
+    if isinstance(images, dict):
+        return {k: (int(v[0]), int(v[1])) for k, v in images.items()}
+    return {im["id"]: (int(im["height"]), int(im["width"])) for im in images}
+
+
 class Params(object):
     """cocoeval.py:494-529 for iouType 'segm'"""
 
@@ -123,14 +198,17 @@ class _Side(object):
 
 class COCOEvalDevice(object):
     """Drop-in for the reference's COCOeval(cocoGt, cocoDt, 'segm'): set `params`, then evaluate() / accumulate() / summarize().
-    gt / dt: lists of COCO annotation records (image_id, category_id, segmentation = {'size': [h, w], 'counts': compressed RLE},
-    score for detections; for ground truth `area` (default: the mask's), `iscrowd`, `ignore` (default 0), `id` (default: position +
-    1)); more can be added with add_gt / add_dt, or from device tensors with add_gt_masks / add_dt_masks."""
+    gt / dt: lists of COCO annotation records (image_id, category_id, segmentation = {'size': [h, w], 'counts': compressed RLE or a
+    list of run lengths} or a list of polygons, score for detections; for ground truth `area` (default: the mask's), `iscrowd`,
+    `ignore` (default 0), `id` (default: position + 1)); more can be added with add_gt / add_dt, or from device tensors with
+    add_gt_masks / add_dt_masks.  A polygon record takes its image's size from `images` (COCO image dicts, or {image id: (h, w)}) or
+    from an RLE record of the same image."""
 
-    def __init__(self, gt=None, dt=None, device="cuda"):
+    def __init__(self, gt=None, dt=None, device="cuda", images=None):
         self.params = Params()
         self.device = device
         self._gt, self._dt = _Side(), _Side()
+        self._size = _image_sizes(images)                            # image id -> (h, w), from `images` and from RLE records
         self.eval, self.stats, self._res = {}, [], None
         self.keep_intersect_inputs = False                           # tools/bench_cocoeval.py: replay the grouped launch on its own
         if gt:
@@ -142,38 +220,78 @@ class COCOEvalDevice(object):
             self.params.catIds = sorted(set(r["category_id"] for r in gt))
 
     # ------------------------------------------------------------------ input ------------------------------------------------------------------
-    def _add_records(self, side, records, is_gt):
-        per_img = {}                                                 # image id -> {counts text: row}: records that share a mask share its row
+    def _add_records(self, side, records, is_gt, images=None):
+        """records of any segmentation_kind.  Rows of an image, in order of first appearance: one per distinct compressed text
+        (records that share a mask share its row), one per uncompressed-RLE or polygon record."""
+        seen = {}                                                    # sizes this call states (kept at the end: a refused call changes nothing)
+        known = self._size
+
+        def note(img, hw):
+            if seen.setdefault(img, known.get(img, hw)) != hw:
+                raise ValueError("image %r has masks of different sizes" % (img,))
+        for img, hw in _image_sizes(images).items():
+            note(img, hw)
+        per_img = {}                                                 # image id -> (list of rows: (kind, payload), {counts text: row})
         todo = []
         for r in records:
             seg = r["segmentation"]
-            if not isinstance(seg, dict) or "counts" not in seg or isinstance(seg["counts"], (list, tuple)):
-                raise ValueError("only compressed-RLE segmentations are supported (polygons / uncompressed RLE are out of scope)")
-            text = seg["counts"] if isinstance(seg["counts"], bytes) else seg["counts"].encode("ascii")
-            ln = int(seg["size"][0]) * int(seg["size"][1])
-            d = per_img.setdefault(r["image_id"], {})
-            if text not in d:
-                d[text] = len(d)
-            todo.append((r, d[text], ln))
-        img_len = {}
-        for r, _row, ln in todo:
-            if img_len.setdefault(r["image_id"], ln) != ln:
-                raise ValueError("image %r has masks of different sizes" % (r["image_id"],))
-        counts, lengths = [], []
-        for img, d in per_img.items():
-            for text in d:                                           # (dicts keep insertion order: row order)
-                counts.append(rle_from_string(text))
-                lengths.append(img_len[img])
-        k = 0
-        rows, area = rle_to_bits(counts, lengths, self.device)
-        base = {}
-        for img, d in per_img.items():
-            n = len(d)
-            self._check_len(img, img_len[img])
-            bits = torch.stack(rows[k:k + n]) if n > 1 else rows[k].reshape(1, -1)
-            base[img] = side.add_chunk(img, bits, area[k:k + n], img_len[img])
-            k += n
-        for r, row, _ln in todo:
+            kind = segmentation_kind(seg)
+            rows_i, shared = per_img.setdefault(r["image_id"], ([], {}))
+            if kind == "polygons":
+                row = len(rows_i)
+                rows_i.append((kind, seg))
+            else:
+                note(r["image_id"], (int(seg["size"][0]), int(seg["size"][1])))
+                if kind == "rle":
+                    text = seg["counts"] if isinstance(seg["counts"], bytes) else seg["counts"].encode("ascii")
+                    if text not in shared:
+                        shared[text] = len(rows_i)
+                        rows_i.append((kind, text))
+                    row = shared[text]
+                else:
+                    row = len(rows_i)
+                    rows_i.append((kind, np.asarray(seg["counts"], dtype=np.int64)))
+            todo.append((r, row))
+        size = {}
+        for img in per_img:
+            size[img] = seen.get(img, known.get(img))
+            if size[img] is None:
+                raise ValueError("image %r: a polygon segmentation needs the image's size (pass `images`, or an RLE record of that image)"
+                                 % (img,))
+            self._check_len(img, size[img][0] * size[img][1])
+        counts, lengths, polys, psizes = [], [], [], []
+        for img, (rows_i, _shared) in per_img.items():
+            for kind, payload in rows_i:
+                if kind == "polygons":
+                    polys.append(payload)
+                    psizes.append(size[img])
+                else:
+                    if kind == "counts" and (len(payload) == 0 or payload.min() < 0 or payload.max() >= 2 ** 32):
+                        raise ValueError("image %r: uncompressed RLE counts must be non-negative run lengths" % (img,))
+                    counts.append(rle_from_string(payload) if kind == "rle" else payload.astype(np.uint32))
+                    lengths.append(size[img][0] * size[img][1])
+        rrows, rarea = rle_to_bits(counts, lengths, self.device)
+        prows, parea = poly_to_bits(polys, psizes, self.device)
+        allrows, allarea = rrows + prows, torch.cat([rarea, parea])
+        kr, kp, base = 0, len(rrows), {}
+        for img, (rows_i, _shared) in per_img.items():
+            idx = []
+            for kind, _payload in rows_i:                            # row -> its place in the RLE launch or in the polygon launch
+                if kind == "polygons":
+                    idx.append(kp)
+                    kp += 1
+                else:
+                    idx.append(kr)
+                    kr += 1
+            n = len(idx)
+            if idx == list(range(idx[0], idx[0] + n)):
+                area = allarea[idx[0]:idx[0] + n]
+            else:                                                    # an image with rows from both launches
+                area = allarea[torch.tensor(idx, dtype=torch.int64, device=allarea.device)]
+            bits = torch.stack([allrows[j] for j in idx]) if n > 1 else allrows[idx[0]].reshape(1, -1)
+            base[img] = side.add_chunk(img, bits, area, size[img][0] * size[img][1])
+        known.update(seen)
+        for r, row in todo:
             n = len(side.rec)
             side.rec.append((r["image_id"], r["category_id"], base[r["image_id"]] + row, float(r.get("score", 0.0)),
                              (r.get("area") if is_gt else None), int(r.get("iscrowd", 0)) if is_gt else 0,
@@ -184,11 +302,12 @@ class COCOEvalDevice(object):
             if s.length.get(image_id, length) != length:
                 raise ValueError("image %r: masks of %d and of %d elements" % (image_id, s.length[image_id], length))
 
-    def add_gt(self, records):
-        self._add_records(self._gt, records, True)
+    def add_gt(self, records, images=None):
+        """images: the sizes polygon records need -- COCO image dicts (id, height, width) or {image id: (h, w)}"""
+        self._add_records(self._gt, records, True, images)
 
-    def add_dt(self, records):
-        self._add_records(self._dt, records, False)
+    def add_dt(self, records, images=None):
+        self._add_records(self._dt, records, False, images)
 
     def _add_masks(self, side, image_id, masks, bits, category_id, rows, score, area, iscrowd, ignore, ids, is_gt):
         if bits is not None:
@@ -541,29 +660,38 @@ def run_reference_protocol(ev, img_ids, cat_ids, max_dets, use_cats, all_classes
 
 def get_cli_parser():
     ap = argparse.ArgumentParser(prog="python -m rsis_amd.cocoeval", description="COCO segm AP of a predictions file against a "
-                                 "ground-truth file, on the GPU (both: JSON lists of COCO records with compressed-RLE segmentations)")
+                                 "ground-truth file, on the GPU (both: JSON lists of COCO records, or COCO dicts with 'annotations' and "
+                                 "'images'; segmentations as compressed RLE, uncompressed RLE or polygons)")
     ap.add_argument("--gt", required=True, help="ground truth: JSON list of annotation records, or a COCO dict with 'annotations'")
     ap.add_argument("--dt", required=True, help="detections: a *_predictions.json of rsis_amd.eval or of the reference's eval.py")
     ap.add_argument("-max_dets", dest="max_dets", default=100, type=int)
     ap.add_argument("--ignore_cats", dest="use_cats", action="store_false")
     ap.add_argument("--all_classes", dest="all_classes", action="store_true")
+    ap.add_argument("--all_images", dest="all_images", action="store_true", help="evaluate every image the ground-truth file lists "
+                    "under 'images' (also those without annotations), not only the images that have ground-truth records")
     ap.add_argument("--out", default=None, help="write the stats as JSON here")
     return ap
 
 
-def _load_records(path):
+def load_coco_file(path):
+    """a JSON list of records -> (records, None); a COCO dict -> (its 'annotations', its 'images' or None)"""
     with open(path) as f:
         d = json.load(f)
-    return d["annotations"] if isinstance(d, dict) else d
+    if isinstance(d, dict):
+        return d["annotations"], d.get("images")
+    return d, None
 
 
 def main(argv=None):
     a = get_cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("rsis_amd.cocoeval needs the GPU: the HIP library is the only compute path")
-    gt, dt = _load_records(a.gt), _load_records(a.dt)
-    ev = COCOEvalDevice(gt, dt)
-    res = run_reference_protocol(ev, sorted(set(r["image_id"] for r in gt)), sorted(set(r["category_id"] for r in gt)), a.max_dets,
+    (gt, images), (dt, _) = load_coco_file(a.gt), load_coco_file(a.dt)
+    if a.all_images and not images:
+        raise SystemExit("--all_images needs a ground-truth file with an 'images' list")
+    ev = COCOEvalDevice(gt, dt, images=images)
+    img_ids = sorted(_image_sizes(images)) if a.all_images else sorted(set(r["image_id"] for r in gt))
+    res = run_reference_protocol(ev, img_ids, sorted(set(r["category_id"] for r in gt)), a.max_dets,
                                  a.use_cats, a.all_classes)
     if a.out:
         with open(a.out, "w") as f:

@@ -785,6 +785,13 @@ int rsis_rle_to_bits(const unsigned int* counts, long counts_len, const long lon
   return rsis_l_rle_to_bits(counts, counts_len, desc, n, ends, bits, bits_len, area, (hipStream_t)stream);
 }
 
+int rsis_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n,
+                      unsigned long long* scratch, unsigned long long* bits, long bits_len, unsigned int* area, void* stream) {
+  if (!xy || !parts || !recs || !scratch || !bits || !area || scratch == bits || nverts < 1 || nparts < 1 || n < 1 || bits_len < 1)
+    return RSIS_ERR_ARG;
+  return rsis_l_poly_to_bits(xy, nverts, parts, nparts, recs, n, scratch, bits, bits_len, area, (hipStream_t)stream);
+}
+
 long rsis_mask_intersect_blocks(long D, long G, long stride) {
   if (D < 1 || G < 1 || stride < 1) return 0;
   return rsis_l_mask_intersect_blocks(D, G, stride);

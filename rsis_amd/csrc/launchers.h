@@ -112,6 +112,8 @@ int rsis_l_overlay_masks(const unsigned char* image, const unsigned char* masks,
 int rsis_l_mask_pack_bits(const unsigned char* masks, int n, long len, unsigned long long* bits, long stride, unsigned int* area, hipStream_t st);
 int rsis_l_rle_to_bits(const unsigned int* counts, long counts_len, const long long* desc, int n, unsigned int* ends, unsigned long long* bits, long bits_len,
                        unsigned int* area, hipStream_t st);
+int rsis_l_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n, unsigned long long* scratch,
+                        unsigned long long* bits, long bits_len, unsigned int* area, hipStream_t st);
 long rsis_l_mask_intersect_blocks(long D, long G, long stride);
 int rsis_l_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks, unsigned int* inter,
                                 long inter_len, hipStream_t st);
