@@ -493,6 +493,24 @@ int rsis_rle_to_bits(const unsigned int* counts, long counts_len, const long lon
                      long bits_len, unsigned int* area, void* stream);
 int rsis_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n,
                       unsigned long long* scratch, unsigned long long* bits, long bits_len, unsigned int* area, void* stream);
+/* ---- COCO label maps of a whole batch, painted from the bit rows of its records at the data layer's output size (dataloader/coco.py;
+ * cocomaps.hip).  bits[bits_len] / area[nrec] are what rsis_poly_to_bits / rsis_rle_to_bits left: element x * h + y of record r is bit
+ * e % 64 of word bits[first word + e / 64].  All tables in DEVICE memory: recs[r] = {first word, words, native h, native w, instance id
+ * (1..255), class id, 0, 0} (int64, 8 entries, nrec records); imgs[b] = {first record, records} (int64, 2 entries) for each of the B
+ * samples, a sample may have 0 records; src_y[B][Ho] and src_x[B][Wo] int32: the native row / column that output row i / column j of
+ * sample b samples (the caller folds resize, flip and crop into them; the kernel does no floating-point arithmetic).
+ * ins[B][Ho][Wo], seg[B][Ho][Wo] int32, EVERY element written: among the sample's records whose bit at (src_x, src_y) is set, the one
+ * of the SMALLEST area[] wins, equal areas go to the LOWER record index; ins = its instance id, seg = its class id; both 0 where no
+ * record covers the pixel or an index lies outside [0, h) x [0, w).  A record of area 0 never wins.  A record whose entries do not
+ * fit bits_len (or whose id is outside 1..255) is skipped; an image entry that does not fit nrec, or has more than max_recs records,
+ * counts as 0 records.  max_recs is the caller's bound on the records of a sample: the table itself cannot be read without a copy.
+ * No allocation, no host sync, no atomics, capture-safe; integer compares only, so the result does not depend on the order of
+ * execution.  nrec == 0: bits / area / recs may be null.
+ * RSIS_ERR_ARG, nothing launched: any other null pointer, ins == seg, an output that is also an input, B, Ho or Wo < 1, a negative
+ * length.  RSIS_ERR_UNSUPPORTED, nothing launched: Ho * Wo >= 2^31, B > 65535, max_recs > 255. ---- */
+int rsis_paint_instance_maps(const unsigned long long* bits, long bits_len, const unsigned int* area, long nrec, const long long* recs,
+                             const long long* imgs, int B, int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, int* ins, int* seg,
+                             void* stream);
 long rsis_mask_intersect_blocks(long D, long G, long stride);
 int rsis_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks,
                               unsigned int* inter, long inter_len, void* stream);

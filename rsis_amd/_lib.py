@@ -174,6 +174,7 @@ SIGNATURES = {
     "rsis_mask_intersect_batch": (_i, [_vp, _l, _vp, _i, _i, _vp, _l, _vp]),
     "rsis_coco_iou_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_poly_to_bits": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _l, _vp, _vp]),
+    "rsis_paint_instance_maps": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "rsis_coco_match_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _i, _vp, _i, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_rle_from_string": (_i, [ctypes.c_char_p, _vp, _i]),
     "rsis_label_contingency_blocks": (_l, [_l]),

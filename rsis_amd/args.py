@@ -75,7 +75,7 @@ _FLAGS = [
     ("-imsize", dict(dest="imsize", default=256, type=int)),
     ("--resize", dict(dest="resize", action="store_true")),
     ("-num_classes", dict(dest="num_classes", default=21, type=int)),
-    ("-dataset", dict(dest="dataset", default="pascal", choices=["pascal", "cityscapes", "leaves"])),
+    ("-dataset", dict(dest="dataset", default="pascal", choices=["pascal", "cityscapes", "leaves", "coco"])),
     ("-pascal_dir", dict(dest="pascal_dir", default="/work/asalvador/dev/data/rsis/VOCAug/")),
     ("-cityscapes_dir", dict(dest="cityscapes_dir", default="/gpfs/scratch/bsc31/bsc31429/CityScapes/")),
     ("-leaves_dir", dict(dest="leaves_dir", default="/gpfs/scratch/bsc31/bsc31429/LeavesDataset/A1/")),
@@ -106,6 +106,10 @@ _FLAGS = [
     ("--graph", dict(dest="graph", action="store_true")),
     # reproduce the reference's accidental 1x/3x/4x trunk learning rate (utils/utils.py:34-52: duplicated tensors handed to Adam)
     ("--enc_lr_quirk", dict(dest="enc_lr_quirk", action="store_true")),
+    # -dataset coco (dataloader/coco.py): <coco_dir>/annotations/instances_<set>.json and the images under <coco_dir>/<set>/
+    ("-coco_dir", dict(dest="coco_dir", default="/data/coco/")),
+    ("-coco_train_set", dict(dest="coco_train_set", default="train2017")),
+    ("-coco_val_set", dict(dest="coco_val_set", default="val2017")),
 ]
 
 _DEFAULTS = dict(resume=False, crop=False, smooth_curves=False, update_encoder=False, transfer=False,

@@ -792,6 +792,19 @@ int rsis_poly_to_bits(const double* xy, long nverts, const long long* parts, lon
   return rsis_l_poly_to_bits(xy, nverts, parts, nparts, recs, n, scratch, bits, bits_len, area, (hipStream_t)stream);
 }
 
+int rsis_paint_instance_maps(const unsigned long long* bits, long bits_len, const unsigned int* area, long nrec, const long long* recs,
+                             const long long* imgs, int B, int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, int* ins, int* seg,
+                             void* stream) {
+  if (!imgs || !src_y || !src_x || !ins || !seg || ins == seg || nrec < 0 || bits_len < 0 || (nrec > 0 && (!bits || !area || !recs)) ||
+      B < 1 || max_recs < 0 || Ho < 1 || Wo < 1)
+    return RSIS_ERR_ARG;
+  const void* in[6] = {bits, area, recs, imgs, src_y, src_x};
+  for (int i = 0; i < 6; ++i)
+    if (in[i] == (const void*)ins || in[i] == (const void*)seg) return RSIS_ERR_ARG;
+  if ((long)Ho * Wo >= (1L << 31) || B > 65535 || max_recs > 255) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_paint_instance_maps(bits, bits_len, area, nrec, recs, imgs, B, max_recs, src_y, src_x, Ho, Wo, ins, seg, (hipStream_t)stream);
+}
+
 long rsis_mask_intersect_blocks(long D, long G, long stride) {
   if (D < 1 || G < 1 || stride < 1) return 0;
   return rsis_l_mask_intersect_blocks(D, G, stride);

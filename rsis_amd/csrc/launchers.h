@@ -114,6 +114,9 @@ int rsis_l_rle_to_bits(const unsigned int* counts, long counts_len, const long l
                        unsigned int* area, hipStream_t st);
 int rsis_l_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n, unsigned long long* scratch,
                         unsigned long long* bits, long bits_len, unsigned int* area, hipStream_t st);
+int rsis_l_paint_instance_maps(const unsigned long long* bits, long bits_len, const unsigned int* area, long nrec, const long long* recs,
+                               const long long* imgs, int B, int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, int* ins, int* seg,
+                               hipStream_t st);
 long rsis_l_mask_intersect_blocks(long D, long G, long stride);
 int rsis_l_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks, unsigned int* inter,
                                 long inter_len, hipStream_t st);

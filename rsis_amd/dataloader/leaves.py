@@ -145,7 +145,8 @@ class DeviceLoader(object):
     `num_workers` threads and copied on a side stream while the current one trains.
     A dataset whose `host_item` returns (image, ins) has its class map derived as `ins > 0` (leaves); one that returns (image, ins, seg)
     (dataloader/pascal.py) has `seg` staged, copied and warped next to `ins`; one with a `maps_from_ids` (dataloader/cityscapes.py) returns
-    (image, raw ids) and has both maps derived from the warped ids on the device.
+    (image, raw ids) and has both maps derived from the warped ids on the device; one with a `device_maps` (dataloader/coco.py) returns
+    (image, record) and has both maps painted on the device from the batch's polygons, then warped like Pascal's.
 
     One process per GPU (rank / world): `batch_size` is the PER-RANK batch; every rank shuffles the whole dataset with the SAME
     seed and takes samples r, r + world, ... of each global batch of batch_size * world, so that an epoch is
@@ -205,6 +206,8 @@ class DeviceLoader(object):
             items = [self.ds.host_item(i, random.Random(sd)) for i, sd in work]
         else:
             items = list(self.pool.map(lambda a: self.ds.host_item(a[0], random.Random(a[1])), work))
+        if hasattr(self.ds, "device_maps"):                    # (image, record): dataloader/coco.py
+            return self._stage_records(items, slot)
         S = items[0][0].shape[1:]
         with_seg = len(items[0]) == 3                          # (image, ins, seg): the class map is staged, copied and warped too
         ent = self._pinned(slot, len(items), S, with_seg)
@@ -220,12 +223,35 @@ class DeviceLoader(object):
                 mats = torch.stack([self.ds.augmentation_transform.matrix(S[0], S[1]) for _ in items])
         return img, ins, mats, ent
 
+    def _stage_records(self, items, slot):
+        """_stage for a dataset that paints its label maps on the device (dataloader/coco.py `device_maps`): the images go to the pinned
+        set as always; in the place of the instance maps travels ONE int64 table, the polygons and index tables of the batch,
+        concatenated here in numpy and copied through a pinned buffer of its own (grown on demand, reused under an event)"""
+        S = items[0][0].shape[1:]
+        ent = self._pinned(slot, len(items), S)
+        for i, it in enumerate(items):
+            np.copyto(ent[3][i], it[0])
+        table, layout = self.ds.stage_tables([it[1] for it in items], S)
+        key = ("tables", slot & 1)
+        pin = self._pins.get(key)
+        if pin is None or pin[0].numel() < len(table):
+            pin = self._pins[key] = [torch.empty((max(1024, 2 * len(table)),), dtype=torch.int64).pin_memory(), None]
+        if pin[1] is not None:
+            pin[1].synchronize()
+            pin[1] = None
+        np.copyto(pin[0].numpy()[:len(table)], table)
+        mats = None
+        if self.ds.augmentation_transform is not None:
+            with self._lock:
+                mats = torch.stack([self.ds.augmentation_transform.matrix(S[0], S[1]) for _ in items])
+        return ent[0], pin[0][:len(table)], mats, ent, (layout, pin)
+
     def _to_device(self, staged):
         """H2D copy, normalisation, warp and target construction of one staged batch -- ALL on the copy stream: none of it depends on the
         training step in flight on the caller's stream, and the host syncs inside (torch.unique, the early-stop rule) then wait for this
         stream only, not for the step (at configs[0]'s batch of 2 the step is 8.6 ms and the serialized batch preparation was ~2 ms of GPU
         idle time per iteration).  The caller's stream waits for the copy stream once, at the end."""
-        img, ins, mats, ent = staged
+        img, ins, mats, ent = staged[:4]
         st = self.copy_stream
         cur = torch.cuda.current_stream()
         with torch.cuda.stream(st):
@@ -235,6 +261,11 @@ class DeviceLoader(object):
             if ent is not None:                 # the staging set may be refilled once these two copies have run
                 ent[2] = torch.cuda.Event()
                 ent[2].record(st)
+            if len(staged) > 4:                 # `m` is the batch's table (_stage_records): both maps are painted from it on the device
+                layout, pin = staged[4]
+                pin[1] = torch.cuda.Event()
+                pin[1].record(st)
+                m, sg = self.ds.device_maps(m, layout)
             x = (x.float() / 255.0 - self.mean) / self.std                      # ToTensor + Normalize (train.py:34-37)
             mf = m.float().unsqueeze(1)
             if mats is not None:                                                # dataset.py:66-67: image and maps share one warp

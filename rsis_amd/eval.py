@@ -29,6 +29,13 @@ reference names it (eval.py:287-291: the Cityscapes path without its extension, 
 truth for these two datasets (it stops at an undefined `cocoGT` unless --no_run_coco_eval is given), so the COCO evaluation is skipped for
 them, said in one line on stderr; the predictions file is written as for Pascal.
 
+    python -m rsis_amd.eval -dataset coco -coco_dir D -eval_split val -num_classes 81 ...
+
+reads <D>/annotations/instances_<-coco_val_set>.json through dataloader/coco.py (label maps painted on the device), resamples every mask
+to its image's original size as for Pascal, without an ignore mask, and scores against the annotation file itself (its records and
+`images`; crowd by the evaluator's rule).  The predictions file is a standard COCO results file: the file's integer `image_id`, the
+ORIGINAL `category_id` (plus `category_name`); `python -m rsis_amd.cocoeval --gt <annotations> --dt <predictions>` gives the same stats.
+
     python -m rsis_amd.eval ... --display [--no_display_text] [--display_route]
 
 additionally saves one figure per image (eval.py:342-359), <models_root>/<model_name>/<model_name>_figs_<eval_split>/<name>.png: the
@@ -88,6 +95,7 @@ class Evaluate(object):
         self.args = args
         self.split = args.eval_split
         self.gt_records = self.ignore_rle = self.dataset = self.dataset_name = None
+        self.gt_images = self.category_ids = None                   # -dataset coco: the file's `images`, class index -> category id
         self.display = bool(getattr(args, "display", False))
         self.figures = []                                           # with --display: (path, records drawn, label rectangles) per image
         if not getattr(args, "synthetic", False):
@@ -95,8 +103,10 @@ class Evaluate(object):
                 self._init_pascal()
             elif args.dataset in ("cityscapes", "leaves"):
                 self._init_files(args.dataset)
+            elif args.dataset == "coco":
+                self._init_coco()
             else:
-                raise Exception("-dataset %s: only --synthetic inputs and -dataset pascal, cityscapes and leaves are wired in this build"
+                raise Exception("-dataset %s: only --synthetic inputs and -dataset pascal, cityscapes, leaves and coco are wired in this build"
                                 % args.dataset)
             return
         self.encoder, self.decoder = load_models(self.args)
@@ -118,6 +128,22 @@ class Evaluate(object):
         for ann in self.gt_records:
             if ann["ignore"] == 1:
                 self.ignore_rle[ann["image_id"]] = ann["segmentation"]
+        self.encoder, self.decoder = load_models(args)
+        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
+                                   drop_last=False)
+
+    def _init_coco(self):
+        """-dataset coco: the reader of dataloader/coco.py; the ground truth is the annotation file itself, records and `images`"""
+        from .cocoeval import load_coco_file
+        from .dataloader.coco import COCO
+        from .dataloader.leaves import DeviceLoader
+        args = self.args
+        self.dataset_name = "coco"
+        self.dataset = COCO(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        self.sample_list = list(self.dataset.image_ids)             # the file's integer image ids
+        self.class_names = self.dataset.get_classes()
+        self.category_ids = list(self.dataset.category_ids)
+        self.gt_records, self.gt_images = load_coco_file(self.dataset.ann_file)
         self.encoder, self.decoder = load_models(args)
         self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
                                    drop_last=False)
@@ -157,7 +183,7 @@ class Evaluate(object):
         if self.dataset is None:
             return display.denormalize(x)
         from PIL import Image
-        path = self.dataset.image_path(index) if self.dataset_name == "pascal" else self.dataset.get_sample_list()[index]
+        path = self.dataset.image_path(index) if self.dataset_name in ("pascal", "coco") else self.dataset.get_sample_list()[index]
         with Image.open(path) as im:
             rgb = np.array(im.convert("RGB"), dtype=np.uint8)
         return torch.as_tensor(rgb).to(x.device)
@@ -181,7 +207,9 @@ class Evaluate(object):
             from . import display
             figs_dir = display.figures_dir(args.models_root, args.model_name, self.split)       # eval.py:343-344
             os.makedirs(figs_dir, exist_ok=True)
-        if coco is not None and self.gt_records is not None:
+        if coco is not None and self.gt_images is not None:          # a COCO file: every record, the sizes from its `images`
+            coco.add_gt(self.gt_records, images=self.gt_images)
+        elif coco is not None and self.gt_records is not None:
             mine = set(self.sample_list)
             coco.add_gt([r for r in self.gt_records if r["image_id"] in mine])
         for inputs, y_mask, y_class, sw_mask, _sw_class in self.loader:
@@ -220,6 +248,8 @@ class Evaluate(object):
                         ann = create_annotation(args, sample_idx, _jsonable(segs[i]), cls_id, score, self.class_names, is_valid)
                         if ann is None:
                             continue
+                        if self.category_ids is not None:                                        # a COCO results file: the ORIGINAL id
+                            ann["category_id"] = self.category_ids[cls_id]
                         if self.dataset_name == "leaves":                                        # eval.py:329-331
                             if objectness > args.stop_th:
                                 shown.append(ann)
@@ -227,10 +257,12 @@ class Evaluate(object):
                         elif cls_id == max_class and score >= args.class_th:                     # eval.py:333
                             shown.append(create_annotation(args, sample_idx, _jsonable(raws[i]), cls_id, score, self.class_names,
                                                            is_valid))
+                            if self.category_ids is not None:
+                                shown[-1]["category_id"] = self.category_ids[cls_id]
                             drawn.append(dict(shown[-1], mask_row=i))
                         predictions.append(ann)
                         rows.append(i)
-                        cats.append(cls_id)
+                        cats.append(ann["category_id"])
                         recscores.append(score)
                 if self.display:                                    # eval.py:342-359: the RAW masks over the original image
                     from . import display
@@ -266,14 +298,17 @@ class Evaluate(object):
             print("%d figures -> %s" % (len(self.figures), os.path.dirname(self.figures[0][0]) if self.figures else "(none)"))
         if self.coco is not None:                                    # eval.py:375-398
             args = self.args
-            cat_ids = list(range(1, len(self.class_names)))
-            res = run_reference_protocol(self.coco, self.sample_list, cat_ids, args.max_dets, args.use_cats, args.all_classes,
-                                         self.class_names)
+            cat_ids, img_ids, names = list(range(1, len(self.class_names))), self.sample_list, self.class_names
+            if self.category_ids is not None:                       # as `python -m rsis_amd.cocoeval` reads the same two files
+                cat_ids = sorted(set(r["category_id"] for r in self.gt_records))
+                img_ids = sorted(set(r["image_id"] for r in self.gt_records))
+                names = dict(zip(self.category_ids, self.class_names))
+            res = run_reference_protocol(self.coco, img_ids, cat_ids, args.max_dets, args.use_cats, args.all_classes, names)
             p = self.coco.params
             res["params"] = {"maxDets": [int(v) for v in p.maxDets], "useCats": int(bool(args.use_cats)), "catIds": cat_ids,
                              "iouThrs": [float(v) for v in p.iouThrs], "recThrs": [float(v) for v in p.recThrs],
                              "areaRng": [[float(v) for v in r] for r in p.areaRng], "areaRngLbl": list(p.areaRngLbl),
-                             "images": len(self.sample_list)}
+                             "images": len(img_ids)}
             epath = os.path.join(out_dir, "%s_%s_cocoeval.json" % (self.args.model_name, self.split))
             with open(epath, "w") as f:
                 json.dump(res, f)

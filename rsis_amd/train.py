@@ -635,12 +635,13 @@ def init_dataloaders(args, rank=0, world=1):
     GPUs, train.py:269-274): every rank of a torchrun job takes B / world samples, so reference hyper-parameters carry over.
     (The loss is the mean of the per-rank masked means -- equal to the global masked mean for equal shard sizes.)"""
     if not getattr(args, "synthetic", False):
-        if args.dataset not in ("leaves", "pascal", "cityscapes"):
-            raise Exception("data: --synthetic, -dataset leaves (CVPPP A1, BASELINE configs[0]), -dataset pascal or -dataset cityscapes")
+        if args.dataset not in ("leaves", "pascal", "cityscapes", "coco"):
+            raise Exception("data: --synthetic, -dataset leaves (CVPPP A1, BASELINE configs[0]), -dataset pascal, cityscapes or coco")
         from .dataloader.cityscapes import CityScapes
+        from .dataloader.coco import COCO
         from .dataloader.leaves import DeviceLoader, LeavesDataset
         from .dataloader.pascal import PascalVOC
-        Dataset = {"leaves": LeavesDataset, "pascal": PascalVOC, "cityscapes": CityScapes}[args.dataset]
+        Dataset = {"leaves": LeavesDataset, "pascal": PascalVOC, "cityscapes": CityScapes, "coco": COCO}[args.dataset]
         if args.batch_size % world != 0:
             raise Exception("-batch_size %d (the global batch) is not divisible by the %d ranks" % (args.batch_size, world))
         loaders = {}
