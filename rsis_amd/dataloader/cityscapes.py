@@ -1,10 +1,10 @@
-"""Cityscapes data layer -- the reference's src/dataloader/cityscapes.py:9-94 + dataset.py:47-84 + dataset_utils.py:27-57, on the host /
-device split of leaves.py:
-  host   : the file list, PNG decode and the PIL bilinear `Scale` of the image, ONE scipy zoom(order=0, mode='nearest') of the RAW
-           `*_gtFine_instanceIds.png` values to the image size, flip and the optional crop into pinned staging (DeviceLoader of
-           leaves.py), the decode cache of LeavesDataset;
-  device : normalisation, one affine warp shared by the image and the raw id map, then class map + compact instance map
-           (rsis_instance_maps: `maps_from_ids`) and the targets (rsis_targets_from_maps).
+"""Cityscapes reader -- the reference's src/dataloader/cityscapes.py:9-94 on the base class of reader.py and the device loader of
+loader.py:
+  host   : the file list, PNG decode and the PIL bilinear `Scale` of the image, ONE nearest zoom of the RAW `*_gtFine_instanceIds.png`
+           values to the image size; flip, the optional crop (`-crop`) and the decode cache are Reader's; `same_size`, so that
+           un-cropped samples are batched;
+  device : normalisation, one affine warp shared by the image and the raw id map, then `label_maps` = `maps_from_ids`: class map +
+           compact instance map (rsis_instance_maps), and the targets (rsis_targets_from_maps).
 The reference derives both maps at full resolution on the host (np.unique over 2 M pixels and one full-image compare per instance,
 cityscapes.py:67-92) and resamples them afterwards.  The class of a pixel is a function of its raw id alone, and the compact instance
 id is the rank of the raw id among the kept ids present -- order-preserving -- so both commute with every step that only MOVES
@@ -18,8 +18,7 @@ import os
 import numpy as np
 import torch
 
-from .augment import RandomAffine
-from .leaves import LeavesDataset
+from .reader import Reader, scale_image, zoom_map
 
 CLASSES = ["<eos>", "person", "rider", "car", "truck", "bus", "train", "motorcycle", "bicycle"]       # cityscapes.py:20
 # labelId -> class: cityscapes.py:68-80 under python-2 integer division (caravan 29 and trailer 30 are not trained)
@@ -57,42 +56,26 @@ def maps_from_ids(ids, table=None):
     return ins, seg
 
 
-class CityScapes(LeavesDataset):
+class CityScapes(Reader):
     """reference CityScapes(MyDataset): same constructor arguments, `classes`, `get_classes`, `get_sample_list`, `__len__`,
     `get_raw_sample`; `host_item` returns (image, RAW ids) and the loader calls `maps_from_ids` after the warp"""
     same_size = True            # every image of the dataset has one size (1024 x 2048): un-cropped samples can be batched
 
     def __init__(self, args, transform=None, target_transform=None, augment=False, split="train", resize=False, imsize=256):
-        self.split = split
+        self._setup(args, transform, target_transform, augment, split, resize, imsize, crop=bool(args.crop),   # cityscapes.py:36-49
+                    zoom_range=(args.zoom, 1) if resize else None)
         self.classes = list(CLASSES)
         self.num_classes = len(self.classes)
-        self.max_seq_len = args.gt_maxseqlen
         self.image_files = sorted(glob.glob(os.path.join(args.cityscapes_dir, "leftImg8bit", split, "*", "*.png")))
         self.ins_files = [w.replace("/leftImg8bit/", "/gtFine/").replace("_leftImg8bit.png", "_gtFine_instanceIds.png")
                           for w in self.image_files]                        # cityscapes.py:26-27 (the labelIds files are never read)
-        self.transform, self.target_transform = transform, target_transform
-        self.batch_size = args.batch_size
         self.no_run_coco_eval = True
-        self.crop = bool(args.crop)                                         # :36-37
-        self.flip = augment
-        if augment:                                                         # :39-49
-            self.augmentation_transform = RandomAffine(rotation_range=args.rotation, translation_range=args.translation,
-                                                       shear_range=args.shear, zoom_range=(args.zoom, 1) if resize else None,
-                                                       interp="nearest")
-        else:
-            self.augmentation_transform = None
-        self.zoom, self.augment, self.imsize, self.resize = args.zoom, augment, imsize, resize
-        self._cache, self._cache_bytes = {}, 0
-        self._cache_limit = int(float(os.environ.get("RSIS_LOADER_CACHE_MB", "1024")) * (1 << 20))
 
     maps_from_ids = staticmethod(maps_from_ids)
 
-    def raw_size(self, index):
-        """(height, width) of the original image, from the file's header"""
-        from PIL import Image
-        with Image.open(self.image_files[index]) as im:
-            w, h = im.size
-        return h, w
+    def label_maps(self, maps):
+        ids, = maps
+        return self.maps_from_ids(ids)
 
     def raw_ids(self, index):
         """the `*_gtFine_instanceIds.png` of a sample as an int32 array"""
@@ -115,24 +98,8 @@ class CityScapes(LeavesDataset):
 
     def _decode(self, index):
         from PIL import Image
-        from scipy.ndimage import zoom
-        img = Image.open(self.image_files[index]).convert("RGB")
-        ids = self.raw_ids(index)
-        S = self.imsize
-        if self.resize:
-            img = img.resize((S, S), Image.BILINEAR)                        # transforms.Scale((S, S))
-        else:                                                               # transforms.Scale(S): shorter side -> S
-            w, h = img.size
-            if w <= h:
-                img = img.resize((S, max(S, int(S * h / w))), Image.BILINEAR)
-            else:
-                img = img.resize((max(S, int(S * w / h)), S), Image.BILINEAR)
-        im = np.asarray(img, dtype=np.uint8).transpose(2, 0, 1)             # (3, h, w)
-        h, w = im.shape[1:]
-        ids = zoom(ids, [float(h) / ids.shape[0], float(w) / ids.shape[1]], mode="nearest", order=0)   # dataset_utils.py:133-140
-        return np.ascontiguousarray(im), np.ascontiguousarray(ids)
-
-    # host_item is LeavesDataset's: flip and crop of (image, ids) -> (uint8 image, int32 raw ids)
+        im = scale_image(Image.open(self.image_files[index]).convert("RGB"), self.imsize, self.resize)
+        return im, zoom_map(self.raw_ids(index), im.shape[1:])
 
 
 def synthesize_cityscapes_dir(path, n=4, sizes=((64, 128),), cities=("aachen", "bochum"), seed=0):

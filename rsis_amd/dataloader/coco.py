@@ -1,14 +1,15 @@
-"""COCO data layer: a standard `instances_<set>.json` read for training and evaluation, on the host / device split of leaves.py.  The
-reference has no COCO reader (its datasets are Pascal VOC, Cityscapes and CVPPP); the sample pipeline is Pascal's (dataset.py:47-84,
-dataset_utils.py:27-57) with the label images replaced by the file's polygons:
-  host   : the annotation file, parsed ONCE into flat numpy arrays (below); JPEG decode and the PIL bilinear `Scale` of the image, flip
-           and the centred random crop of the image into pinned staging, the decode cache of LeavesDataset.  Instead of label arrays
-           `host_item` returns a small record (sample, resized size, flip, crop offsets); DeviceLoader._stage turns the batch's records
-           into ONE int64 table: the polygons at their native sizes and two index tables per sample, src_y / src_x, that fold the
-           nearest resize, the flip and the crop of the maps;
-  device : `device_maps`: one rsis_poly_to_bits launch for all records of the batch (polymask.hip, bit for bit the COCO mask API), one
-           rsis_paint_instance_maps launch (cocomaps.hip) that writes the instance-id and class-id maps at the output size; then, as
-           for Pascal, normalisation, ONE affine warp shared by image and maps, the targets (rsis_targets_from_maps).
+"""COCO reader: a standard `instances_<set>.json` read for training and evaluation, on the base class of reader.py and the device
+loader of loader.py.  The reference has no COCO reader (its datasets are Pascal VOC, Cityscapes and CVPPP); the sample pipeline is
+Pascal's (dataset.py:47-84, dataset_utils.py:27-57) with the label images replaced by the file's polygons:
+  host   : the annotation file, parsed ONCE into flat numpy arrays (below); JPEG decode and the PIL bilinear `Scale` of the image;
+           the flip / crop draws and the decode cache are Reader's.  Instead of label arrays (`num_maps` = 0) `host_item` returns a
+           small record (sample, resized size, flip, crop offsets); `stage_batch` = `stage_tables` turns the batch's records into ONE
+           int64 table: the polygons at their native sizes and two index tables per sample, src_y / src_x, that fold the nearest
+           resize, the flip and the crop of the maps;
+  device : `maps_to_warp` = `device_maps`: one rsis_poly_to_bits launch for all records of the batch (polymask.hip, bit for bit the
+           COCO mask API), one rsis_paint_instance_maps launch (cocomaps.hip) that writes the instance-id and class-id maps at the
+           output size; then, as for Pascal, normalisation, ONE affine warp shared by image and maps, the targets
+           (rsis_targets_from_maps).
 The label images never exist on the host, nor at native size anywhere.
 
 Parsing rules (also INTEGRATION.md):
@@ -35,8 +36,7 @@ import sys
 import numpy as np
 import torch
 
-from .augment import RandomAffine
-from .leaves import LeavesDataset
+from .reader import Reader, flip_crop, scale_image
 
 MAX_RECORDS = 255          # instance ids of rsis_targets_from_maps: 0..255
 
@@ -110,37 +110,25 @@ def compose_maps(masks, inst_ids, class_ids, h, w):
     return ins, seg
 
 
-class COCO(LeavesDataset):
+class COCO(Reader):
     """A COCO instances file behind the readers' interface: same constructor arguments, `classes`, `get_classes`, `get_sample_list`,
     `__len__`, `get_raw_sample`, `image_path`, `raw_size`; `host_item` returns (image, record) and the loader paints both maps on the
     device (`stage_tables` on its staging thread, `device_maps` on its copy stream)"""
+    num_maps = 0
 
     def __init__(self, args, transform=None, target_transform=None, augment=False, split="train", resize=False, imsize=256):
         if split not in ("train", "val"):
             raise ValueError("-dataset coco has the splits train and val (the test sets have no annotations), not %r" % (split,))
-        self.split = split
+        self._setup(args, transform, target_transform, augment, split, resize, imsize, crop=args.batch_size != 1,
+                    zoom_range=(args.zoom, max(args.zoom * 2, 1.0)))       # the augmentation of pascal.py:46-51
         name = args.coco_train_set if split == "train" else args.coco_val_set
         self.ann_file = os.path.join(args.coco_dir, "annotations", "instances_%s.json" % name)
         self.image_dir = os.path.join(args.coco_dir, name)
-        self.max_seq_len = args.gt_maxseqlen
-        self.transform, self.target_transform = transform, target_transform
-        self.batch_size = args.batch_size
-        self.crop = self.batch_size != 1
-        self.flip = augment
-        if augment:                                                         # the augmentation of pascal.py:46-51
-            self.augmentation_transform = RandomAffine(rotation_range=args.rotation, translation_range=args.translation,
-                                                       shear_range=args.shear, zoom_range=(args.zoom, max(args.zoom * 2, 1.0)),
-                                                       interp="nearest")
-        else:
-            self.augmentation_transform = None
-        self.zoom, self.augment, self.imsize, self.resize = args.zoom, augment, imsize, resize
         self._parse()
         self.num_classes = len(self.classes)
         if int(args.num_classes) != self.num_classes:
             raise ValueError("%s has %d categories: -num_classes must be %d (the categories and <eos>), not %d"
                              % (self.ann_file, self.num_classes - 1, self.num_classes, int(args.num_classes)))
-        self._cache, self._cache_bytes = {}, 0
-        self._cache_limit = int(float(os.environ.get("RSIS_LOADER_CACHE_MB", "1024")) * (1 << 20))
 
     # ------------------------------------------------------------------ the annotation file ------------------------------------------
     def _parse(self):
@@ -199,9 +187,6 @@ class COCO(LeavesDataset):
         self.xy = np.concatenate(xy) if xy else np.zeros((0,), np.float64)  # (x, y) pairs of every kept part
         self.rec_class = np.asarray(cls, np.int32)
 
-    def image_path(self, index):
-        return self.image_files[index]
-
     def raw_size(self, index):
         """(height, width) of the original image, as the annotation file states it"""
         return int(self.native_size[index, 0]), int(self.native_size[index, 1])
@@ -227,34 +212,14 @@ class COCO(LeavesDataset):
     # ------------------------------------------------------------------ per sample, on the host --------------------------------------
     def _decode(self, index):
         from PIL import Image
-        img = Image.open(self.image_path(index)).convert("RGB")
-        S = self.imsize
-        if self.resize:
-            img = img.resize((S, S), Image.BILINEAR)                        # transforms.Scale((S, S))
-        else:                                                               # transforms.Scale(S): shorter side -> S
-            w, h = img.size
-            if w <= h:
-                img = img.resize((S, max(S, int(S * h / w))), Image.BILINEAR)
-            else:
-                img = img.resize((max(S, int(S * w / h)), S), Image.BILINEAR)
-        return (np.ascontiguousarray(np.asarray(img, dtype=np.uint8).transpose(2, 0, 1)),)             # (3, h, w)
+        return (scale_image(Image.open(self.image_path(index)).convert("RGB"), self.imsize, self.resize),)
 
     def host_item(self, index, rng):
-        """-> (uint8 image (3, S, S), record): record = (sample, resized (h, w), flip, crop (oh, ow) or None); the draws are Pascal's"""
+        """-> (uint8 image (3, S, S), record): record = (sample, resized (h, w), flip, crop (oh, ow) or None); the draws are Reader's"""
         im, = self._decoded(index)
-        S = self.imsize
         h, w = im.shape[1:]
-        flip = bool(self.flip and rng.random() < 0.5)
-        if flip:
-            im = im[:, :, ::-1]
-        crop = None
-        if self.crop:                                                       # transforms.py:15-21 random_crop (centred range)
-            rw, rh = (w - S) // 2, (h - S) // 2
-            ow = 0 if rw <= 0 else rng.randrange(rw)
-            oh = 0 if rh <= 0 else rng.randrange(rh)
-            im = im[:, oh:oh + S, ow:ow + S]
-            crop = (oh, ow)
-        return np.ascontiguousarray(im), (int(index), (h, w), flip, crop)
+        flip, crop = self._draw((h, w), rng)
+        return np.ascontiguousarray(flip_crop(im, flip, crop, self.imsize)), (int(index), (h, w), flip, crop)
 
     # ------------------------------------------------------------------ per batch: tables on the host, maps on the device -------------
     def stage_tables(self, records, S):
@@ -293,6 +258,12 @@ class COCO(LeavesDataset):
         layout = dict(off=[int(v) for v in off], nverts=int(nverts.sum()), nparts=len(part), n=n, B=B, Ho=int(Ho), Wo=int(Wo),
                       words=int(words.sum()), max_recs=int(cnt.max()))
         return np.concatenate(secs), layout
+
+    def stage_batch(self, items, S):
+        return self.stage_tables([it[1] for it in items], S)
+
+    def maps_to_warp(self, maps, table, layout):
+        return list(self.device_maps(table, layout))
 
     @staticmethod
     def device_maps(table, layout):

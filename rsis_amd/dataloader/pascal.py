@@ -1,16 +1,15 @@
-"""Pascal VOC data layer -- the reference's src/dataloader/pascal.py:17-79 + dataset.py:47-84 + dataset_utils.py:27-57, on the host /
-device split of leaves.py:
-  host   : the split file, JPEG decode and the PIL bilinear `Scale` of the image, scipy zoom(order=0, mode='nearest') of BOTH maps of
-           ProcMasks/<name>.npy ([seg, ins], written by rsis_amd.pascal_precompute) to the image size, flip and the centred random
-           crop into pinned staging (DeviceLoader of leaves.py), the decode cache of LeavesDataset;
-  device : normalisation, ONE affine warp shared by image, instance map and class map, the targets (rsis_targets_from_maps).
+"""Pascal VOC reader -- the reference's src/dataloader/pascal.py:17-79 on the base class of reader.py and the device loader of loader.py:
+  host   : the split file, JPEG decode and the PIL bilinear `Scale` of the image, the nearest zoom of BOTH maps of ProcMasks/<name>.npy
+           ([seg, ins], written by rsis_amd.pascal_precompute) to the image size; flip, the centred random crop and the decode cache are
+           Reader's;
+  device : normalisation, ONE affine warp shared by image, instance map and class map (`num_maps` = 2, used as they are), the targets
+           (rsis_targets_from_maps).
 Unlike leaves, the zoom range of the augmentation does not depend on --resize (pascal.py:47-51)."""
 import os
 
 import numpy as np
 
-from .augment import RandomAffine
-from .leaves import LeavesDataset
+from .reader import Reader, scale_image, zoom_map
 
 CLASSES = ["<eos>", "airplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "dining table", "dog", "horse",
            "motorcycle", "person", "potted plant", "sheep", "sofa", "train", "tv"]          # pascal.py:28-32
@@ -39,42 +38,23 @@ def palette_table():
     return np.array([tuple(cmap[i]) + (i,) for i in ids], np.uint8)
 
 
-class PascalVOC(LeavesDataset):
+class PascalVOC(Reader):
     """reference PascalVOC(MyDataset): same constructor arguments, `classes`, `get_classes`, `get_sample_list`, `__len__`,
     `get_raw_sample`; `host_item` returns THREE arrays (image, instance map, class map)"""
+    num_maps = 2
 
     def __init__(self, args, transform=None, target_transform=None, augment=False, split="train", resize=False, imsize=256):
-        self.split = split
+        self._setup(args, transform, target_transform, augment, split, resize, imsize, crop=args.batch_size != 1,   # pascal.py:41-51
+                    zoom_range=(args.zoom, max(args.zoom * 2, 1.0)))
         self.classes = list(CLASSES)
         self.num_classes = len(self.classes)
-        self.max_seq_len = args.gt_maxseqlen
         self.image_dir = os.path.join(args.pascal_dir, "JPEGImages")
-        self.transform, self.target_transform = transform, target_transform
-        self.batch_size = args.batch_size
-        self.crop = self.batch_size != 1                                   # pascal.py:41-44
-        self.flip = augment
-        if augment:                                                         # :46-51
-            self.augmentation_transform = RandomAffine(rotation_range=args.rotation, translation_range=args.translation,
-                                                       shear_range=args.shear, zoom_range=(args.zoom, max(args.zoom * 2, 1.0)),
-                                                       interp="nearest")
-        else:
-            self.augmentation_transform = None
-        self.zoom, self.augment, self.imsize, self.resize = args.zoom, augment, imsize, resize
         self.masks_dir = os.path.join(args.pascal_dir, "ProcMasks")
         with open(os.path.join(args.pascal_dir, "ImageSets", "Segmentation", split + ".txt"), "r") as lines:   # :60-66
             self.image_files = [line.rstrip("\n") for line in lines]
-        self._cache, self._cache_bytes = {}, 0
-        self._cache_limit = int(float(os.environ.get("RSIS_LOADER_CACHE_MB", "1024")) * (1 << 20))
 
     def image_path(self, index):
         return os.path.join(self.image_dir, self.image_files[index].rstrip() + ".jpg")
-
-    def raw_size(self, index):
-        """(height, width) of the original image, from the file's header"""
-        from PIL import Image
-        with Image.open(self.image_path(index)) as im:
-            w, h = im.size
-        return h, w
 
     def get_raw_sample(self, index):
         """(PIL RGB image, instance-id map, class map) in raw size -- pascal.py:68-79"""
@@ -88,38 +68,9 @@ class PascalVOC(LeavesDataset):
         return img, mask[:, :, 1], mask[:, :, 0]
 
     def _decode(self, index):
-        from PIL import Image
-        from scipy.ndimage import zoom
         img, ins, seg = self.get_raw_sample(index)
-        S = self.imsize
-        if self.resize:
-            img = img.resize((S, S), Image.BILINEAR)                        # transforms.Scale((S, S))
-        else:                                                               # transforms.Scale(S): shorter side -> S
-            w, h = img.size
-            if w <= h:
-                img = img.resize((S, max(S, int(S * h / w))), Image.BILINEAR)
-            else:
-                img = img.resize((max(S, int(S * w / h)), S), Image.BILINEAR)
-        im = np.asarray(img, dtype=np.uint8).transpose(2, 0, 1)             # (3, h, w)
-        h, w = im.shape[1:]
-        f = [float(h) / ins.shape[0], float(w) / ins.shape[1]]              # dataset_utils.py:27-38,133-140: both maps
-        ins = zoom(ins, f, mode="nearest", order=0)
-        seg = zoom(seg, f, mode="nearest", order=0)
-        return np.ascontiguousarray(im), np.ascontiguousarray(ins), np.ascontiguousarray(seg)
-
-    def host_item(self, index, rng):
-        """-> (uint8 image (3, S, S), int32 instance map (S, S), int32 class map (S, S)); un-cropped sizes when batch_size is 1"""
-        im, ins, seg = self._decoded(index)
-        S = self.imsize
-        h, w = im.shape[1:]
-        if self.flip and rng.random() < 0.5:                                # dataset_utils.py:51-55
-            im, ins, seg = im[:, :, ::-1], ins[:, ::-1], seg[:, ::-1]
-        if self.crop:                                                       # transforms.py:15-21 random_crop (centred range)
-            rw, rh = (w - S) // 2, (h - S) // 2
-            ow = 0 if rw <= 0 else rng.randrange(rw)
-            oh = 0 if rh <= 0 else rng.randrange(rh)
-            im, ins, seg = im[:, oh:oh + S, ow:ow + S], ins[oh:oh + S, ow:ow + S], seg[oh:oh + S, ow:ow + S]
-        return np.ascontiguousarray(im), np.ascontiguousarray(ins.astype(np.int32)), np.ascontiguousarray(seg.astype(np.int32))
+        im = scale_image(img, self.imsize, self.resize)
+        return im, zoom_map(ins, im.shape[1:]), zoom_map(seg, im.shape[1:])      # dataset_utils.py:27-38,133-140: both maps
 
 
 def synthesize_pascal_dir(path, n=6, sizes=((48, 64), (75, 50)), seed=0, classes=(2, 7, 15)):

@@ -114,67 +114,44 @@ class Evaluate(object):
         self.loader = SyntheticLoader(args, max(1, args.synthetic_batches // 4), args.seed + 7)
         self.sample_list = ["synthetic_%06d" % i for i in range(len(self.loader) * args.batch_size)]
 
+    def _open(self, name):
+        """eval.py:191-218, the part every dataset shares: the reader of -eval_split, the models, the loader; -> args"""
+        from .dataloader import eval_loader, open_reader
+        args = self.args
+        self.dataset_name = name
+        self.dataset = open_reader(args, self.split, dataset=name)
+        self.class_names = self.dataset.get_classes()
+        self.encoder, self.decoder = load_models(args)
+        self.loader = eval_loader(args, self.dataset)
+        return args
+
     def _init_pascal(self):
         """eval.py:191-218 for -dataset pascal"""
-        from .dataloader.leaves import DeviceLoader
-        from .dataloader.pascal import PascalVOC
-        args = self.args
-        self.dataset_name = "pascal"
-        self.dataset = PascalVOC(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        args = self._open("pascal")
         self.sample_list = [s.rstrip() for s in self.dataset.get_sample_list()]
-        self.class_names = self.dataset.get_classes()
         self.gt_records = load_plain_pickle(os.path.join(args.pascal_dir, "VOCGT_%s.pkl" % self.split))
         self.ignore_rle = {}                                        # image id -> segmentation of its ignore mask (eval.py:198-209)
         for ann in self.gt_records:
             if ann["ignore"] == 1:
                 self.ignore_rle[ann["image_id"]] = ann["segmentation"]
-        self.encoder, self.decoder = load_models(args)
-        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
-                                   drop_last=False)
 
     def _init_coco(self):
         """-dataset coco: the reader of dataloader/coco.py; the ground truth is the annotation file itself, records and `images`"""
         from .cocoeval import load_coco_file
-        from .dataloader.coco import COCO
-        from .dataloader.leaves import DeviceLoader
-        args = self.args
-        self.dataset_name = "coco"
-        self.dataset = COCO(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        self._open("coco")
         self.sample_list = list(self.dataset.image_ids)             # the file's integer image ids
-        self.class_names = self.dataset.get_classes()
         self.category_ids = list(self.dataset.category_ids)
         self.gt_records, self.gt_images = load_coco_file(self.dataset.ann_file)
-        self.encoder, self.decoder = load_models(args)
-        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
-                                   drop_last=False)
 
     def _init_files(self, name):
         """eval.py:191-218 for -dataset cityscapes / leaves: the reader and loader of eval_cityscapes.py / eval_leaves.py; no ground truth"""
-        from .dataloader.leaves import DeviceLoader, LeavesDataset
-        args = self.args
-        self.dataset_name = name
+        args = self._open(name)
         if name == "cityscapes":
-            from .dataloader.cityscapes import CityScapes
-            self.dataset = CityScapes(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
             self.sample_list = [os.path.splitext(f)[0] for f in self.dataset.get_sample_list()]  # eval.py:288
         else:
-            self.dataset = LeavesDataset(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
             self.sample_list = list(self.dataset.get_sample_list())                             # eval.py:291
-        self.class_names = self.dataset.get_classes()
-        self.encoder, self.decoder = load_models(args)
-        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
-                                   drop_last=False)
         if not getattr(args, "no_run_coco_eval", False):
             print("-dataset %s has no ground-truth file in eval.py: the COCO evaluation is skipped" % name, file=sys.stderr)
-
-    def _raw_size(self, index):
-        """(height, width) of the original image of sample `index` (eval.py:293-295)"""
-        if hasattr(self.dataset, "raw_size"):
-            return self.dataset.raw_size(index)
-        from PIL import Image
-        with Image.open(self.dataset.get_sample_list()[index]) as im:
-            w, h = im.size
-        return h, w
 
     def _display_image(self, index, x):
         """the (h, w, 3) uint8 image under the figure of sample `index`, on the device: the original file (eval.py:285-293), or with
@@ -183,8 +160,7 @@ class Evaluate(object):
         if self.dataset is None:
             return display.denormalize(x)
         from PIL import Image
-        path = self.dataset.image_path(index) if self.dataset_name in ("pascal", "coco") else self.dataset.get_sample_list()[index]
-        with Image.open(path) as im:
+        with Image.open(self.dataset.image_path(index)) as im:
             rgb = np.array(im.convert("RGB"), dtype=np.uint8)
         return torch.as_tensor(rgb).to(x.device)
 
@@ -226,7 +202,7 @@ class Evaluate(object):
                 sample_idx = self.sample_list[s + acc]
                 ignore = None
                 if self.dataset is not None:                       # eval.py:280-295: the ORIGINAL size, the image's ignore pixels
-                    h, w = self._raw_size(s + acc)
+                    h, w = self.dataset.raw_size(s + acc)              # (eval.py:293-295)
                     if self.ignore_rle is not None:
                         ignore = self._ignore_mask(sample_idx)
                 # all T masks of the image in one launch each: resample + threshold + area, then run-length encoding

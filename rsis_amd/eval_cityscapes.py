@@ -73,14 +73,12 @@ class Evaluate(object):
 
     def _init_files(self):
         """eval_cityscapes.py:38-51: the images of -eval_split through the reader, in file order"""
-        from .dataloader.cityscapes import CityScapes
-        from .dataloader.leaves import DeviceLoader
+        from .dataloader import eval_loader, open_reader
         args = self.args
-        self.dataset = CityScapes(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)
+        self.dataset = open_reader(args, self.split, dataset="cityscapes")
         self.sample_list = [os.path.basename(f).split(".")[0] for f in self.dataset.get_sample_list()]   # :114-120
         self.encoder, self.decoder = load_models(args)
-        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
-                                   drop_last=False)
+        self.loader = eval_loader(args, self.dataset)
 
     def _create_figures_files(self):
         """create_figures on the files of the dataset: original sizes from the PNG headers, ground truth = the raw instanceIds arrays"""

@@ -21,7 +21,7 @@ import sys
 import torch
 
 from .args import get_parser
-from .dataloader.leaves import DeviceLoader, LeavesDataset
+from .dataloader import eval_loader, open_reader
 from .eval import load_models
 from .eval_post import write_leaves_result
 from .test import test
@@ -30,14 +30,12 @@ from .test import test
 class Evaluate(object):
     def __init__(self, args):
         self.args, self.split, self.T = args, args.eval_split, args.maxseqlen
-        self.dataset = LeavesDataset(args, split=self.split, augment=False, resize=args.resize, imsize=args.imsize)   # :36
-        self.loader = DeviceLoader(self.dataset, args.batch_size, shuffle=False, num_workers=args.num_workers, seed=args.seed,
-                                   drop_last=False)                                                                  # :38-41
+        self.dataset = open_reader(args, self.split, dataset="leaves")                                               # :36
+        self.loader = eval_loader(args, self.dataset)                                                                # :38-41
         self.sample_list = self.dataset.get_sample_list()
         self.encoder, self.decoder = load_models(args)
 
     def create_figures(self):
-        from PIL import Image
         args = self.args
         results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results", "A1")
         os.makedirs(results_dir, exist_ok=True)
@@ -52,8 +50,7 @@ class Evaluate(object):
             Hm, Wm = x.size(-2), x.size(-1)
             for s in range(out_masks.shape[0]):
                 path = self.sample_list[s + acc]
-                with Image.open(path) as im:                                                    # :100-103 original size
-                    w, h = im.size
+                h, w = self.dataset.raw_size(s + acc)                                           # :100-103 original size
                 sample_idx = os.path.basename(path).split(".")[0]
                 written.append(write_leaves_result(args, sample_idx, out_masks[s].view(self.T, Hm, Wm), stop_probs[s], h, w, results_dir))
             acc += out_masks.shape[0]

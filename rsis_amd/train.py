@@ -635,18 +635,15 @@ def init_dataloaders(args, rank=0, world=1):
     GPUs, train.py:269-274): every rank of a torchrun job takes B / world samples, so reference hyper-parameters carry over.
     (The loss is the mean of the per-rank masked means -- equal to the global masked mean for equal shard sizes.)"""
     if not getattr(args, "synthetic", False):
-        if args.dataset not in ("leaves", "pascal", "cityscapes", "coco"):
+        from .dataloader import READERS, open_reader
+        if args.dataset not in READERS:
             raise Exception("data: --synthetic, -dataset leaves (CVPPP A1, BASELINE configs[0]), -dataset pascal, cityscapes or coco")
-        from .dataloader.cityscapes import CityScapes
-        from .dataloader.coco import COCO
-        from .dataloader.leaves import DeviceLoader, LeavesDataset
-        from .dataloader.pascal import PascalVOC
-        Dataset = {"leaves": LeavesDataset, "pascal": PascalVOC, "cityscapes": CityScapes, "coco": COCO}[args.dataset]
+        from .dataloader.loader import DeviceLoader
         if args.batch_size % world != 0:
             raise Exception("-batch_size %d (the global batch) is not divisible by the %d ranks" % (args.batch_size, world))
         loaders = {}
         for split in ("train", "val"):                                       # train.py:31-49
-            ds = Dataset(args, split=split, augment=args.augment and split == "train", resize=args.resize, imsize=args.imsize)
+            ds = open_reader(args, split, augment=args.augment and split == "train")
             loaders[split] = DeviceLoader(ds, args.batch_size // world, shuffle=True, num_workers=args.num_workers,
                                           seed=args.seed + (0 if split == "train" else 1), rank=rank, world=world)
         return loaders, ds.get_classes()

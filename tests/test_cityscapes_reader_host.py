@@ -151,10 +151,11 @@ def test_flip_flips_image_and_ids_together(tree):
 
 def test_loader_batches_same_size_datasets_without_crop_only(tree):
     from rsis_amd.dataloader.cityscapes import CityScapes
-    from rsis_amd.dataloader.leaves import DeviceLoader
+    from rsis_amd.dataloader.loader import DeviceLoader
 
     class Other(object):
         crop = False
+        same_size = False
     with pytest.raises(ValueError):
         DeviceLoader(Other(), 3, device="cpu")
     dl = DeviceLoader(CityScapes(_args(tree), split="train", imsize=32), 3, device="cpu")

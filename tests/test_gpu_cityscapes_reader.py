@@ -149,7 +149,7 @@ def test_device_loader_on_cityscapes_targets_equal_sequence_from_masks_of_the_wa
     from rsis_amd.dataloader import sequence_from_masks, targets
     from rsis_amd.dataloader.augment import affine_nearest
     from rsis_amd.dataloader.cityscapes import CityScapes
-    from rsis_amd.dataloader.leaves import MEAN, STD, DeviceLoader
+    from rsis_amd.dataloader.loader import MEAN, STD, DeviceLoader
     S, T = (32, 64), 20
     ds = CityScapes(_args(city_tree), split="train", imsize=32, augment=True)
     dl = DeviceLoader(ds, 3, shuffle=False, num_workers=2, seed=5)

@@ -285,7 +285,7 @@ def test_device_loader_batch_equals_the_host_pipeline(coco_tree, augment):
     from rsis_amd.dataloader import sequence_from_masks
     from rsis_amd.dataloader.augment import affine_nearest
     from rsis_amd.dataloader.coco import COCO
-    from rsis_amd.dataloader.leaves import MEAN, STD, DeviceLoader
+    from rsis_amd.dataloader.loader import MEAN, STD, DeviceLoader
     S, T, seed = 32, 20, 5
     ann = _annotation(coco_tree, "train2017")
     ds = COCO(_args(coco_tree), split="train", imsize=S, augment=augment)

@@ -237,7 +237,7 @@ def test_device_loader_on_pascal_targets_equal_sequence_from_masks_of_the_warped
     sequence_from_masks of the warped maps"""
     from rsis_amd.dataloader import sequence_from_masks
     from rsis_amd.dataloader.augment import affine_nearest
-    from rsis_amd.dataloader.leaves import MEAN, STD, DeviceLoader
+    from rsis_amd.dataloader.loader import MEAN, STD, DeviceLoader
     from rsis_amd.dataloader.pascal import PascalVOC
     d, _ = voc_tree
     S, T = 32, 10

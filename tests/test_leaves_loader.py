@@ -73,7 +73,8 @@ def test_device_loader_targets_equal_reference_sequence_from_masks(tmp_path):
     """without augmentation the device batch must be exactly batch_to_var(sequence_from_masks(host maps)) and the normalised image"""
     import random
     from rsis_amd.dataloader import sequence_from_masks
-    from rsis_amd.dataloader.leaves import MEAN, STD, DeviceLoader, LeavesDataset, synthesize_leaves_dir
+    from rsis_amd.dataloader.leaves import LeavesDataset, synthesize_leaves_dir
+    from rsis_amd.dataloader.loader import MEAN, STD, DeviceLoader
     d = synthesize_leaves_dir(str(tmp_path / "A1"), n=100, size=(96, 112), seed=2)
     ds = LeavesDataset(_args(d), split="train", imsize=64)
     dl = DeviceLoader(ds, 4, shuffle=False, num_workers=2, seed=5)

@@ -52,11 +52,11 @@ def test_synthetic_targets_clamp_instances_to_gt_slots():
 
 
 def test_leaves_loader_rank_sharding():
-    """rsis_amd.dataloader.leaves.shard_batches: under one process per GPU every rank sees len(ds) // (B_rank * world) steps per epoch
+    """rsis_amd.dataloader.loader.shard_batches: under one process per GPU every rank sees len(ds) // (B_rank * world) steps per epoch
     (the reference's len(ds) // B with B the global batch, train.py:46-49), the shards of a step are disjoint and their union is
     the global batch"""
     import random
-    from rsis_amd.dataloader.leaves import shard_batches
+    from rsis_amd.dataloader.loader import shard_batches
     order = list(range(103))
     random.Random(5).shuffle(order)
     for world, bs in ((1, 4), (2, 4), (8, 2), (4, 32)):

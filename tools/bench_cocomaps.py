@@ -132,7 +132,7 @@ def one_case(a, k):
 def loader_rates(a):
     import torch
     from rsis_amd.dataloader.coco import COCO, synthesize_coco_dir
-    from rsis_amd.dataloader.leaves import DeviceLoader
+    from rsis_amd.dataloader.loader import DeviceLoader
     d = synthesize_coco_dir(os.path.join(tempfile.mkdtemp(), "coco"), n=a.loader_images, sizes=((H, W),), sets=("train2017",))
     args = argparse.Namespace(gt_maxseqlen=a.T, batch_size=4, coco_dir=d, coco_train_set="train2017", coco_val_set="val2017", num_classes=4,
                               rotation=10, translation=0.1, shear=0.1, zoom=0.7)

@@ -36,7 +36,7 @@ def main(argv=None):
     ap.add_argument("--loader_images", type=int, default=8)
     a = ap.parse_args(argv)
     from rsis_amd.dataloader.cityscapes import CityScapes, maps_from_ids, synthesize_cityscapes_dir
-    from rsis_amd.dataloader.leaves import DeviceLoader
+    from rsis_amd.dataloader.loader import DeviceLoader
     from rsis_amd.dataloader.targets import targets_from_maps
     r = np.random.default_rng(0)
     B, H, W = a.batch, a.height, a.width

@@ -1,7 +1,8 @@
 import os, sys, time, argparse
 sys.path.insert(0, os.getcwd())
 import torch
-from rsis_amd.dataloader.leaves import LeavesDataset, DeviceLoader, synthesize_leaves_dir
+from rsis_amd.dataloader.leaves import LeavesDataset, synthesize_leaves_dir
+from rsis_amd.dataloader.loader import DeviceLoader
 d = synthesize_leaves_dir("/tmp/sb/A1", n=104, size=(272, 288), seed=3)
 a = argparse.Namespace(gt_maxseqlen=16, batch_size=2, leaves_dir=d, leaves_test_dir=d, rotation=10, translation=0.1, shear=0.1, zoom=0.7)
 ds = LeavesDataset(a, split="train", resize=True, imsize=256)
