@@ -409,6 +409,22 @@ int rsis_heads_fwd_keys(const unsigned long long* const* keys, float* const* sid
 int rsis_heads_bwd(const float* const* side, const int* Cside, int nside, int B, const float* Wc, int ncls, const float* Ws,
                    const float* class_probs, const float* dprobs, const float* dstop, float* const* dside, float* dWc, float* dbc,
                    float* dWs, float* dbs, void* stream);
+/* The WIDE heads family: the same operation for 1 <= ncls <= 1024 and ANY rows >= 1 (1 <= K <= 2048, nside <= 5; anything else
+ * RSIS_ERR_UNSUPPORTED, nothing written).  The callers use the three entry points above wherever those accept the call (the results of
+ * the two families agree to rounding, not by bits: the softmax sum and the sums over the rows are taken in another order).
+ * rsis_heads_wide_fwd: keys == NULL reads side[i] as rsis_heads_fwd does; otherwise keys / side_out / arg_out as rsis_heads_fwd_keys
+ * (side is ignored).  The softmax is reduced by the whole block in a fixed order.
+ * rsis_heads_wide_bwd: the semantics of rsis_heads_bwd (NULL dprobs / dstop = zero, NULL dside[i] / parameter targets skipped, the
+ * parameter gradients ACCUMULATED) in two launches on `stream`, no atomics, bit-reproducible: a pass over the rows that leaves the
+ * d-logits in scratch[rows][ncls + 1] and writes d side, then a pass over 16 x 64 tiles of the (ncls + 1) x K parameter gradient that
+ * sums over the rows in a fixed order.  scratch: device floats, scratch_floats >= rows * (ncls + 1) (RSIS_ERR_ARG otherwise, nothing
+ * written); it allocates nothing and can be captured into a graph. */
+int rsis_heads_wide_fwd(const unsigned long long* const* keys, float* const* side_out, int* const* arg_out, const float* const* side,
+                        const int* Cside, int nside, int rows, const float* Wc, const float* bc, int ncls, const float* Ws, const float* bs,
+                        float* class_probs, float* stop, void* stream);
+int rsis_heads_wide_bwd(const float* const* side, const int* Cside, int nside, int rows, const float* Wc, int ncls, const float* Ws,
+                        const float* class_probs, const float* dprobs, const float* dstop, float* const* dside, float* dWc, float* dbc,
+                        float* dWs, float* dbs, float* scratch, long scratch_floats, void* stream);
 
 /* ---- loss tail of a training iteration (train.py:159-176; hungarian.py:10-59): masked means of the class NLL (probs[n][C],
  * targets y_class[n] int64, optional per-class weights cls_w[C]), of the matched soft-IoU costs siou[n] and of the balanced stop

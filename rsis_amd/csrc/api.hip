@@ -905,6 +905,32 @@ int rsis_heads_bwd(const float* const* side, const int* Cside, int nside, int B,
   return rsis_l_heads_bwd(side, Cside, nside, B, Wc, ncls, Ws, class_probs, dprobs, dstop, dside, dWc, dbc, dWs, dbs, (hipStream_t)stream);
 }
 
+int rsis_heads_wide_fwd(const unsigned long long* const* keys, float* const* side_out, int* const* arg_out, const float* const* side,
+                        const int* Cside, int nside, int rows, const float* Wc, const float* bc, int ncls, const float* Ws, const float* bs,
+                        float* class_probs, float* stop, void* stream) {
+  if (nside < 1 || nside > 5) return RSIS_ERR_UNSUPPORTED;
+  if (!Cside || !Wc || !bc || !Ws || !bs || !class_probs || !stop) return RSIS_ERR_ARG;
+  if (keys) {
+    if (!side_out || !arg_out) return RSIS_ERR_ARG;
+    for (int i = 0; i < nside; ++i) if (!keys[i] || !side_out[i] || !arg_out[i]) return RSIS_ERR_ARG;
+    return rsis_l_heads_wide_fwd((const float* const*)side_out, Cside, nside, rows, Wc, bc, ncls, Ws, bs, class_probs, stop, (hipStream_t)stream,
+                                 keys, side_out, arg_out);
+  }
+  if (!side) return RSIS_ERR_ARG;
+  for (int i = 0; i < nside; ++i) if (!side[i]) return RSIS_ERR_ARG;
+  return rsis_l_heads_wide_fwd(side, Cside, nside, rows, Wc, bc, ncls, Ws, bs, class_probs, stop, (hipStream_t)stream);
+}
+
+int rsis_heads_wide_bwd(const float* const* side, const int* Cside, int nside, int rows, const float* Wc, int ncls, const float* Ws,
+                        const float* class_probs, const float* dprobs, const float* dstop, float* const* dside, float* dWc, float* dbc,
+                        float* dWs, float* dbs, float* scratch, long scratch_floats, void* stream) {
+  if (nside < 1 || nside > 5) return RSIS_ERR_UNSUPPORTED;
+  if (!side || !Cside || !Wc || !Ws || !class_probs) return RSIS_ERR_ARG;
+  for (int i = 0; i < nside; ++i) if (!side[i]) return RSIS_ERR_ARG;
+  return rsis_l_heads_wide_bwd(side, Cside, nside, rows, Wc, ncls, Ws, class_probs, dprobs, dstop, dside, dWc, dbc, dWs, dbs, scratch, scratch_floats,
+                               (hipStream_t)stream);
+}
+
 int rsis_largest_component(const unsigned char* mask, unsigned char* out, int* labels, int* counts, int* best, int n, int h, int w,
                            void* stream) {
   if (!mask || !out || !labels || !counts || !best || n < 1 || h < 1 || w < 1 || (long)h * w >= (1L << 31)) return RSIS_ERR_ARG;

@@ -88,6 +88,12 @@ int rsis_l_heads_fwd(const float* const* side, const int* C, int n, int B, const
                      int* const* arg_out = nullptr);
 int rsis_l_heads_bwd(const float* const* side, const int* C, int n, int B, const float* Wc, int ncls, const float* Ws, const float* probs, const float* dprobs,
                      const float* dstop, float* const* dside, float* dWc, float* dbc, float* dWs, float* dbs, hipStream_t st);
+int rsis_l_heads_wide_fwd(const float* const* side, const int* C, int n, int rows, const float* Wc, const float* bc, int ncls, const float* Ws,
+                          const float* bs, float* probs, float* stop, hipStream_t st, const unsigned long long* const* keys = nullptr,
+                          float* const* side_out = nullptr, int* const* arg_out = nullptr);
+int rsis_l_heads_wide_bwd(const float* const* side, const int* C, int n, int rows, const float* Wc, int ncls, const float* Ws, const float* probs,
+                          const float* dprobs, const float* dstop, float* const* dside, float* dWc, float* dbc, float* dWs, float* dbs, float* scratch,
+                          long scratch_floats, hipStream_t st);
 int rsis_l_loss_tail(const float* probs, const long long* y_class, const float* stop, const float* siou, const float* sw_mask, const float* sw_class,
                      const float* cls_w, int n, int C, float bw, float w_iou, float w_cls, float w_stop, float* out, float* dprobs, float* dstop, float* dsiou,
                      const float* gout, hipStream_t st);

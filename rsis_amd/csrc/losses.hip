@@ -401,6 +401,222 @@ int rsis_l_heads_bwd(const float* const* side, const int* C, int n, int B, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// The WIDE heads family: up to HEADS_WIDE_MAXC classes and any row count (the kernels above stop at 64 classes -- the serial softmax of
+// thread 0 -- and at the rows whose d-logits fit 64 KB of LDS in EVERY block).  Same operands, same +=/NULL semantics.
+//   forward  : one block per row as above, the logits in dynamic LDS (ncls + 1 floats), the softmax by the whole block -- a max and a
+//              sum reduction in a fixed order (per-thread strided partials, the wave tree, the four wave partials left to right);
+//   backward : two launches in stream order, no atomics.  The ROW pass (grid = rows) forms the d-logits of its row once, leaves them in
+//              the caller's scratch DL[rows][ncls + 1] and writes d side of the row; the PARAMETER pass (grid = tiles of the
+//              (ncls + 1) x K gradient) owns one 16 x 64 tile per block and walks ALL rows in LDS-staged chunks of 128, row 0 first:
+//              dW[r][k] += sum_i DL[i][r] * side[i][k], one fmaf chain per output -- the order does not depend on the grid.
+// The parameter pass is a small GEMM (13 MFLOP at 82 x 248 x 640 rows): plain FMAs from LDS, four outputs per thread.  It is far too
+// small to pay for an MFMA operand layout, and fp32 FMA chains keep the exact-integer contract of the tests.
+// LDS traffic of its inner loop: the 64 lanes of a wave read 64 consecutive floats of the side chunk (one bank each) and ONE float4 of
+// the d-logit chunk (a single address: broadcast); the staging writes are consecutive floats.  No two blocks write one address.
+// ------------------------------------------------------------------------------------------------
+#define HEADS_WIDE_MAXC 1024
+#define HW_TR 16              // gradient rows (classes | stop) of a parameter tile: 4 per wave
+#define HW_TK 64              // feature columns of a parameter tile: one per lane
+#define HW_CH 128             // rows staged per chunk
+
+__device__ __forceinline__ float heads_block_max256(float v, float* sh) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+
+__device__ __forceinline__ float heads_block_sum256(float v, float* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void heads_wide_fwd_kernel(HeadSides s, int K, const float* __restrict__ Wc, const float* __restrict__ bc,
+                                                             int ncls, const float* __restrict__ Ws, const float* __restrict__ bs,
+                                                             float* __restrict__ probs, float* __restrict__ stop) {
+  __shared__ float sv[HEADS_MAXK];
+  __shared__ float red[4];
+  extern __shared__ __attribute__((aligned(16))) float heads_lds[];
+  float* const lg = heads_lds;                         // [ncls + 1]
+  const int b = blockIdx.x;
+  heads_load_side(s, b, sv);
+  __syncthreads();
+  // one wave-quarter (16 lanes) per output row, as heads_fwd_kernel
+  const int row = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  for (int r = row; r <= ncls; r += 16) {
+    const float* w = r < ncls ? Wc + (size_t)r * K : Ws;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int k = sub; k < K; k += 64) {
+      const float w0 = w[k], w1 = k + 16 < K ? w[k + 16] : 0.f, w2 = k + 32 < K ? w[k + 32] : 0.f, w3 = k + 48 < K ? w[k + 48] : 0.f;
+      a0 = fmaf(w0, sv[k], a0);
+      a1 = fmaf(w1, k + 16 < K ? sv[k + 16] : 0.f, a1);
+      a2 = fmaf(w2, k + 32 < K ? sv[k + 32] : 0.f, a2);
+      a3 = fmaf(w3, k + 48 < K ? sv[k + 48] : 0.f, a3);
+    }
+    float acc = (a0 + a1) + (a2 + a3);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) acc += __shfl_down(acc, o, 16);
+    if (sub == 0) lg[r] = acc + (r < ncls ? bc[r] : bs[0]);
+  }
+  __syncthreads();
+  float m = -INFINITY;
+  for (int c = threadIdx.x; c < ncls; c += 256) m = fmaxf(m, lg[c]);
+  m = heads_block_max256(m, red);
+  float z = 0.f;
+  for (int c = threadIdx.x; c < ncls; c += 256) { const float e = expf(lg[c] - m); lg[c] = e; z += e; }     // (a thread revisits only its own classes)
+  z = heads_block_sum256(z, red);
+  for (int c = threadIdx.x; c < ncls; c += 256) probs[(size_t)b * ncls + c] = lg[c] / z;
+  if (threadIdx.x == 0) stop[b] = lg[ncls];
+}
+
+__global__ __launch_bounds__(256) void heads_wide_bwd_rows_kernel(HeadSides s, int K, const float* __restrict__ Wc, int ncls,
+                                                                  const float* __restrict__ Ws, const float* __restrict__ probs,
+                                                                  const float* __restrict__ dprobs, const float* __restrict__ dstop,
+                                                                  float* __restrict__ DLg) {
+  __shared__ float red[4];
+  extern __shared__ __attribute__((aligned(16))) float heads_lds[];
+  const int b = blockIdx.x, R = ncls + 1;
+  float* const dl = heads_lds;                         // [R]: probs, then d logits of fc_class | d stop
+  float* const gp = dl + R;                            // [ncls]: dprobs
+  float dot = 0.f;
+  for (int c = threadIdx.x; c < ncls; c += 256) {
+    const float p = probs[(size_t)b * ncls + c], g = dprobs ? dprobs[(size_t)b * ncls + c] : 0.f;
+    dl[c] = p;
+    gp[c] = g;
+    dot = fmaf(g, p, dot);
+  }
+  dot = heads_block_sum256(dot, red);
+  for (int c = threadIdx.x; c < ncls; c += 256) {       // softmax backward: p * (g - sum g p)
+    const float v = dl[c] * (gp[c] - dot);
+    dl[c] = v;
+    DLg[(size_t)b * R + c] = v;
+  }
+  if (threadIdx.x == 0) {
+    const float v = dstop ? dstop[b] : 0.f;
+    dl[ncls] = v;
+    DLg[(size_t)b * R + ncls] = v;
+  }
+  __syncthreads();
+  // d side[k] = sum_c dl[c] * Wc[c][k] + dstop * Ws[k]   (coalesced along k)
+  int base = 0;
+  for (int i = 0; i < s.n; ++i) {
+    if (s.d[i]) {
+      for (int k = threadIdx.x; k < s.C[i]; k += blockDim.x) {
+        const int kk = base + k;
+        float acc = dl[ncls] * Ws[kk];
+        for (int c0 = 0; c0 < ncls; c0 += 16) {
+          float wv[16];
+#pragma unroll
+          for (int j = 0; j < 16; ++j) wv[j] = c0 + j < ncls ? Wc[(size_t)(c0 + j) * K + kk] : 0.f;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) acc = fmaf(c0 + j < ncls ? dl[c0 + j] : 0.f, wv[j], acc);
+        }
+        s.d[i][(size_t)b * s.C[i] + k] = acc;
+      }
+    }
+    base += s.C[i];
+  }
+}
+
+__global__ __launch_bounds__(256) void heads_wide_bwd_params_kernel(HeadSides s, int K, int rows, int ncls, const float* __restrict__ DLg,
+                                                                    float* __restrict__ dWc, float* __restrict__ dbc,
+                                                                    float* __restrict__ dWs, float* __restrict__ dbs) {
+  __shared__ __attribute__((aligned(16))) float dls[HW_CH][HW_TR];
+  __shared__ float svs[HW_CH][HW_TK];
+  const int R = ncls + 1, r0 = blockIdx.x * HW_TR, k0 = blockIdx.y * HW_TK;
+  const int tk = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int k = k0 + tk;
+  const float* sp = nullptr;                           // feature k of row 0, and the row pitch of the side vector that holds it
+  int sc = 0;
+  if (k < K) {
+    int sb = 0, si = 0;
+    while (si < s.n - 1 && k >= sb + s.C[si]) { sb += s.C[si]; ++si; }
+    sp = s.p[si] + (k - sb);
+    sc = s.C[si];
+  }
+  float acc[4] = {0.f, 0.f, 0.f, 0.f}, bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  // a chunk travels global -> registers -> LDS: the loads of chunk c + 1 are issued before the FMAs of chunk c and land under them
+  // (written straight into LDS, one dependent global load per staged element, a chunk of 64 rows took 6 us)
+  float sreg[HW_CH / 4], dreg[HW_CH * HW_TR / 256];
+#define HW_LOAD(ROW0)                                                                                              \
+  {                                                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < HW_CH / 4; ++j) {                                                        \
+      const int row = (ROW0) + w + 4 * j;                                                                           \
+      sreg[j] = (sp && row < rows) ? sp[(size_t)row * sc] : 0.f;                                                    \
+    }                                                                                                               \
+    _Pragma("unroll") for (int j = 0; j < HW_CH * HW_TR / 256; ++j) {                                              \
+      const int e = threadIdx.x + 256 * j, row = (ROW0) + e / HW_TR, r = r0 + e % HW_TR;                            \
+      dreg[j] = (row < rows && r < R) ? DLg[(size_t)row * R + r] : 0.f;                                             \
+    }                                                                                                               \
+  }
+  HW_LOAD(0)
+  for (int row0 = 0; row0 < rows; row0 += HW_CH) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < HW_CH / 4; ++j) svs[w + 4 * j][tk] = sreg[j];
+#pragma unroll
+    for (int j = 0; j < HW_CH * HW_TR / 256; ++j) { const int e = threadIdx.x + 256 * j; dls[e / HW_TR][e % HW_TR] = dreg[j]; }
+    __syncthreads();
+    if (row0 + HW_CH < rows) HW_LOAD(row0 + HW_CH)
+#pragma unroll 8
+    for (int i = 0; i < HW_CH; ++i) {                    // (rows past the end were staged as zeros: they leave every sum unchanged)
+      const float4 d = *(const float4*)&dls[i][w * 4];
+      const float x = svs[i][tk];
+      acc[0] = fmaf(d.x, x, acc[0]); acc[1] = fmaf(d.y, x, acc[1]); acc[2] = fmaf(d.z, x, acc[2]); acc[3] = fmaf(d.w, x, acc[3]);
+      bsum[0] += d.x; bsum[1] += d.y; bsum[2] += d.z; bsum[3] += d.w;
+    }
+  }
+#undef HW_LOAD
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = r0 + w * 4 + j;
+    if (r >= R) continue;
+    if (k < K) {
+      if (r < ncls) { if (dWc) dWc[(size_t)r * K + k] += acc[j]; }
+      else if (dWs) dWs[k] += acc[j];
+    }
+    if (blockIdx.y == 0 && tk == 0) {                   // the bias gradients: the blocks of k-tile 0
+      if (r < ncls) { if (dbc) dbc[r] += bsum[j]; }
+      else if (dbs) dbs[0] += bsum[j];
+    }
+  }
+}
+
+int rsis_l_heads_wide_fwd(const float* const* side, const int* C, int n, int rows, const float* Wc, const float* bc, int ncls, const float* Ws,
+                          const float* bs, float* probs, float* stop, hipStream_t st, const unsigned long long* const* keys,
+                          float* const* side_out, int* const* arg_out) {
+  HeadSides s;
+  const int K = heads_sides(s, side, nullptr, C, n);
+  if (K < 1 || K > HEADS_MAXK || ncls < 1 || ncls > HEADS_WIDE_MAXC || rows < 1) return RSIS_ERR_UNSUPPORTED;
+  if (keys)
+    for (int i = 0; i < n; ++i) { s.key[i] = keys[i]; s.so[i] = side_out[i]; s.ao[i] = arg_out[i]; }
+  hipLaunchKernelGGL(heads_wide_fwd_kernel, dim3(rows), dim3(256), sizeof(float) * (ncls + 1), st, s, K, Wc, bc, ncls, Ws, bs, probs, stop);
+  return rsis_check_launch();
+}
+
+int rsis_l_heads_wide_bwd(const float* const* side, const int* C, int n, int rows, const float* Wc, int ncls, const float* Ws,
+                          const float* probs, const float* dprobs, const float* dstop, float* const* dside, float* dWc, float* dbc,
+                          float* dWs, float* dbs, float* scratch, long scratch_floats, hipStream_t st) {
+  HeadSides s;
+  const int K = heads_sides(s, side, dside, C, n);
+  if (K < 1 || K > HEADS_MAXK || ncls < 1 || ncls > HEADS_WIDE_MAXC || rows < 1) return RSIS_ERR_UNSUPPORTED;
+  if (!scratch || scratch_floats < (long)rows * (ncls + 1)) return RSIS_ERR_ARG;
+  hipLaunchKernelGGL(heads_wide_bwd_rows_kernel, dim3(rows), dim3(256), sizeof(float) * (2 * ncls + 1), st, s, K, Wc, ncls, Ws, probs, dprobs,
+                     dstop, scratch);
+  const int rc = rsis_check_launch();
+  if (rc != RSIS_OK) return rc;
+  if (!dWc && !dbc && !dWs && !dbs) return RSIS_OK;
+  const int R = ncls + 1;
+  hipLaunchKernelGGL(heads_wide_bwd_params_kernel, dim3((R + HW_TR - 1) / HW_TR, (K + HW_TK - 1) / HW_TK), dim3(256), 0, st, s, K, rows, ncls,
+                     scratch, dWc, dbc, dWs, dbs);
+  return rsis_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Loss tail of a training iteration (reference src/train.py:159-176 with utils/hungarian.py:10-59): the masked means of the
 // class NLL, the matched soft-IoU costs and the balanced stop BCE, and their weighted sum -- ~100 tiny eager launches (gather,
 // log, neg, where, sum, div, mul, ... and their autograd) folded into one single-block kernel each way.  n = B*T samples.

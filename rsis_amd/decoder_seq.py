@@ -63,7 +63,7 @@ def supported(decoder, skip_feats, T):
     if decoder.conv_out.kernel_size != 3 or decoder.conv_out.padding != 1 or decoder.conv_out.bias is None:
         return False
     hs = [c.hidden_size for c in decoder.clstm_list]
-    if sum(hs) != decoder.fc_class.weight.shape[1] or not ops.heads_supported([skip_feats[0]] * n, decoder.fc_class, decoder.fc_stop):
+    if sum(hs) != decoder.fc_class.weight.shape[1] or not ops.heads_supported([skip_feats[0]] * n, decoder.fc_class, decoder.fc_stop, min_rows=1):
         return False
     for i, c in enumerate(decoder.clstm_list):      # the channel pyramid of model.py:98-106 (level i consumes up(h[i-1]) | skip[i])
         c_up = 0 if i == 0 else hs[i - 1]
@@ -126,17 +126,19 @@ UPCONV = [os.environ.get("RSIS_UPCONV", "1") != "0"]       # the last level's up
 
 def _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, probs_tb, dp_tb, ds_tb, dsides, hb):
     """backward of the class / stop heads: the T * B rows of all timesteps in ONE launch (every row is independent; the parameter
-    gradients are sums over rows, which the kernel reduces itself) -- per timestep when the rows do not fit the kernel's LDS"""
-    def call(rows, sl):
-        return L.rsis_heads_bwd(ptr_array([lv.SIDE[sl] for lv in levels]), int_array(hs), n, rows, ptr(Wc.detach()), Wc.shape[0], ptr(Ws.detach()),
-                                ptr(probs_tb[sl]), ptr(dp_tb[sl]) if dp_tb is not None else None, ptr(ds_tb[sl]) if ds_tb is not None else None,
-                                ptr_array([ds[sl] for ds in dsides]), ptr(hb[0]), ptr(hb[1]), ptr(hb[2]), ptr(hb[3]), stream())
-    rc = call(T * B, slice(None))
-    if rc == 3:          # RSIS_ERR_UNSUPPORTED: more rows than the kernel's LDS holds
+    gradients are sums over rows, which the kernel reduces itself) -- per timestep when the rows do not fit the kernel's LDS, and on
+    the wide kernels (one launch pair over all T * B rows) where the kernel takes neither: the order of ops.heads_family"""
+    def call(rows, sl, wide=False):
+        return ops.heads_bwd_launch(L, [lv.SIDE[sl] for lv in levels], hs, rows, Wc, Ws, probs_tb[sl], dp_tb[sl] if dp_tb is not None else None,
+                                    ds_tb[sl] if ds_tb is not None else None, [ds[sl] for ds in dsides], hb, wide)
+    K, ncls = sum(hs), Wc.shape[0]
+    if ops.heads_family(T * B, K, ncls, backward=True) == "small":
+        check(call(T * B, slice(None)), "rsis_heads_bwd(all steps)")
+    elif ops.heads_family(B, K, ncls, backward=True) == "small":      # more rows than the kernel's LDS holds
         for t in range(T):
             check(call(B, t), "rsis_heads_bwd")
     else:
-        check(rc, "rsis_heads_bwd(all steps)")
+        check(call(T * B, slice(None), True), "rsis_heads_wide_bwd(all steps)")
 
 
 def _per_level(buf, hs, T, B):
@@ -455,9 +457,8 @@ class _DecoderSeqFn(torch.autograd.Function):
         def heads():
             """the class / stop heads (model.py:169-182) of ALL timesteps in one launch: every (t, b) row is independent, the per-level
             key / feature / arg-max arrays are [T][B][hid] contiguous, i.e. T * B rows; the launch decodes the pooled keys (writes SIDE / ARG)"""
-            check(L.rsis_heads_fwd_keys(ptr_array([v.KEY for v in levels]), ptr_array([v.SIDE for v in levels]), ptr_array([v.ARG for v in levels]),
-                                        int_array(hs), n, T * B, ptr(Wc.detach()), ptr(bc.detach()), Wc.shape[0], ptr(Ws.detach()), ptr(bs.detach()),
-                                        ptr(probs_tb), ptr(stop_tb), stream()), "rsis_heads_fwd_keys(all steps)")
+            ops.heads_fwd_launch(L, [v.SIDE for v in levels], hs, T * B, Wc, bc, Ws, bs, probs_tb, stop_tb,
+                                 ([v.KEY for v in levels], [v.ARG for v in levels]))
         # conv_out (model.py:167) on every timestep at once, logits straight into (B, T, N)
         out_masks = torch.empty((B, T, H5 * W5), **f32)
         if upc:       # upsample + conv_out in one pass, the upsampled tensor never formed (nor rounded to bf16)

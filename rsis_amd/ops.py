@@ -899,6 +899,50 @@ def softiou_matched(out_masks, y_mask, perm, S, e=1e-6):
     return _SoftIoUMatchedFn.apply(out_masks, y_mask, perm, S, float(e))
 
 
+# ---- THE rule that picks the heads kernels (csrc/losses.hip), asked by _HeadsFn and by decoder_seq's forward heads and
+# _heads_bwd_all_steps: the kernels of rsis_heads_fwd / rsis_heads_bwd whenever they accept the call -- what ran before the wide family
+# existed keeps its bits -- and the wide family (rsis_heads_wide_*) otherwise.  The limits restate rsis_l_heads_* (losses.hip).
+HEADS_MAXK, HEADS_MAXC, HEADS_WIDE_MAXC, HEADS_LDS_FLOATS = 2048, 64, 1024, 64 * 1024 // 4
+
+
+def heads_family(rows, K, ncls, backward=False):
+    """"small", "wide" or None (no kernel takes the call) for `rows` rows of K features and ncls classes; backward: rsis_heads_bwd also
+    needs 2 rows (ncls + 1) + rows ceil(K / rows) floats of LDS within 64 KB"""
+    if not (rows >= 1 and 1 <= K <= HEADS_MAXK and 1 <= ncls <= HEADS_WIDE_MAXC):
+        return None
+    if ncls <= HEADS_MAXC and (not backward or 2 * rows * (ncls + 1) + rows * ((K + rows - 1) // rows) <= HEADS_LDS_FLOATS):
+        return "small"
+    return "wide"
+
+
+def heads_fwd_launch(L, sides, Cs, rows, Wc, bc, Ws, bs, probs, stop, keys=None):
+    """the forward heads of `rows` rows on the family heads_family picks.  sides: the per-level feature tensors (with keys: where the
+    launch writes them); keys = (per-level key tensors, per-level arg-max tensors)"""
+    ncls, n = Wc.shape[0], len(Cs)
+    fam = heads_family(rows, sum(Cs), ncls)
+    w = (ptr(Wc.detach()), ptr(bc.detach()), ncls, ptr(Ws.detach()), ptr(bs.detach()), ptr(probs), ptr(stop), stream())
+    if fam == "wide":
+        if keys is not None:
+            check(L.rsis_heads_wide_fwd(ptr_array(keys[0]), ptr_array(sides), ptr_array(keys[1]), None, int_array(Cs), n, rows, *w), "rsis_heads_wide_fwd(keys)")
+        else:
+            check(L.rsis_heads_wide_fwd(None, None, None, ptr_array(sides), int_array(Cs), n, rows, *w), "rsis_heads_wide_fwd")
+    elif keys is not None:      # (fam None: the small entry point reports the refusal)
+        check(L.rsis_heads_fwd_keys(ptr_array(keys[0]), ptr_array(sides), ptr_array(keys[1]), int_array(Cs), n, rows, *w), "rsis_heads_fwd_keys")
+    else:
+        check(L.rsis_heads_fwd(ptr_array(sides), int_array(Cs), n, rows, *w), "rsis_heads_fwd")
+
+
+def heads_bwd_launch(L, sides, Cs, rows, Wc, Ws, probs, dprobs, dstop, dsides, hb, wide):
+    """one backward call over `rows` rows: rsis_heads_bwd, or (wide) the launch pair of rsis_heads_wide_bwd with its scratch"""
+    ncls = Wc.shape[0]
+    a = (ptr_array(sides), int_array(Cs), len(Cs), rows, ptr(Wc.detach()), ncls, ptr(Ws.detach()), ptr(probs), ptr(dprobs), ptr(dstop),
+         ptr_array(dsides), ptr(hb[0]), ptr(hb[1]), ptr(hb[2]), ptr(hb[3]))
+    if not wide:
+        return L.rsis_heads_bwd(*a, stream())
+    scratch = torch.empty(rows * (ncls + 1), dtype=torch.float32, device=Wc.device)
+    return L.rsis_heads_wide_bwd(*a, ptr(scratch), scratch.numel(), stream())
+
+
 class _HeadsFn(torch.autograd.Function):
     """class_probs, stop = softmax(fc_class(cat(sides))), fc_stop(cat(sides))  (reference model.py:169-182) in one launch each
     way; the concatenation is by pointer and the parameter gradients accumulate in place when DIRECT_GRAD is on."""
@@ -916,13 +960,7 @@ class _HeadsFn(torch.autograd.Function):
         B, ncls = sides[0].shape[0], Wc.shape[0]
         probs = torch.empty((B, ncls), dtype=torch.float32, device=Wc.device)
         stop = torch.empty((B, 1), dtype=torch.float32, device=Wc.device)
-        if keys is not None:
-            check(lib().rsis_heads_fwd_keys(ptr_array(keys[0]), ptr_array(sides), ptr_array(keys[1]), int_array([s.shape[1] for s in sides]),
-                                            n, B, ptr(Wc.detach()), ptr(bc.detach()), ncls, ptr(Ws.detach()), ptr(bs.detach()), ptr(probs),
-                                            ptr(stop), stream()), "rsis_heads_fwd_keys")
-        else:
-            check(lib().rsis_heads_fwd(ptr_array(sides), int_array([s.shape[1] for s in sides]), n, B, ptr(Wc.detach()), ptr(bc.detach()),
-                                       ncls, ptr(Ws.detach()), ptr(bs.detach()), ptr(probs), ptr(stop), stream()), "rsis_heads_fwd")
+        heads_fwd_launch(lib(), sides, [s.shape[1] for s in sides], B, Wc, bc, Ws, bs, probs, stop, keys)
         ctx.n = n
         ctx.extra = len(tensors) - (n + 4)
         ctx.shapes = [tuple(t.shape) for t in tensors[:n]]
@@ -948,17 +986,20 @@ class _HeadsFn(torch.autograd.Function):
             else:
                 tgts.append(None)
                 outs.append(None)
-        check(lib().rsis_heads_bwd(ptr_array(sides), int_array([s.shape[1] for s in sides]), n, B, ptr(Wc.detach()), ncls,
-                                   ptr(Ws.detach()), ptr(probs), ptr(dprobs), ptr(dstop), ptr_array(dsides), ptr(outs[0]),
-                                   ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), stream()), "rsis_heads_bwd")
+        Cs = [s.shape[1] for s in sides]
+        wide = heads_family(B, sum(Cs), ncls, backward=True) == "wide"
+        check(heads_bwd_launch(lib(), sides, Cs, B, Wc, Ws, probs, dprobs, dstop, dsides, outs, wide), "rsis_heads_wide_bwd" if wide else "rsis_heads_bwd")
         grads = [d.reshape(sh) if d is not None else None for d, sh in zip(dsides, ctx.shapes)]
         grads += [None if t is not None else o for t, o in zip(tgts, outs)]
         return (None,) + tuple(grads) + (None,) * ctx.extra
 
 
-def heads_supported(sides, fc_class, fc_stop):
-    return (sides[0].is_cuda and 2 <= sides[0].shape[0] <= 64 and len(sides) <= 5 and fc_class.weight.shape[1] <= 2048 and
-            fc_class.weight.shape[0] <= 64 and fc_stop.weight.shape[0] == 1 and fc_class.bias is not None and fc_stop.bias is not None)
+def heads_supported(sides, fc_class, fc_stop, min_rows=2):
+    """the heads run on the kernels (heads_family: either family).  A single row is left to the callers that ask for it (min_rows=1,
+    the sequence decoder): single-step RSIS.forward keeps the reference's 1-D outputs at B == 1 (model.py:169-182)"""
+    return (sides[0].is_cuda and sides[0].shape[0] >= min_rows and len(sides) <= 5 and fc_stop.weight.shape[0] == 1 and
+            fc_class.bias is not None and fc_stop.bias is not None and
+            heads_family(sides[0].shape[0], fc_class.weight.shape[1], fc_class.weight.shape[0]) is not None)
 
 
 def heads(sides, fc_class, fc_stop, keys=None):

@@ -30,6 +30,8 @@ def test(args, encoder, decoder, x, return_logits=False):
     for out_mask, out_class, out_stop in steps:
         out_mask = ops.upsample_bilinear_ac(out_mask, (x.size()[-2], x.size()[-1]))   # test.py:39-40
         out_masks.append(out_mask)
+        if out_class.dim() == 1:       # a batch of one on the per-step path: RSIS.forward keeps the reference's 1-D (C,) / (1,) outputs
+            out_class, out_stop = out_class.view(1, -1), out_stop.view(1, -1)
         out_classes.append(out_class)
         out_stops.append(out_stop)
     out_masks = torch.cat(out_masks, 1)                                 # test.py:46
