@@ -7,27 +7,8 @@
 //   * conv_out (model.py:109,167: 8 -> 1 channels, 3x3) over ALL T timesteps: forward, data gradient, weight + bias gradient.
 // The first three come as GROUPED launches: the cells of one diagonal of the decoder's (level, timestep) wavefront are independent,
 // so their jobs share a grid (job table by value in the kernel arguments, block ranges per job).
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned kd_pack2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ void kd_unpack(const u32x4 c, float (&v)[8]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { v[2 * k] = __uint_as_float(c[k] << 16); v[2 * k + 1] = __uint_as_float(c[k] & 0xFFFF0000u); }
-}
-__device__ __forceinline__ u32x4 kd_pack(const float (&v)[8]) {
-  u32x4 c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) c[k] = kd_pack2(v[2 * k], v[2 * k + 1]);
-  return c;
-}
 
 #define RSIS_KD_MAXJ 8
 template <typename J>
@@ -65,11 +46,11 @@ __global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGro
   ac_coord(wo, sw, Wi, w0, w1, lw);
   const u32x4* xb = (const u32x4*)p.src + pl * Hi * Wi;
   float v00[8], v01[8], v10[8], v11[8], o[8];
-  kd_unpack(xb[h0 * Wi + w0], v00); kd_unpack(xb[h0 * Wi + w1], v01);
-  kd_unpack(xb[h1 * Wi + w0], v10); kd_unpack(xb[h1 * Wi + w1], v11);
+  blk_cell_unpack(xb[h0 * Wi + w0], v00); blk_cell_unpack(xb[h0 * Wi + w1], v01);
+  blk_cell_unpack(xb[h1 * Wi + w0], v10); blk_cell_unpack(xb[h1 * Wi + w1], v11);
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = (1.f - lh) * ((1.f - lw) * v00[k] + lw * v01[k]) + lh * ((1.f - lw) * v10[k] + lw * v11[k]);
-  ((u32x4*)p.dst)[loc] = kd_pack(o);
+  ((u32x4*)p.dst)[loc] = blk_cell_pack(o);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -115,7 +96,7 @@ __global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGro
       for (int k = 0; k < KD_MAXC; ++k) {
         if (ww[k] != 0.f) {
           float v[8];
-          kd_unpack(yb[ho * Wo + wo_lo + k], v);
+          blk_cell_unpack(yb[ho * Wo + wo_lo + k], v);
 #pragma unroll
           for (int c = 0; c < 8; ++c) row[c] += ww[k] * v[c];
         }
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGro
         const float ww = (w0 == wi ? 1.f - lw : 0.f) + (w1 == wi ? lw : 0.f);
         if (ww != 0.f) {
           float v[8];
-          kd_unpack(yb[ho * Wo + wo], v);
+          blk_cell_unpack(yb[ho * Wo + wo], v);
 #pragma unroll
           for (int k = 0; k < 8; ++k) row[k] += ww * v[k];
         }
@@ -151,7 +132,7 @@ __global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGro
     for (int k = 0; k < 8; ++k)
       if (p.arg[pl * 8 + k] == sp) acc[k] += p.dpool[pl * 8 + k];
   }
-  ((u32x4*)p.dst)[loc] = kd_pack(acc);
+  ((u32x4*)p.dst)[loc] = blk_cell_pack(acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -169,9 +150,9 @@ __global__ __launch_bounds__(256) void blk_lstm_bwd_group_kernel(const KdGroup<B
   const long b = bc / Cbh;
   const int cbh = (int)(bc - b * Cbh);
   float dh[8], d2[8];
-  kd_unpack(((const u32x4*)p.dh)[loc], dh);
+  blk_cell_unpack(((const u32x4*)p.dh)[loc], dh);
   if (p.dh2) {
-    kd_unpack(((const u32x4*)p.dh2)[loc], d2);
+    blk_cell_unpack(((const u32x4*)p.dh2)[loc], d2);
 #pragma unroll
     for (int k = 0; k < 8; ++k) dh[k] += d2[k];
   }
@@ -187,7 +168,7 @@ __global__ __launch_bounds__(256) void blk_lstm_bwd_group_kernel(const KdGroup<B
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     float a[8], da[8];
-    kd_unpack(((const u32x4*)p.act)[a0 + (size_t)q * HW], a);
+    blk_cell_unpack(((const u32x4*)p.act)[a0 + (size_t)q * HW], a);
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
       const int k = 2 * q + h2;
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(256) void blk_lstm_bwd_group_kernel(const KdGroup<B
       da[4 * h2 + 3] = dcv * gi * (1.f - gg * gg);
       if (p.dc_prev) p.dc_prev[s0 + (size_t)k * HW] = dcv * gf;
     }
-    ((u32x4*)p.da)[a0 + (size_t)q * HW] = kd_pack(da);
+    ((u32x4*)p.da)[a0 + (size_t)q * HW] = blk_cell_pack(da);
   }
 }
 
@@ -247,13 +228,13 @@ __global__ __launch_bounds__(256) void blk_sum_leading_kernel(const u32x4* __res
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
   float acc[8], v[8];
-  kd_unpack(x[e], acc);
+  blk_cell_unpack(x[e], acc);
   for (int t = 1; t < T; ++t) {
-    kd_unpack(x[(size_t)t * n + e], v);
+    blk_cell_unpack(x[(size_t)t * n + e], v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] += v[k];
   }
-  y[e] = kd_pack(acc);
+  y[e] = blk_cell_pack(acc);
 }
 int rsis_l_blk_sum_leading(const void* x, void* y, int T, long n, hipStream_t st) {
   if ((n + 255) / 256 > 0x7FFFFFFFL) return RSIS_ERR_ARG;
@@ -271,7 +252,7 @@ __global__ __launch_bounds__(256) void blk_channel_sum_kernel(const u32x4* __res
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8];
   for (long i = (long)sp * 256 + threadIdx.x; i < n; i += (long)splits * 256) {
     const long b = i / HW;
-    kd_unpack(dy[(b * Cb + cb) * HW + (i - b * HW)], v);
+    blk_cell_unpack(dy[(b * Cb + cb) * HW + (i - b * HW)], v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] += v[k];
   }
@@ -337,7 +318,7 @@ __global__ __launch_bounds__(256) void blk_c1_fwd_kernel(const u32x4* __restrict
       const int ix = xq * 4 + c6 - 1;
       if ((unsigned)ix >= (unsigned)W) continue;
       float v[8];
-      kd_unpack(xb[iy * W + ix], v);
+      blk_cell_unpack(xb[iy * W + ix], v);
 #pragma unroll
       for (int o = 0; o < 4; ++o) {
         const int s = c6 - o;               // tap column of output o that reads input column c6
@@ -379,7 +360,7 @@ __global__ __launch_bounds__(256) void blk_c1_dgrad_kernel(const float* __restri
     for (int k = 0; k < 9; ++k) a = fmaf(wl[c * 9 + k], g[k], a);
     o[c] = a;
   }
-  dx[e] = kd_pack(o);
+  dx[e] = blk_cell_pack(o);
 }
 
 // weight + bias gradient: persistent blocks; a thread walks pixels, keeps the 72 + 1 sums, block reduction, one atomic per sum
@@ -397,7 +378,7 @@ __global__ __launch_bounds__(256) void blk_c1_wgrad_kernel(const float* __restri
     const float* gb = dy + c1b_ymap(img, B, T) * H * W;
     // dW[c][r][s] += sum over output pixels (oy, ox) of dy[oy][ox] * x[oy + r - 1][ox + s - 1][c]: this thread owns INPUT pixel (yy, xx)
     float v[8];
-    kd_unpack(x[e], v);
+    blk_cell_unpack(x[e], v);
     gsum += gb[yy * W + xx];
 #pragma unroll
     for (int r = 0; r < 3; ++r)

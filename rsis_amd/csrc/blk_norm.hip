@@ -8,30 +8,10 @@
 // in two levels -- S partial sums per channel written by the grid (double), summed again by every block of the apply pass (8
 // threads x S adds) -- so the result does not depend on the order blocks run in: bit-reproducible without atomics.
 // The arithmetic is fp32 on the exact bf16 inputs, with ONE rounding to bf16 at each store.
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
 #include <type_traits>
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void cell_unpack(const u32x4 c, float* v) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[2 * k] = __uint_as_float(c[k] << 16);
-    v[2 * k + 1] = __uint_as_float(c[k] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ u32x4 cell_pack(const float* v) {
-  u32x4 c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 f = {v[2 * k], v[2 * k + 1]};
-    c[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-  }
-  return c;
-}
 // cell index of element n = b * HW + sp of channel block cb
 // (n < B * HW < 2^31, checked by the launchers: ONE 32-bit division per cell -- the 64-bit one this replaced is ~80 instructions, and
 //  an apply thread does four of them before it can request its first cell)
@@ -111,7 +91,7 @@ __global__ __launch_bounds__(512) void blk_bn_fwd_block_kernel(const u32x4* __re
 #pragma unroll
   for (int u = 0; u < NPT; ++u) {
     float v[8];
-    cell_unpack(c[u], v);
+    blk_cell_unpack(c[u], v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) { a[k] += v[k]; a[8 + k] += v[k] * v[k]; }
   }
@@ -126,7 +106,7 @@ __global__ __launch_bounds__(512) void blk_bn_fwd_block_kernel(const u32x4* __re
     const double m = tot[k] / (double)N;
     double var = tot[8 + k] / (double)N - m * m;
     if (var < 0.0) var = 0.0;
-    const float mean = (float)m, rstd = rsqrtf((float)var + eps);
+    const float mean = (float)m, rstd = blk_bn_rstd((float)var, eps);
     save_mean[ch] = mean;
     save_rstd[ch] = rstd;
     if (run_mean) {
@@ -134,9 +114,7 @@ __global__ __launch_bounds__(512) void blk_bn_fwd_block_kernel(const u32x4* __re
       run_mean[ch] = (1.f - momentum) * run_mean[ch] + momentum * mean;
       run_var[ch] = (1.f - momentum) * run_var[ch] + momentum * unb;
     }
-    const float g = gamma[ch] * rstd;
-    sc[k] = g;
-    sh[k] = beta[ch] - mean * g;
+    blk_bn_affine(gamma[ch], beta[ch], mean, rstd, sc[k], sh[k]);
   }
   __syncthreads();
   float scv[8], shv[8];
@@ -146,12 +124,12 @@ __global__ __launch_bounds__(512) void blk_bn_fwd_block_kernel(const u32x4* __re
   for (int u = 0; u < NPT; ++u) {
     if (threadIdx.x + u * 512 >= N) continue;
     float v[8];
-    cell_unpack(c[u], v);
+    blk_cell_unpack(c[u], v);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = v[k] * scv[k] + shv[k];
+    for (int k = 0; k < 8; ++k) v[k] = blk_bn_apply(v[k], scv[k], shv[k]);
     if (res) {
       float rv[8];
-      cell_unpack(r[u], rv);
+      blk_cell_unpack(r[u], rv);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] += rv[k];
     }
@@ -159,7 +137,7 @@ __global__ __launch_bounds__(512) void blk_bn_fwd_block_kernel(const u32x4* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
     }
-    y[cell_index(threadIdx.x + u * 512, cb, Cb, HW)] = cell_pack(v);
+    y[cell_index(threadIdx.x + u * 512, cb, Cb, HW)] = blk_cell_pack(v);
   }
 }
 
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(256) void blk_bn_stats_kernel(const u32x4* __restri
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       float v[8];
-      cell_unpack(c[u], v);
+      blk_cell_unpack(c[u], v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) { a[k] += v[k]; a[8 + k] += v[k] * v[k]; }
     }
@@ -244,7 +222,7 @@ __global__ __launch_bounds__(256) void blk_bn_apply_kernel(const u32x4* __restri
       double var = q / (double)N - m * m;
       if (var < 0.0) var = 0.0;
       mean = (float)m;
-      rstd = rsqrtf((float)var + eps);
+      rstd = blk_bn_rstd((float)var, eps);
       if (blockIdx.x == 0) {
         save_mean[c] = mean;
         save_rstd[c] = rstd;
@@ -256,11 +234,9 @@ __global__ __launch_bounds__(256) void blk_bn_apply_kernel(const u32x4* __restri
       }
     } else {
       mean = run_mean[c];
-      rstd = rsqrtf(run_var[c] + eps);
+      rstd = blk_bn_rstd(run_var[c], eps);
     }
-    const float g = gam_c * rstd;
-    sc[k] = g;
-    sh[k] = bet_c - mean * g;
+    blk_bn_affine(gam_c, bet_c, mean, rstd, sc[k], sh[k]);
   }
   __syncthreads();
   float scv[8], shv[8];
@@ -272,12 +248,12 @@ __global__ __launch_bounds__(256) void blk_bn_apply_kernel(const u32x4* __restri
     if (n >= N) continue;
     const size_t idx = cell_index(n, cb, Cb, HW);
     float v[8];
-    cell_unpack(xc[u], v);
+    blk_cell_unpack(xc[u], v);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = v[k] * scv[k] + shv[k];
+    for (int k = 0; k < 8; ++k) v[k] = blk_bn_apply(v[k], scv[k], shv[k]);
     if (res) {
       float r[8];
-      cell_unpack(rc[u], r);
+      blk_cell_unpack(rc[u], r);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] += r[k];
     }
@@ -285,26 +261,26 @@ __global__ __launch_bounds__(256) void blk_bn_apply_kernel(const u32x4* __restri
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
     }
-    y[idx] = cell_pack(v);
+    y[idx] = blk_cell_pack(v);
   }
 }
 
 // ---- backward.  g = dy * [y > 0] (relu; y = the forward output.  Without y the mask is recomputed from x: no residual then);
 //      part[s][cb][0..7] = sum g, [8..15] = sum g * xhat ----
-// (scm / shm: the forward's fused scale / shift per channel, sc = gamma * rstd, sh = beta - mean * sc, computed once per thread)
+// (scm / shm: the forward's fused scale / shift per channel, blk_bn_affine of blk_cell.h, computed once per thread)
 __device__ __forceinline__ void bn_bwd_g(const u32x4 dyc, const u32x4 xc, const bool has_y, const u32x4 yc, const float* mean, const float* rstd,
                                          const float* scm, const float* shm, const int relu, float* g, float* xh) {
   float dv[8], xv[8], yv[8];
-  cell_unpack(dyc, dv);
-  cell_unpack(xc, xv);
-  if (has_y) cell_unpack(yc, yv);
+  blk_cell_unpack(dyc, dv);
+  blk_cell_unpack(xc, xv);
+  if (has_y) blk_cell_unpack(yc, yv);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     xh[k] = (xv[k] - mean[k]) * rstd[k];
     bool on = true;
     // (without y the mask is recomputed in the forward's own fused form x * sc + sh: the same roundings, so the mask is the one of
     //  the output the forward stored)
-    if (relu) on = has_y ? (yv[k] > 0.f) : (xv[k] * scm[k] + shm[k] > 0.f);
+    if (relu) on = has_y ? (yv[k] > 0.f) : (blk_bn_apply(xv[k], scm[k], shm[k]) > 0.f);
     g[k] = on ? dv[k] : 0.f;
   }
 }
@@ -320,7 +296,7 @@ __global__ __launch_bounds__(256) void blk_bn_bwd_reduce_kernel(const u32x4* __r
   for (int k = 0; k < 8; ++k) { mean[k] = save_mean[cb * 8 + k]; rstd[k] = save_rstd[cb * 8 + k]; gam[k] = gamma[cb * 8 + k]; bet[k] = beta[cb * 8 + k]; }
   float scm[8], shm[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) { scm[k] = gam[k] * rstd[k]; shm[k] = bet[k] - mean[k] * scm[k]; }
+  for (int k = 0; k < 8; ++k) blk_bn_affine(gam[k], bet[k], mean[k], rstd[k], scm[k], shm[k]);
   float a[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) a[k] = 0.f;
@@ -398,7 +374,7 @@ __global__ __launch_bounds__(256) void blk_bn_bwd_apply_kernel(const u32x4* __re
   for (int k = 0; k < 8; ++k) { mean[k] = sm[0][k]; rstd[k] = sm[1][k]; gam[k] = sm[2][k]; bet[k] = sm[3][k]; c1[k] = sm[4][k]; c2[k] = sm[5][k]; }
   float scm[8], shm[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) { scm[k] = gam[k] * rstd[k]; shm[k] = bet[k] - mean[k] * scm[k]; }
+  for (int k = 0; k < 8; ++k) blk_bn_affine(gam[k], bet[k], mean[k], rstd[k], scm[k], shm[k]);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const long n = ((long)blockIdx.x * U + u) * 256 + threadIdx.x;
@@ -408,8 +384,8 @@ __global__ __launch_bounds__(256) void blk_bn_bwd_apply_kernel(const u32x4* __re
     bn_bwd_g(dcv[u], xcv[u], has_y, ycv[u], mean, rstd, scm, shm, relu, g, xh);
 #pragma unroll
     for (int k = 0; k < 8; ++k) o[k] = gam[k] * rstd[k] * (g[k] - c1[k] - xh[k] * c2[k]);
-    dx[idx] = cell_pack(o);
-    if (dres) dres[idx] = cell_pack(g);
+    dx[idx] = blk_cell_pack(o);
+    if (dres) dres[idx] = blk_cell_pack(g);
   }
 }
 
@@ -438,7 +414,7 @@ __global__ __launch_bounds__(512) void blk_bn_bwd_block_kernel(const u32x4* __re
   for (int k = 0; k < 8; ++k) { mean[k] = save_mean[cb * 8 + k]; rstd[k] = save_rstd[cb * 8 + k]; gam[k] = gamma[cb * 8 + k]; bet[k] = beta[cb * 8 + k]; }
   float scm[8], shm[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) { scm[k] = gam[k] * rstd[k]; shm[k] = bet[k] - mean[k] * scm[k]; }
+  for (int k = 0; k < 8; ++k) blk_bn_affine(gam[k], bet[k], mean[k], rstd[k], scm[k], shm[k]);
   float a[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) a[k] = 0.f;
@@ -466,8 +442,8 @@ __global__ __launch_bounds__(512) void blk_bn_bwd_block_kernel(const u32x4* __re
 #pragma unroll
     for (int k = 0; k < 8; ++k) o[k] = gam[k] * rstd[k] * (g[k] - c1[k] - xh[k] * c2[k]);
     const size_t id = cell_index(threadIdx.x + u * 512, cb, Cb, HW);
-    dx[id] = cell_pack(o);
-    if (dres) dres[id] = cell_pack(g);
+    dx[id] = blk_cell_pack(o);
+    if (dres) dres[id] = blk_cell_pack(g);
   }
 }
 

@@ -19,29 +19,13 @@
 // The weights need no conversion and are copied global -> LDS by the LDS-DMA (`buffer_load_dwordx4 ... lds`).
 // With 16x the f32 MFMA rate these layers are HBM-bound (the f32 kernels are MFMA-bound): what matters here is bytes in
 // flight per CU and one pass over the input, not MFMA utilisation.
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
 #include <stdlib.h>
-#ifndef XCD_CHUNKED
-#define XCD_CHUNKED 1
-#endif
 
 enum { EPI_PLAIN = 0, EPI_LSTM = 1 };
-typedef __attribute__((address_space(3))) void* lds_vp_t;
 typedef const float __attribute__((address_space(1)))* gcf_t;
 typedef float __attribute__((address_space(1)))* gf_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define RSIS_OOB 0x7FFFFFF0u
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-
 // KS: 1 or 3.  BM: output rows per block (32 / 64 / 128 -> 1 / 2 / 4 waves along M).  TW x TH: output pixels per block (KS = 1:
 // TH = 1 and TW consecutive pixels of the flattened map).  CKB: input channels per LDS stage.  V4 (KS = 1, H*W % 4 == 0): the
 // activation tile is fetched as dwordx4 along the pixels.
@@ -76,21 +60,10 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
   const int H = KS == 1 ? 1 : p.H, W = KS == 1 ? p.H * p.W : p.W, HW = p.H * p.W;
   const int ldw = p.ldw;
 
-  // ---- block -> (co tile, spatial tile); blocks b, b+8, ... share an XCD: a tile's co tiles stay on one L2 ----
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = bid >> 3;
-  const int co_t = q % p.n_co_tiles;
-  // (XCD x owns the contiguous range [x * chunk, (x + 1) * chunk) of the spatial tiles: blocks b, b + 8, ... -- the ones this XCD
-  //  runs one after the other -- are NEIGHBOURING tiles, so the halo rows / columns two tiles share are L2 hits instead of a
-  //  second fetch from HBM by another XCD.  Measured against the round-robin map `(q / n_co_tiles) * 8 + xcd` (a build with
-  //  -DXCD_CHUNKED=0): the bf16 gate launch of the 112 x 112 level 48.4 -> 33.6 us, the fp32 128 x 128 level 83.7 -> 79.3 us.)
-  const int sp_t = XCD_CHUNKED ? xcd * ((p.n_px_tiles + 7) >> 3) + q / p.n_co_tiles : (q / p.n_co_tiles) * 8 + xcd;
+  int co_t, b0, x0, y0;      // block -> (co tile, spatial tile)
+  const int sp_t = blk_tile_of_block(blockIdx.x, p.n_co_tiles, p.n_px_tiles, co_t);
   if (sp_t >= p.n_px_tiles) return;
-  const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-  const int tx = sp_t % tiles_x;
-  const int ty = (sp_t / tiles_x) % tiles_y;
-  const int b0 = sp_t / (tiles_x * tiles_y);
-  const int x0 = tx * TW, y0 = ty * TH;
+  const int tiles = blk_tile_origin<TW, TH>(sp_t, W, H, b0, x0, y0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -125,18 +98,12 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
   // ---- per-lane LDS read bases (cells; the rest are immediates in the unrolled loop) ----
   int xoff[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int pp = (wn * TN + j) * 32 + l31;
-    const int x = pp % TW, y = pp / TW;
-    xoff[j] = hi * IMS + y * PW + x;
-  }
+  for (int j = 0; j < TN; ++j) xoff[j] = blk_xoff<TN, TW, PW, IMS>(wn, j, l31, hi);
   const int woff = hi * BM + wm * 32 + l31;
 
   f32x16 acc[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  for (int j = 0; j < TN; ++j) acc[j] = blk_acc_zero();
 
   const char* const wbase = (const char*)p.wp + (size_t)co_t * BM * 16;
 
@@ -185,14 +152,14 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
         if (NCB * (TW / 4) % 256 == 0 || cb < NCB) {                                                               \
           _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                          \
             u32x4 cell;                                                                                            \
-            _Pragma("unroll") for (int c2 = 0; c2 < 4; ++c2) cell[c2] = pack_bf16x2(rx[i][(2 * c2) * 4 + k], rx[i][(2 * c2 + 1) * 4 + k]); \
+            _Pragma("unroll") for (int c2 = 0; c2 < 4; ++c2) cell[c2] = blk_pack2(rx[i][(2 * c2) * 4 + k], rx[i][(2 * c2 + 1) * 4 + k]); \
             Xs[cb * TW + x4 * 4 + k] = cell;                                                                       \
           }                                                                                                        \
         }                                                                                                          \
       } else {                                                                                                     \
         if (XC % 256 == 0 || e < XC) {                                                                             \
           u32x4 cell;                                                                                              \
-          _Pragma("unroll") for (int c2 = 0; c2 < 4; ++c2) cell[c2] = pack_bf16x2(rx[i][2 * c2], rx[i][2 * c2 + 1]); \
+          _Pragma("unroll") for (int c2 = 0; c2 < 4; ++c2) cell[c2] = blk_pack2(rx[i][2 * c2], rx[i][2 * c2 + 1]); \
           Xs[e] = cell;                                                                                            \
         }                                                                                                          \
       }                                                                                                            \
@@ -218,14 +185,8 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
 #pragma unroll
         for (int r = 0; r < KS; ++r)
 #pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            const bf16x8 a = __builtin_bit_cast(bf16x8, Ws[((r * KS + s) * NCB + 2 * kk) * BM]);
-            bf16x8 b[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = __builtin_bit_cast(bf16x8, Xs[xoff[j] + 2 * kk * IMS + r * PW + s]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[j], acc[j], 0, 0, 0);
-          }
+          for (int s = 0; s < KS; ++s)
+            blk_mfma_tap<TN>(Xs + 2 * kk * IMS + r * PW + s, Ws + ((r * KS + s) * NCB + 2 * kk) * BM, xoff, acc);
     }
     BF_LAND()
     if (more) BF_STORE(cur ^ 1)
@@ -384,7 +345,7 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
       unsigned long long kk[4];
 #pragma unroll
       for (int r4 = 0; r4 < 4; ++r4) kk[r4] = rsis_key_max32(best[r4]);
-      rsis_side_key_max4(p.side_key + (size_t)b0 * p.hid, (co_base >> 2) + hi, p.hid, kk, l31 == 0, tiles_x * tiles_y >= RSIS_SIDE_CHECK_TILES);
+      rsis_side_key_max4(p.side_key + (size_t)b0 * p.hid, (co_base >> 2) + hi, p.hid, kk, l31 == 0, tiles >= RSIS_SIDE_CHECK_TILES);
     }
   }
 #endif
@@ -398,8 +359,6 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(const ConvArgs p) {
 // waits, raw `s_barrier`), a conversion pass turns the landed stage into bf16 cells (8 ds_read_b32 + 4 v_cvt_pk + 1 ds_write_b128
 // per cell, conflict-free both ways), and the MFMA loop reads cells exactly as before.  The weights ride the same ring.
 // ------------------------------------------------------------------------------------------------
-#define RSIS_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
-
 template <int BM, int BN, int CKB, int NR>
 __global__ __launch_bounds__(256) void conv1x1_bf16_ring_kernel(const ConvArgs p) {
 #if __HIP_DEVICE_COMPILE__
@@ -425,18 +384,11 @@ __global__ __launch_bounds__(256) void conv1x1_bf16_ring_kernel(const ConvArgs p
   const int HW = p.H * p.W, C = p.C[0];
   const int nq = (C + CKB - 1) / CKB;
   const int ldw = p.ldw;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = bid >> 3;
-  const int co_t = q % p.n_co_tiles;
-  // (XCD x owns the contiguous range [x * chunk, (x + 1) * chunk) of the spatial tiles: blocks b, b + 8, ... -- the ones this XCD
-  //  runs one after the other -- are NEIGHBOURING tiles, so the halo rows / columns two tiles share are L2 hits instead of a
-  //  second fetch from HBM by another XCD.  Measured against the round-robin map `(q / n_co_tiles) * 8 + xcd` (a build with
-  //  -DXCD_CHUNKED=0): the bf16 gate launch of the 112 x 112 level 48.4 -> 33.6 us, the fp32 128 x 128 level 83.7 -> 79.3 us.)
-  const int sp_t = XCD_CHUNKED ? xcd * ((p.n_px_tiles + 7) >> 3) + q / p.n_co_tiles : (q / p.n_co_tiles) * 8 + xcd;
+  int co_t, b0, x0, y0;      // (one row of tiles: the flattened map.  The zeroing and the tap loop below stay written out: through
+                             //  blk_acc_zero / blk_mfma_tap hipcc orders one v_mov of this kernel differently)
+  const int sp_t = blk_tile_of_block(blockIdx.x, p.n_co_tiles, p.n_px_tiles, co_t);
   if (sp_t >= p.n_px_tiles) return;
-  const int tiles_x = (HW + BN - 1) / BN;
-  const int tx = sp_t % tiles_x, b0 = sp_t / tiles_x;
-  const int x0 = tx * BN;
+  blk_tile_origin<BN, 1>(sp_t, HW, 1, b0, x0, y0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -509,7 +461,7 @@ __global__ __launch_bounds__(256) void conv1x1_bf16_ring_kernel(const ConvArgs p
         const float* r8 = raw + cb * 8 * BN + px;
         u32x4 cell;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) cell[k] = pack_bf16x2(r8[(2 * k) * BN], r8[(2 * k + 1) * BN]);
+        for (int k = 0; k < 4; ++k) cell[k] = blk_pack2(r8[(2 * k) * BN], r8[(2 * k + 1) * BN]);
         xb[c] = cell;
       }
     }

@@ -10,27 +10,9 @@
 //   * the epilogue packs the 4 consecutive output channels a lane holds per 8-row group into one 8-byte store (two lanes = a cell).
 // The MFMA loop, the LDS cell layout and the packed bf16 weights (pack.hip modes 5-7) are those of conv_bf16_kernel; the data
 // gradient is the same kernel on the flipped / transposed pack.  Stride 1, "same" padding, one source, C % 8 == 0, Cout % 8 == 0.
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
 #include <type_traits>
-
-typedef __attribute__((address_space(3))) void* lds_vp_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-#define RSIS_OOB 0x7FFFFFF0u
-#define RSIS_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
-#ifndef XCD_CHUNKED
-#define XCD_CHUNKED 1
-#endif
-
-__device__ __forceinline__ unsigned blk_pack2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
 
 // KS: 1 or 3.  BM: output channels per block (32 / 64 / 128 -> 1 / 2 / 4 waves along M).  TW x TH output pixels per block (KS = 1:
 // TH = 1 and TW consecutive pixels of the flattened map).  CKB: input channels per ring stage (KS = 3: the pack's chunk, 16).
@@ -59,17 +41,10 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
   const int H = KS == 1 ? 1 : p.H, W = KS == 1 ? p.H * p.W : p.W, HW = p.H * p.W;
   const int ldw = p.ldw;
 
-  // block -> (co tile, spatial tile): XCD x owns a contiguous range of the spatial tiles (conv_bf16.hip)
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = bid >> 3;
-  const int co_t = q % p.n_co_tiles;
-  const int sp_t = XCD_CHUNKED ? xcd * ((p.n_px_tiles + 7) >> 3) + q / p.n_co_tiles : (q / p.n_co_tiles) * 8 + xcd;
+  int co_t, b0, x0, y0;
+  const int sp_t = blk_tile_of_block(blockIdx.x, p.n_co_tiles, p.n_px_tiles, co_t);
   if (sp_t >= p.n_px_tiles) return;
-  const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-  const int tx = sp_t % tiles_x;
-  const int ty = (sp_t / tiles_x) % tiles_y;
-  const int b0 = sp_t / (tiles_x * tiles_y);
-  const int x0 = tx * TW, y0 = ty * TH;
+  blk_tile_origin<TW, TH>(sp_t, W, H, b0, x0, y0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -113,18 +88,12 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
 
   int xoff[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int pp = (wn * TN + j) * 32 + l31;
-    const int x = pp % TW, y = pp / TW;
-    xoff[j] = hi * IMS + y * PW + x;
-  }
+  for (int j = 0; j < TN; ++j) xoff[j] = blk_xoff<TN, TW, PW, IMS>(wn, j, l31, hi);
   const int woff = hi * BM + wm * 32 + l31;
 
   f32x16 acc[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  for (int j = 0; j < TN; ++j) acc[j] = blk_acc_zero();
 
   // prologue: NR - 1 chunks in flight
 #pragma unroll
@@ -147,20 +116,13 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
 #pragma unroll
         for (int r = 0; r < KS; ++r)
 #pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            const bf16x8 a = __builtin_bit_cast(bf16x8, Ws[((r * KS + s) * NCB + 2 * kk) * BM]);
-            bf16x8 b[TN];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = __builtin_bit_cast(bf16x8, Xs[xoff[j] + 2 * kk * IMS + r * PW + s]);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[j], acc[j], 0, 0, 0);
-          }
+          for (int s = 0; s < KS; ++s)
+            blk_mfma_tap<TN>(Xs + 2 * kk * IMS + r * PW + s, Ws + ((r * KS + s) * NCB + 2 * kk) * BM, xoff, acc);
     }
   }
 #undef BLK_ISSUE
 
-  // ---- epilogue: accumulator column = pixel l31, rows i + 8 g + 4 hi (r = 4 g + i) -> the half cell [4 hi, 4 hi + 4) of channel
-  //      block co_base / 8 + g: one 8-byte store; blocks >= Cout / 8 fall outside the descriptor ----
+  // ---- epilogue: one 8-byte half-cell store per (pixel group j, channel block g); blocks >= Cout / 8 fall outside the descriptor ----
   const int co_base = co_t * BM + wm * 32;
   const int Cbo = p.Cout >> 3;
   char* const obase = (char*)p.dst[0] + (size_t)b0 * Cbo * HW * 16;
@@ -170,14 +132,12 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
   const bool has_add = p.addend != nullptr;
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(has_add ? (const char*)p.addend + (size_t)b0 * Cbo * HW * 16 : obase), 0, has_add ? Cbo * HW * 16 : 0, 0x00020000);
-  // (the addend cells are fetched for the whole tile BEFORE the first store and outside any per-element condition: with the load
-  //  inside `if (has_add)` hipcc branches around each one and waits vmcnt(0) behind it -- 4 TN dependent L2 round trips per wave,
-  //  each also draining the stores issued so far)
+  // (the addend cells of the whole tile are fetched BEFORE the first store: blk_half_off in blk_cell.h)
   auto epilogue = [&](auto with_addend, auto with_affine) {
     constexpr bool ADD = decltype(with_addend)::value, AFF = decltype(with_affine)::value;
     // AFF (inference): the eval-mode BatchNorm (+ residual) (+ ReLU) of blk_bn_apply_kernel in the epilogue of the conv that feeds it,
-    // in that kernel's own arithmetic (rstd = rsqrtf(var + eps), g = gamma * rstd, y = x * g + (beta - mean * g), then the residual, then
-    // the ReLU); this lane's 16 channels are co_base + 8 g + 4 hi + i
+    // in that kernel's own arithmetic (blk_cell.h: blk_bn_affine, blk_bn_apply, then the residual, then the ReLU); this lane's 16
+    // channels are co_base + 8 g + 4 hi + i
     float sc[16], sh[16];
     if constexpr (AFF) {
       const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.ep_gamma, 0, p.Cout * 4, 0x00020000);
@@ -194,11 +154,7 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
         vv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, o, 0, 0));
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float rstd = rsqrtf(vv[r] + p.ep_eps);
-        sc[r] = gv[r] * rstd;
-        sh[r] = bv[r] - mv[r] * sc[r];
-      }
+      for (int r = 0; r < 16; ++r) blk_bn_affine(gv[r], bv[r], mv[r], blk_bn_rstd(vv[r], p.ep_eps), sc[r], sh[r]);
     }
     const bool pre_round = p.ep_round != 0;
     const bool relu = p.ep_relu != 0;
@@ -213,7 +169,7 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int cbo = (co_base >> 3) + g;
-        off[j][g] = (in && cbo < Cbo) ? (unsigned)(cbo * HW + osp) * 16u + 8u * hi : RSIS_OOB;
+        off[j][g] = (in && cbo < Cbo) ? blk_half_off(cbo, HW, osp, hi) : RSIS_OOB;
         if constexpr (ADD) av[j][g] = __builtin_amdgcn_raw_buffer_load_b64(ra, off[j][g], 0, 0);
       }
     }
@@ -225,14 +181,13 @@ __global__ __launch_bounds__(256) void conv_blk_kernel(const ConvArgs p) {
         if constexpr (AFF) {
           if (pre_round) {        // (the conv's own bf16 store of the unfused path, then its BatchNorm)
             const unsigned q0 = blk_pack2(o0, o1), q1 = blk_pack2(o2, o3);
-            o0 = __uint_as_float(q0 << 16); o1 = __uint_as_float(q0 & 0xFFFF0000u); o2 = __uint_as_float(q1 << 16); o3 = __uint_as_float(q1 & 0xFFFF0000u);
+            o0 = blk_lo(q0); o1 = blk_hi(q0); o2 = blk_lo(q1); o3 = blk_hi(q1);
           }
-          o0 = o0 * sc[4 * g] + sh[4 * g]; o1 = o1 * sc[4 * g + 1] + sh[4 * g + 1];
-          o2 = o2 * sc[4 * g + 2] + sh[4 * g + 2]; o3 = o3 * sc[4 * g + 3] + sh[4 * g + 3];
+          o0 = blk_bn_apply(o0, sc[4 * g], sh[4 * g]); o1 = blk_bn_apply(o1, sc[4 * g + 1], sh[4 * g + 1]);
+          o2 = blk_bn_apply(o2, sc[4 * g + 2], sh[4 * g + 2]); o3 = blk_bn_apply(o3, sc[4 * g + 3], sh[4 * g + 3]);
         }
         if constexpr (ADD) {
-          o0 += __uint_as_float(av[j][g][0] << 16); o1 += __uint_as_float(av[j][g][0] & 0xFFFF0000u);
-          o2 += __uint_as_float(av[j][g][1] << 16); o3 += __uint_as_float(av[j][g][1] & 0xFFFF0000u);
+          o0 += blk_lo(av[j][g][0]); o1 += blk_hi(av[j][g][0]); o2 += blk_lo(av[j][g][1]); o3 += blk_hi(av[j][g][1]);
         }
         if constexpr (AFF) {
           if (relu) { o0 = fmaxf(o0, 0.f); o1 = fmaxf(o1, 0.f); o2 = fmaxf(o2, 0.f); o3 = fmaxf(o3, 0.f); }
@@ -332,8 +287,8 @@ __global__ __launch_bounds__(256) void blk_to_nchw_kernel(const u32x4* __restric
   const u32x4 cell = x[e];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    d[(size_t)(2 * k) * HW] = __uint_as_float(cell[k] << 16);
-    d[(size_t)(2 * k + 1) * HW] = __uint_as_float(cell[k] & 0xFFFF0000u);
+    d[(size_t)(2 * k) * HW] = blk_lo(cell[k]);
+    d[(size_t)(2 * k + 1) * HW] = blk_hi(cell[k]);
   }
 }
 int rsis_l_blk_from_nchw(const float* x, void* y, int B, int C, int HW, hipStream_t st) {

@@ -2,7 +2,8 @@
 // BASELINE.json configs[2..4].  Reference ops: the ConvLSTM gates of src/modules/clstm.py:43-58 inside the decoder loop of
 // src/modules/model.py:129-165 (forward, fused cell epilogue), their data gradient, and the time-invariant skip term of the gates.
 //
-// conv_blk.hip is the trunk's kernel: one source, plain epilogue.  The decoder needs, on the same LDS-DMA ring and MFMA loop,
+// conv_blk.hip is the trunk's kernel: one source, plain epilogue.  The decoder needs, on the same LDS-DMA ring and MFMA loop
+// (the shared pieces are in blk_cell.h),
 //   * the channel concat of up to three blk sources ([up(h) | h_prev], torch.cat of clstm.py:43 folded into the chunk cursor),
 //   * the fused LSTM cell epilogue: gates = acc + G (blk addend, the hoisted skip term) -> sigma / tanh -> c (fp32 NCHW: the cell
 //     state keeps its precision over the T steps), h (blk, rounded ONCE), the saved gates (blk, rows 4 j + gate) and the packed
@@ -20,33 +21,12 @@
 // (r & 3) + 8 (r >> 2) + 4 hi, i.e. four groups of 4 consecutive rows.  For h the rows are gate-interleaved, so a lane holds all four
 // gates of hidden channels 2 r4 + hi: the two lanes (l31, hi = 0 / 1) exchange two values each (one wave shuffle pair) to own
 // channels 0-3 / 4-7 of the cell.
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
 #include <type_traits>
 #include <stdlib.h>
 
-typedef __attribute__((address_space(3))) void* lds_vp_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-#define RSIS_OOB 0x7FFFFFF0u
-#define RSIS_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
-#ifndef XCD_CHUNKED
-#define XCD_CHUNKED 1
-#endif
-
 enum { BEPI_PLAIN = 0, BEPI_LSTM = 1 };
-
-__device__ __forceinline__ unsigned bd_pack2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float bd_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bd_hi(unsigned v) { return __uint_as_float(v & 0xFFFF0000u); }
-__device__ __forceinline__ float bd_round(float v) { return bd_lo(bd_pack2(v, 0.f)); }      // the value a bf16 store keeps
 
 constexpr int bd_rows64(int n) { return (n + 63) / 64; }
 // 16-byte cells of LDS one block of a tile variant needs: a ring of NR stages of (activation patch + weight chunk), each padded to
@@ -80,15 +60,14 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
   const int q0 = (Cb0 + NCB - 1) / NCB, q1 = (Cb1 + NCB - 1) / NCB, q2 = (Cb2 + NCB - 1) / NCB;     // 16-channel chunks per source
   const int nq = q0 + q1 + q2;
 
+  // (block -> tile, the zeroing and the tap below are blk_tile_of_block, blk_acc_zero and blk_mfma_tap of blk_cell.h written out: called
+  //  from this body they change the instruction order of the group kernels, so the text stays)
   const int xcd = bid & 7, q = bid >> 3;
   const int co_t = q % p.n_co_tiles;
   const int sp_t = XCD_CHUNKED ? xcd * ((p.n_px_tiles + 7) >> 3) + q / p.n_co_tiles : (q / p.n_co_tiles) * 8 + xcd;
   if (sp_t >= p.n_px_tiles) return;
-  const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-  const int tx = sp_t % tiles_x;
-  const int ty = (sp_t / tiles_x) % tiles_y;
-  const int b0 = sp_t / (tiles_x * tiles_y);
-  const int x0 = tx * TW, y0 = ty * TH;
+  int b0, x0, y0;
+  const int tiles = blk_tile_origin<TW, TH>(sp_t, W, H, b0, x0, y0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -140,11 +119,7 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
 
   int xoff[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int pp = (wn * TN + j) * 32 + l31;
-    const int x = pp % TW, y = pp / TW;
-    xoff[j] = hi * IMS + y * PW + x;
-  }
+  for (int j = 0; j < TN; ++j) xoff[j] = blk_xoff<TN, TW, PW, IMS>(wn, j, l31, hi);
   const int woff = hi * BM + wm * 32 + l31;
 
   f32x16 acc[TN];
@@ -200,7 +175,7 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
       const int co = co_base + (r & 3) + 8 * (r >> 2) + 4 * hi;
       bv[r] = (bias && co < p.Cout) ? bias[co] : 0.f;
     }
-    // (addend cells of the whole tile first, outside any per-element condition: see conv_blk.hip)
+    // (addend cells of the whole tile first, outside any per-element condition: see blk_half_off in blk_cell.h)
     auto epilogue = [&](auto with_addend) {
       constexpr bool ADD = decltype(with_addend)::value;
       u32x2 av[TN][4];
@@ -213,7 +188,7 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int cbo = (co_base >> 3) + g;
-            av[j][g] = __builtin_amdgcn_raw_buffer_load_b64(ra, (oy < H && ox < W && cbo < Cbo) ? (unsigned)(cbo * HW + osp) * 16u + 8u * hi : RSIS_OOB, 0, 0);
+            av[j][g] = __builtin_amdgcn_raw_buffer_load_b64(ra, (oy < H && ox < W && cbo < Cbo) ? blk_half_off(cbo, HW, osp, hi) : RSIS_OOB, 0, 0);
           }
         }
       }
@@ -229,11 +204,11 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
           const bool ok = in && cbo < Cbo;
           float o0 = acc[j][4 * g] + bv[4 * g], o1 = acc[j][4 * g + 1] + bv[4 * g + 1];
           float o2 = acc[j][4 * g + 2] + bv[4 * g + 2], o3 = acc[j][4 * g + 3] + bv[4 * g + 3];
-          if constexpr (ADD) { o0 += bd_lo(av[j][g][0]); o1 += bd_hi(av[j][g][0]); o2 += bd_lo(av[j][g][1]); o3 += bd_hi(av[j][g][1]); }
-          const u32x2 v = {bd_pack2(o0, o1), bd_pack2(o2, o3)};
+          if constexpr (ADD) { o0 += blk_lo(av[j][g][0]); o1 += blk_hi(av[j][g][0]); o2 += blk_lo(av[j][g][1]); o3 += blk_hi(av[j][g][1]); }
+          const u32x2 v = {blk_pack2(o0, o1), blk_pack2(o2, o3)};
           const bool first = cbo < Cbd0;
-          const unsigned off0 = (ok && first) ? (unsigned)(cbo * HW + osp) * 16u + 8u * hi : RSIS_OOB;
-          const unsigned off1 = (ok && !first) ? (unsigned)((cbo - Cbd0) * HW + osp) * 16u + 8u * hi : RSIS_OOB;
+          const unsigned off0 = (ok && first) ? blk_half_off(cbo, HW, osp, hi) : RSIS_OOB;
+          const unsigned off1 = (ok && !first) ? blk_half_off(cbo - Cbd0, HW, osp, hi) : RSIS_OOB;
           __builtin_amdgcn_raw_buffer_store_b64(v, ro0, off0, 0, 0);
           if (Cbd1) __builtin_amdgcn_raw_buffer_store_b64(v, ro1, off1, 0, 0);
         }
@@ -273,7 +248,7 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
       for (int r4 = 0; r4 < 4; ++r4) {            // all loads of the tile first
         const int jh = 8 * cbh + 2 * r4 + hi;
         const bool ok = in && jh < hid;
-        ga[r4] = __builtin_amdgcn_raw_buffer_load_b64(r_add, ok ? (unsigned)((4 * cbh + r4) * HW + osp) * 16u + 8u * hi : RSIS_OOB, 0, 0);
+        ga[r4] = __builtin_amdgcn_raw_buffer_load_b64(r_add, ok ? blk_half_off(4 * cbh + r4, HW, osp, hi) : RSIS_OOB, 0, 0);
         cpv[r4] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_cp, ok ? (unsigned)(jh * HW + osp) * 4u : RSIS_OOB, 0, 0));
       }
       float hv[4];
@@ -281,22 +256,22 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
       for (int r4 = 0; r4 < 4; ++r4) {
         const int jh = 8 * cbh + 2 * r4 + hi;
         const bool ok = in && jh < hid;
-        const float ai = acc[j][4 * r4 + 0] + bv[4 * r4 + 0] + bd_lo(ga[r4][0]), af = acc[j][4 * r4 + 1] + bv[4 * r4 + 1] + bd_hi(ga[r4][0]);
-        const float ao = acc[j][4 * r4 + 2] + bv[4 * r4 + 2] + bd_lo(ga[r4][1]), ag = acc[j][4 * r4 + 3] + bv[4 * r4 + 3] + bd_hi(ga[r4][1]);
+        const float ai = acc[j][4 * r4 + 0] + bv[4 * r4 + 0] + blk_lo(ga[r4][0]), af = acc[j][4 * r4 + 1] + bv[4 * r4 + 1] + blk_hi(ga[r4][0]);
+        const float ao = acc[j][4 * r4 + 2] + bv[4 * r4 + 2] + blk_lo(ga[r4][1]), ag = acc[j][4 * r4 + 3] + bv[4 * r4 + 3] + blk_hi(ga[r4][1]);
         const float gi = rsis_sigmoid_fast(ai), gf = rsis_sigmoid_fast(af), go = rsis_sigmoid_fast(ao), gg = rsis_tanh_fast(ag);
         const float c = gf * cpv[r4] + gi * gg;     // clstm.py:57
         const float h = go * rsis_tanh_fast(c);      // clstm.py:58
         hv[r4] = h;
         if (p.side_key && ok) { const unsigned long long k = rsis_side_key(h, osp); best[r4] = k > best[r4] ? k : best[r4]; }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c), r_c, ok ? (unsigned)(jh * HW + osp) * 4u : RSIS_OOB, 0, 0);
-        const u32x2 av = {bd_pack2(gi, gf), bd_pack2(go, gg)};
-        __builtin_amdgcn_raw_buffer_store_b64(av, r_act, ok ? (unsigned)((4 * cbh + r4) * HW + osp) * 16u + 8u * hi : RSIS_OOB, 0, 0);
+        const u32x2 av = {blk_pack2(gi, gf), blk_pack2(go, gg)};
+        __builtin_amdgcn_raw_buffer_store_b64(av, r_act, ok ? blk_half_off(4 * cbh + r4, HW, osp, hi) : RSIS_OOB, 0, 0);
       }
       // h cell: this lane holds channels 2 r4 + hi; lane (l31, 0) takes channels 0-3, lane (l31, 1) channels 4-7
       const float s0 = hi ? hv[0] : hv[2], s1 = hi ? hv[1] : hv[3];
       const float g0 = __shfl_xor(s0, 32, 64), g1 = __shfl_xor(s1, 32, 64);
-      const u32x2 hc = hi ? u32x2{bd_pack2(g0, hv[2]), bd_pack2(g1, hv[3])} : u32x2{bd_pack2(hv[0], g0), bd_pack2(hv[1], g1)};
-      __builtin_amdgcn_raw_buffer_store_b64(hc, r_h, (in && cbh < Cbh) ? (unsigned)(cbh * HW + osp) * 16u + 8u * hi : RSIS_OOB, 0, 0);
+      const u32x2 hc = hi ? u32x2{blk_pack2(g0, hv[2]), blk_pack2(g1, hv[3])} : u32x2{blk_pack2(hv[0], g0), blk_pack2(hv[1], g1)};
+      __builtin_amdgcn_raw_buffer_store_b64(hc, r_h, (in && cbh < Cbh) ? blk_half_off(cbh, HW, osp, hi) : RSIS_OOB, 0, 0);
     }
     if (p.side_key) {
       unsigned long long kk[4];
@@ -305,7 +280,7 @@ __device__ __forceinline__ void bd_body(const BlkConvJob& p, const int bid, u32x
       // (parked in the ring slot nobody reads any more: the last chunk sits in slot (nq - 1) % NR, slot nq % NR was last read before the
       //  barrier every wave has passed and nothing was issued into it since -- no LDS of its own: 40 KB is four blocks per CU exactly)
       rsis_side_key_block((unsigned long long*)(lds + (nq % NR) * STG), wave, WGM, WGN, hi, kk, l31 == 0, p.side_key + (size_t)b0 * hid, (co_t * BM) >> 2, hid,
-                          tiles_x * tiles_y >= RSIS_SIDE_CHECK_TILES);
+                          tiles >= RSIS_SIDE_CHECK_TILES);
     }
   }
 #endif

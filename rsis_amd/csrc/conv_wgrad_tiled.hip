@@ -42,8 +42,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
 
 // limb pairs (A limb, B limb) of one K16 step, smallest weight first.  The first WG_LIMB_PRODUCTS are issued: 6 = the pairs with
 // i + j <= 2; 9 would be the exact product.  (RSIS_LIMB_PA / PB of limb_split.h issue the same six in ANOTHER order, for the staged
@@ -53,8 +51,8 @@ typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
 [[maybe_unused]] __device__ constexpr int wg_limb_pb[9] = {0, 1, 2, 0, 1, 0, 1, 2, 2};
 
 // eight fp32 values (k = 0..7 of a lane's fragment) -> three bf16x8 limb fragments; element 2m sits in the low half of dword m
-__device__ __forceinline__ void wg_limb_pack8(const float (&v)[8], wg_bf16x8 (&out)[3]) {
-  wg_u32x4 q[3];
+__device__ __forceinline__ void wg_limb_pack8(const float (&v)[8], bf16x8 (&out)[3]) {
+  u32x4 q[3];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     float lo[3], hi[3];
@@ -66,7 +64,7 @@ __device__ __forceinline__ void wg_limb_pack8(const float (&v)[8], wg_bf16x8 (&o
     q[2][m] = __builtin_amdgcn_perm(__float_as_uint(hi[2]), __float_as_uint(lo[2]), 0x07060302u);
   }
 #pragma unroll
-  for (int l = 0; l < 3; ++l) out[l] = __builtin_bit_cast(wg_bf16x8, q[l]);
+  for (int l = 0; l < 3; ++l) out[l] = __builtin_bit_cast(bf16x8, q[l]);
 }
 
 struct WgradTiledArgs {
@@ -276,7 +274,7 @@ __device__ __forceinline__ void wgrad_tiled_body(const WgradTiledArgs& p, const 
       if constexpr (LIMB) {
 #pragma unroll
         for (int g = 0; g < NG / 2 / KSP; g += 2) {       // step blocks g, g + 1 = one K16 step
-          wg_bf16x8 al[TM][3], bl[TN][3];
+          bf16x8 al[TM][3], bl[TN][3];
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
             const f32x4 a0 = *reinterpret_cast<const f32x4*>(As + i * 32 * TP + sg[g]);

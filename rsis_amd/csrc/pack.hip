@@ -9,7 +9,7 @@
 //   direct-3x3 layout   :  8-channel chunks per segment (zero padded); inside a chunk row (c2*9 + rs)*2 + h is channel
 //                          c0 + 2*c2 + h, tap rs.  FWD columns = co_p; DGRAD rows = chunks of co_p, columns = cg, tap 8-rs.
 // co_p -> reference row: (co_p&3)*hid + (co_p>>2) for gate-interleaved ConvLSTM rows (clstm.py:47), identity otherwise.
-#include "common.h"
+#include "blk_cell.h"
 #include "../../include/rsis_hip.h"
 #include "launchers.h"
 
@@ -93,13 +93,7 @@ __global__ void pack_kernel(int mode, const float* __restrict__ W, float* __rest
 //   a concat segment, the tail of a segment is zero), tap rs, 8-channel block cb of the chunk; NCB = CKB / 8.
 //   PACK_BF16_FWD: reduction channel = input channel of the concat, col = co_p.
 //   PACK_BF16_DGRAD: reduction channel = dy channel co_p, col = cg (index in the concat), 3x3 taps flipped.
-typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pk_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ unsigned short to_bf16(float v) {
-  const pk_f32x2 f = {v, 0.f};
-  return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f, pk_bf16x2)) & 0xFFFFu);
-}
+__device__ __forceinline__ unsigned short to_bf16(float v) { return (unsigned short)(blk_pack2(v, 0.f) & 0xFFFFu); }
 
 __device__ __forceinline__ int pack_bf16_idx(int mode, int kb, int col, int e, int Cout, int Ctot, int KK, const SegMap& m, int hid) {
   const int CKB = bf16_ckb(KK), NCB = CKB / 8;
@@ -180,10 +174,10 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
         if (dst[u] >= 0) lds16[dst[u]] = to_bf16(src[u] < 0 ? 0.f : v[u]);
     }
     __syncthreads();
-    const pk_u32x4* src = (const pk_u32x4*)lds16;
+    const u32x4* src = (const u32x4*)lds16;
     for (int i = threadIdx.x; i < R * 64; i += 256) {
       const int rr = i >> 6, cl = i & 63;
-      *(pk_u32x4*)(out + ((long)(q * R + rr) * j.ldw + c0 + cl) * 8) = src[i];
+      *(u32x4*)(out + ((long)(q * R + rr) * j.ldw + c0 + cl) * 8) = src[i];
     }
   } else {
     const int r0 = (tb / nct) * 16;
@@ -202,8 +196,8 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
         const unsigned lo = to_bf16(src[2 * e2] < 0 ? 0.f : f[2 * e2]), hi = to_bf16(src[2 * e2 + 1] < 0 ? 0.f : f[2 * e2 + 1]);
         v[e2] = lo | (hi << 16);
       }
-      const pk_u32x4 cell = {v[0], v[1], v[2], v[3]};
-      *(pk_u32x4*)(out + ((long)(r0 + rr) * j.ldw + c0 + cl) * 8) = cell;
+      const u32x4 cell = {v[0], v[1], v[2], v[3]};
+      *(u32x4*)(out + ((long)(r0 + rr) * j.ldw + c0 + cl) * 8) = cell;
     }
   }
 }

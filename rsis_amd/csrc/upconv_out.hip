@@ -17,10 +17,8 @@
 // order; the logits and their gradient are fp32 [B][T][Ho*Wo] (image t * B + b of the former pairs with image b * T + t of the
 // latter, as rsis_conv_out_seq_*).  w is the reference layout [1][8][3][3].
 // HBM-bound: algorithmic bytes per launch = the three tensors once (fwd: h + out; bwd: dout + h + dh).
-#include "common.h"
+#include "blk_cell.h"
 #include "launchers.h"
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 struct UpconvArgs {
   const void* h;
@@ -38,20 +36,10 @@ struct UpconvArgs {
   int ntiles;
 };
 
-__device__ __forceinline__ float bf_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(unsigned v) { return __uint_as_float(v & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned bf_pack2(float lo, float hi) {
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  const f32x2_t f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
 template <int HBLK>
-__device__ __forceinline__ void load_h8(const void* h, long img, int HsWs, int sp, float* v) {
+__device__ __forceinline__ void load_h8(const void* h, long img, int HsWs, int sp, float (&v)[8]) {
   if constexpr (HBLK) {
-    const u32x4_t c = ((const u32x4_t*)h)[img * HsWs + sp];
-    v[0] = bf_lo(c[0]); v[1] = bf_hi(c[0]); v[2] = bf_lo(c[1]); v[3] = bf_hi(c[1]);
-    v[4] = bf_lo(c[2]); v[5] = bf_hi(c[2]); v[6] = bf_lo(c[3]); v[7] = bf_hi(c[3]);
+    blk_cell_unpack(((const u32x4*)h)[img * HsWs + sp], v);
   } else {
     const float* p = (const float*)h + img * 8 * HsWs + sp;
 #pragma unroll
@@ -320,8 +308,7 @@ __global__ __launch_bounds__(256, 2) void upconv_bwd_kernel(const UpconvArgs a) 
           dv[c] = s;
         }
         if constexpr (HBLK) {
-          const u32x4_t cell = {bf_pack2(dv[0], dv[1]), bf_pack2(dv[2], dv[3]), bf_pack2(dv[4], dv[5]), bf_pack2(dv[6], dv[7])};
-          ((u32x4_t*)a.dh)[(long)m * HsWs + sp] = cell;
+          ((u32x4*)a.dh)[(long)m * HsWs + sp] = blk_cell_pack(dv);
         } else {
           float* const p = (float*)a.dh + (long)m * 8 * HsWs + sp;
 #pragma unroll

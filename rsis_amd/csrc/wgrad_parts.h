@@ -3,16 +3,8 @@
 // two epilogues.  Device code: included by
 // conv_wgrad_bf16.hip and, for wg_atomic_tiles, by conv_wgrad_tiled.hip.
 #pragma once
-#include "common.h"
+#include "blk_cell.h"
 #include "limb_split.h"
-
-typedef __attribute__((address_space(3))) void* lds_vp_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define RSIS_OOB 0x7FFFFFF0u
-#define RSIS_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 
 // ---- stage geometries ----
 constexpr int WG_CU_LDS = 160 * 1024;                 // LDS of a CU
@@ -83,11 +75,6 @@ __device__ __forceinline__ char* wgb_stage_lds() {
 }
 
 // ---- staging of the register-staged bodies ----
-__device__ __forceinline__ unsigned wg_pack2(float lo, float hi) {
-  const f32x2 f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-
 // One staging task = 8 consecutive pixels of one row of one channel -> one 16-byte bf16 cell.
 // V4: two dwordx4 loads (W % 4 == 0: each is entirely inside or outside the row); otherwise 8 dword loads + a validity mask.
 template <bool V4>
@@ -111,7 +98,7 @@ struct Task8 {
   __device__ __forceinline__ u32x4 cell() const {
     u32x4 c;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = wg_pack2(v[2 * k], v[2 * k + 1]);
+    for (int k = 0; k < 4; ++k) c[k] = blk_pack2(v[2 * k], v[2 * k + 1]);
     return c;
   }
   // LIMBS: the three exact bf16 limbs of the 8 values (limb_split.h) as three cells, one per limb plane of the stage.  (The stores of
