@@ -81,12 +81,16 @@ __device__ __forceinline__ float rsis_tanh_fast(float x) { return 2.0f * __built
 
 // align_corners=True bilinear source coordinate (nn.UpsamplingBilinear2d: model.py:149,163): output index o reads inputs i0, i1
 // with weights (1 - l1, l1).  One definition for every kernel that must agree bit for bit on which inputs an output touches.
+// i0 comes from the ROUNDED product; l1 = scale * o - i0 is ONE fused multiply-add, written out: left as `src - i0` the compiler
+// contracted it in the forward kernels and in the generic backward but not in the tiled backward's table loop, whose weights then
+// differed from the forward's by up to half an ulp of the coordinate -- the backward was not the adjoint of the forward it follows.
 __device__ __forceinline__ void ac_coord(int o, float scale, int in, int& i0, int& i1, float& l1) {
-  const float src = scale * o;
+  const float of = (float)o;
+  const float src = scale * of;
   i0 = (int)src;
   if (i0 > in - 1) i0 = in - 1;
   i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - i0;
+  l1 = fmaf(scale, of, -(float)i0);
 }
 static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 

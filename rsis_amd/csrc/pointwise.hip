@@ -317,8 +317,10 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
       const int ly = e / RM, c = e - ly * RM;
       const int r0 = st[0][ly] - oy;
       float acc = 0.f;
+      // weights beyond the region are zero.  An input row that NO output touches (scale > 2) starts at min(l, out - 1), which can lie
+      // above the region's origin: clamped at 0 as well (its weights are all zero, but 0 * a stray LDS word need not be)
 #pragma unroll
-      for (int k = 0; k < UK; ++k) acc = fmaf(wgt[0][ly][k], reg[min(r0 + k, ey - 1) * RP + cs + c], acc);   // weights beyond the region are zero
+      for (int k = 0; k < UK; ++k) acc = fmaf(wgt[0][ly][k], reg[min(max(r0 + k, 0), ey - 1) * RP + cs + c], acc);
       tmp[ly * RP + c] = acc;
     }
     __syncthreads();
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
       const int c0 = st[1][lx] - ox;
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < UK; ++k) acc = fmaf(wgt[1][lx][k], tmp[ly * RP + min(c0 + k, ex - 1)], acc);
+      for (int k = 0; k < UK; ++k) acc = fmaf(wgt[1][lx][k], tmp[ly * RP + min(max(c0 + k, 0), ex - 1)], acc);
       if (pool_g && hi * Wi + wi == pool_arg[bc]) acc += pool_g[bc];     // + the global max-pool's gradient at its arg-max pixel
       dx[bc * Hi * Wi + (size_t)hi * Wi + wi] = acc;
     }
