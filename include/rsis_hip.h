@@ -227,6 +227,44 @@ int rsis_global_maxpool_bwd(const float* dy, const int* argmax, float* dx, long 
 /* dx[bc][argmax[bc]] += dy[bc] (dx already holds the gradient of another consumer of the same tensor) */
 int rsis_global_maxpool_bwd_add(const float* dy, const int* argmax, float* dx, long BC, int HW, void* stream);
 
+/* ---- the decoder's dropout (model.py:137-182: nn.Dropout2d on every level's hidden state, nn.Dropout on the class / stop head
+ * features), folded into the launches the decoder already makes.  Dropout2d is ONE factor s in {0, 1 / (1 - p)} per channel plane:
+ * it commutes with the global max-pool (s >= 0) and with the bilinear resize, so no kernel ever forms the dropped hidden state.
+ * `scale` below is [BC] fp32, one factor per plane; a NULL scale makes every call the unscaled entry point above, bit for bit.
+ *   rsis_upsample_bilinear_ac_scaled_fwd : y = scale * resize(x): interpolated in fp32 as rsis_upsample_bilinear_ac_fwd does, then
+ *                                          multiplied (equal sizes: the scaled copy);
+ *   rsis_upsample_maxpool_scaled_bwd     : dx = scale * (resize^T(dy) + dpool at argmax);
+ *   rsis_global_maxpool_scaled_bwd_add   : dx[bc][argmax[bc]] += scale[bc] * dy[bc];
+ *   rsis_scale_planes                    : y[bc][:] = scale[bc] * x[bc][:] (HW elements per plane; x == y allowed): the transpose of
+ *                                          the equal-size resize. ---- */
+int rsis_upsample_bilinear_ac_scaled_fwd(const float* x, const float* scale, float* y, long BC, int Hi, int Wi, int Ho, int Wo, void* stream);
+int rsis_upsample_maxpool_scaled_bwd(const float* dy, const float* dpool, const int* argmax, const float* scale, float* dx, long BC, int Hi,
+                                     int Wi, int Ho, int Wo, void* stream);
+int rsis_global_maxpool_scaled_bwd_add(const float* dy, const int* argmax, const float* scale, float* dx, long BC, int HW, void* stream);
+int rsis_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, void* stream);
+
+/* The mask generator: ONE launch fills the three scale arrays of a whole sequence, n floats each,
+ *   array 0 = s2 (Dropout2d, rate p2), array 1 = mc (class head, rate pc), array 2 = ms (stop head, rate ps),
+ * all in the layout of the decoder's pooled side features: level after level, each [T][B][hid_i] (n = T * B * sum hid_i).
+ * state: 8 device words (uint32), owned by the caller:
+ *   state[0] = key word 0: the seed;   state[1] = key word 1: the rank of the process;
+ *   state[2], state[3] = the call counter (low, high word);   state[4] = 0 between calls (the kernel's block ticket);  5..7 unused.
+ * Element e (0 <= e < n) of array a is a pure function of (state, a, e):
+ *   w[0..3] = Philox4x32-10(counter = (e >> 2, a, state[2], state[3]), key = (state[0], state[1]))     (Salmon et al., SC'11)
+ *   word = w[e & 3];   u = (word >> 8) * 2^-24 (exact in fp32);   kept iff u >= p;
+ *   value = kept ? 1.0f / (1.0f - p) (one fp32 division) : 0.0f            -- p == 0: all ones.
+ * The kernel reads the state and then advances the call counter by one itself (an ordinary store by the last block to have read it), so a
+ * captured graph draws fresh masks on every replay with no host involvement.  0 <= p < 1 for every rate, else RSIS_ERR_ARG (nothing
+ * launched, the state untouched). */
+int rsis_dropout_scales(unsigned int* state, float* s2, float* mc, float* ms, long n, float p2, float pc, float ps, void* stream);
+/* The head masks, element-wise over the n pooled features (all arrays in the layout above):
+ *   rsis_dropout_heads_mask     : side <- s2 * side (in place: SIDE = s2 * decode(KEY)), side_c = mc * side, side_s = ms * side -- the
+ *                                 features the class / stop heads (rsis_heads_fwd / rsis_heads_wide_fwd) are then run on;
+ *   rsis_dropout_heads_mask_bwd : dside = mc * dside_c + ms * dside_s (either gradient may be NULL = zero), from the d side of two
+ *                                 rsis_heads_bwd / rsis_heads_wide_bwd calls (dstop == NULL on side_c, dprobs == NULL on side_s). */
+int rsis_dropout_heads_mask(float* side, const float* s2, const float* mc, const float* ms, float* side_c, float* side_s, long n, void* stream);
+int rsis_dropout_heads_mask_bwd(const float* dside_c, const float* dside_s, const float* mc, const float* ms, float* dside, long n, void* stream);
+
 /* ---- nn.BatchNorm2d (+ residual add + ReLU of the bottleneck) (model.py:50-54,59-63; torchvision trunk) ----
  * train bit0: batch statistics, running-stat update (momentum, unbiased var), saves mean / rstd for the backward;
  * train bit1: `stats` (scratch of 2*C doubles) was zeroed by the caller (one memset for a whole arena instead of one per
@@ -673,6 +711,18 @@ typedef struct rsis_blk_resize_job {
 } rsis_blk_resize_job;
 int rsis_blk_upsample_fwd_batch(const rsis_blk_resize_job* jobs, int njobs, void* stream);
 int rsis_blk_upsample_bwd_batch(const rsis_blk_resize_job* jobs, int njobs, void* stream);
+/* The same two with the decoder's Dropout2d scale: channel plane (b, c) of the result (forward: y; backward: dx, after dpool was added) is
+ * multiplied by scale[b][c] ([B][C] fp32; NULL = the unscaled job) in fp32 before the one rounding to bf16. */
+typedef struct rsis_blk_resize_scaled_job {
+  const void* src;
+  void* dst;
+  const float* dpool;
+  const int* arg;
+  int B, C, Hi, Wi, Ho, Wo;
+  const float* scale;
+} rsis_blk_resize_scaled_job;
+int rsis_blk_upsample_fwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream);
+int rsis_blk_upsample_bwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream);
 
 /* rsis_convlstm_bwd_gates on blk tensors: dh, dh2 (may be NULL) blk [B][hid]; act, da blk [B][4 hid] (rows 4 j + gate); c, c_prev,
  * dc_next, dc_prev fp32 [B][hid][HW] (c_prev / dc_next / dc_prev may be NULL). */

@@ -68,6 +68,11 @@ class BlkResizeJob(ctypes.Structure):
                [(k, ctypes.c_int) for k in ("B", "C", "Hi", "Wi", "Ho", "Wo")]
 
 
+class BlkResizeScaledJob(ctypes.Structure):
+    """struct rsis_blk_resize_scaled_job of include/rsis_hip.h"""
+    _fields_ = BlkResizeJob._fields_ + [("scale", ctypes.c_void_p)]
+
+
 class BlkLstmBwdJob(ctypes.Structure):
     """struct rsis_blk_lstm_bwd_job of include/rsis_hip.h"""
     _fields_ = [(k, ctypes.c_void_p) for k in ("dh", "dh2", "dc_next", "act", "c_prev", "c", "da", "dc_prev")] + \
@@ -188,6 +193,15 @@ SIGNATURES = {
     "rsis_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "rsis_sgd_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _vp]),
     "rsis_rmsprop_step": (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp]),
+    "rsis_upsample_bilinear_ac_scaled_fwd": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
+    "rsis_upsample_maxpool_scaled_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
+    "rsis_global_maxpool_scaled_bwd_add": (_i, [_vp, _vp, _vp, _vp, _l, _i, _vp]),
+    "rsis_scale_planes": (_i, [_vp, _vp, _vp, _l, _i, _vp]),
+    "rsis_dropout_scales": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _vp]),
+    "rsis_dropout_heads_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rsis_dropout_heads_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rsis_blk_upsample_fwd_scaled_batch": (_i, [ctypes.POINTER(BlkResizeScaledJob), _i, _vp]),
+    "rsis_blk_upsample_bwd_scaled_batch": (_i, [ctypes.POINTER(BlkResizeScaledJob), _i, _vp]),
 }
 
 _LIB = None

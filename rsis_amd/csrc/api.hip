@@ -581,16 +581,48 @@ int rsis_convlstm_bwd_gates(const float* dh, const float* dh2, const float* dc_n
 
 int rsis_upsample_bilinear_ac_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, void* stream) {
   if (!x || !y) return RSIS_ERR_ARG;
-  return rsis_l_upsample_fwd(x, y, BC, Hi, Wi, Ho, Wo, (hipStream_t)stream);
+  return rsis_l_upsample_fwd(x, y, BC, Hi, Wi, Ho, Wo, nullptr, (hipStream_t)stream);
+}
+// the scaled forms (the decoder's Dropout2d folded in): a null scale is the unscaled call; equal sizes are the (scaled) copy
+int rsis_upsample_bilinear_ac_scaled_fwd(const float* x, const float* scale, float* y, long BC, int Hi, int Wi, int Ho, int Wo, void* stream) {
+  if (!x || !y || BC < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return RSIS_ERR_ARG;
+  if (scale && Hi == Ho && Wi == Wo) return rsis_l_scale_planes(x, scale, y, BC, Hi * Wi, (hipStream_t)stream);
+  return rsis_l_upsample_fwd(x, y, BC, Hi, Wi, Ho, Wo, scale, (hipStream_t)stream);
+}
+int rsis_upsample_maxpool_scaled_bwd(const float* dy, const float* dpool, const int* argmax, const float* scale, float* dx, long BC, int Hi, int Wi,
+                                     int Ho, int Wo, void* stream) {
+  if (!dy || !dx || !dpool || !argmax || BC < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return RSIS_ERR_ARG;
+  return rsis_l_upsample_bwd(dy, dx, BC, Hi, Wi, Ho, Wo, dpool, argmax, scale, (hipStream_t)stream);
+}
+int rsis_global_maxpool_scaled_bwd_add(const float* dy, const int* argmax, const float* scale, float* dx, long BC, int HW, void* stream) {
+  if (!dy || !dx || !argmax || BC < 1 || HW < 1) return RSIS_ERR_ARG;
+  return rsis_l_gmax_bwd_add(dy, argmax, dx, BC, HW, scale, (hipStream_t)stream);
+}
+int rsis_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, void* stream) {
+  if (!x || !scale || !y || BC < 1 || HW < 1) return RSIS_ERR_ARG;
+  return rsis_l_scale_planes(x, scale, y, BC, HW, (hipStream_t)stream);
+}
+int rsis_dropout_scales(unsigned int* state, float* s2, float* mc, float* ms, long n, float p2, float pc, float ps, void* stream) {
+  if (!state || !s2 || !mc || !ms || n < 1 || n > (1L << 33)) return RSIS_ERR_ARG;
+  if (!(p2 >= 0.f && p2 < 1.f) || !(pc >= 0.f && pc < 1.f) || !(ps >= 0.f && ps < 1.f)) return RSIS_ERR_ARG;
+  return rsis_l_dropout_scales(state, s2, mc, ms, n, p2, pc, ps, (hipStream_t)stream);
+}
+int rsis_dropout_heads_mask(float* side, const float* s2, const float* mc, const float* ms, float* side_c, float* side_s, long n, void* stream) {
+  if (!side || !s2 || !mc || !ms || !side_c || !side_s || n < 1) return RSIS_ERR_ARG;
+  return rsis_l_dropout_heads_mask(side, s2, mc, ms, side_c, side_s, n, (hipStream_t)stream);
+}
+int rsis_dropout_heads_mask_bwd(const float* dside_c, const float* dside_s, const float* mc, const float* ms, float* dside, long n, void* stream) {
+  if (!mc || !ms || !dside || n < 1) return RSIS_ERR_ARG;
+  return rsis_l_dropout_heads_mask_bwd(dside_c, dside_s, mc, ms, dside, n, (hipStream_t)stream);
 }
 int rsis_upsample_bilinear_ac_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int Ho, int Wo, void* stream) {
   if (!dy || !dx) return RSIS_ERR_ARG;
-  return rsis_l_upsample_bwd(dy, dx, BC, Hi, Wi, Ho, Wo, nullptr, nullptr, (hipStream_t)stream);
+  return rsis_l_upsample_bwd(dy, dx, BC, Hi, Wi, Ho, Wo, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 int rsis_upsample_maxpool_bwd(const float* dy, const float* dpool, const int* argmax, float* dx, long BC, int Hi, int Wi, int Ho,
                               int Wo, void* stream) {
   if (!dy || !dx || !dpool || !argmax) return RSIS_ERR_ARG;
-  return rsis_l_upsample_bwd(dy, dx, BC, Hi, Wi, Ho, Wo, dpool, argmax, (hipStream_t)stream);
+  return rsis_l_upsample_bwd(dy, dx, BC, Hi, Wi, Ho, Wo, dpool, argmax, nullptr, (hipStream_t)stream);
 }
 int rsis_global_maxpool_fwd(const float* x, float* y, int* argmax, long BC, int HW, void* stream) {
   if (!x || !y || !argmax) return RSIS_ERR_ARG;
@@ -602,7 +634,7 @@ int rsis_global_maxpool_bwd(const float* dy, const int* argmax, float* dx, long 
 }
 int rsis_global_maxpool_bwd_add(const float* dy, const int* argmax, float* dx, long BC, int HW, void* stream) {
   if (!dy || !dx || !argmax) return RSIS_ERR_ARG;
-  return rsis_l_gmax_bwd_add(dy, argmax, dx, BC, HW, (hipStream_t)stream);
+  return rsis_l_gmax_bwd_add(dy, argmax, dx, BC, HW, nullptr, (hipStream_t)stream);
 }
 int rsis_bn_fwd(const float* x, const float* res, float* y, double* stats, const float* gamma, const float* beta,
                 float* running_mean, float* running_var, float* save_mean, float* save_rstd, int B, int C, int HW,
@@ -1031,6 +1063,28 @@ int rsis_blk_upsample_bwd_batch(const rsis_blk_resize_job* jobs, int njobs, void
   BlkResizeJob a[64];
   const int rc = blk_resize_jobs(jobs, njobs, a, true);
   return rc ? rc : rsis_l_blk_upsample_bwd(a, njobs, (hipStream_t)stream);
+}
+// (the checks of blk_resize_jobs, job by job; the scale rides along)
+static int blk_resize_scaled_jobs(const rsis_blk_resize_scaled_job* jobs, int njobs, BlkResizeScaledJob* out, bool bwd) {
+  if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;
+  for (int j = 0; j < njobs; ++j) {
+    const rsis_blk_resize_scaled_job& q = jobs[j];
+    const rsis_blk_resize_job plain = {q.src, q.dst, q.dpool, q.arg, q.B, q.C, q.Hi, q.Wi, q.Ho, q.Wo};
+    const int rc = blk_resize_jobs(&plain, 1, &out[j], bwd);
+    if (rc) return rc;
+    out[j].scale = q.scale;
+  }
+  return RSIS_OK;
+}
+int rsis_blk_upsample_fwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream) {
+  BlkResizeScaledJob a[64];
+  const int rc = blk_resize_scaled_jobs(jobs, njobs, a, false);
+  return rc ? rc : rsis_l_blk_upsample_fwd_scaled(a, njobs, (hipStream_t)stream);
+}
+int rsis_blk_upsample_bwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream) {
+  BlkResizeScaledJob a[64];
+  const int rc = blk_resize_scaled_jobs(jobs, njobs, a, true);
+  return rc ? rc : rsis_l_blk_upsample_bwd_scaled(a, njobs, (hipStream_t)stream);
 }
 int rsis_blk_lstm_bwd_batch(const rsis_blk_lstm_bwd_job* jobs, int njobs, void* stream) {
   if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;

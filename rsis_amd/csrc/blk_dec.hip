@@ -9,6 +9,7 @@
 // so their jobs share a grid (job table by value in the kernel arguments, block ranges per job).
 #include "blk_cell.h"
 #include "launchers.h"
+#include <type_traits>
 
 #define RSIS_KD_MAXJ 8
 template <typename J>
@@ -30,11 +31,24 @@ __device__ __forceinline__ int kd_find(const G& g, long e, long& local) {
 // ------------------------------------------------------------------------------------------------
 // upsample forward: one thread = one output cell, 4 input cells (same arithmetic per element as upsample_fwd_kernel)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGroup<BlkResizeJob> g) {
+// J = BlkResizeScaledJob: every channel of the cell is multiplied by its plane's scale before the store (J = BlkResizeJob: the kernel
+// without it)
+template <typename J>
+__device__ __forceinline__ void blk_scale_cell(const J& p, long pl, float v[8]) {
+  if constexpr (std::is_same<J, BlkResizeScaledJob>::value) {
+    if (p.scale) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] *= p.scale[pl * 8 + k];
+    }
+  }
+}
+
+template <typename J>
+__global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGroup<J> g) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= g.begin[g.n]) return;
   long loc;
-  const BlkResizeJob& p = g.job[kd_find(g, e, loc)];
+  const J& p = g.job[kd_find(g, e, loc)];
   const int Hi = p.Hi, Wi = p.Wi, Ho = p.Ho, Wo = p.Wo;
   const int wo = (int)(loc % Wo);
   const long t = loc / Wo;
@@ -49,7 +63,14 @@ __global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGro
   blk_cell_unpack(xb[h0 * Wi + w0], v00); blk_cell_unpack(xb[h0 * Wi + w1], v01);
   blk_cell_unpack(xb[h1 * Wi + w0], v10); blk_cell_unpack(xb[h1 * Wi + w1], v11);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) o[k] = (1.f - lh) * ((1.f - lw) * v00[k] + lw * v01[k]) + lh * ((1.f - lw) * v10[k] + lw * v11[k]);
+  for (int k = 0; k < 8; ++k) {
+    // (1 - lh) ((1 - lw) v00 + lw v01) + lh ((1 - lw) v10 + lw v11) with its fused multiply-adds written out -- the ones the compiler
+    // chose for the plain expression in the unscaled kernel; left to it, the scaled kernel fused other products (1 element in 10^5 then
+    // rounded to the neighbouring bf16, and was no longer scale x the unscaled result)
+    const float top = __builtin_fmaf(1.f - lw, v00[k], lw * v01[k]), bot = __builtin_fmaf(1.f - lw, v10[k], lw * v11[k]);
+    o[k] = __builtin_fmaf(1.f - lh, top, lh * bot);
+  }
+  blk_scale_cell(p, pl, o);
   ((u32x4*)p.dst)[loc] = blk_cell_pack(o);
 }
 
@@ -57,11 +78,12 @@ __global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGro
 // upsample backward (gather form, as upsample_bwd_generic_kernel: the candidate outputs of an input pixel are scanned with the SAME
 // ac_coord the forward uses, so forward and backward agree on which outputs touch which input) + the pooled gradient at the arg-max
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGroup<BlkResizeJob> g) {
+template <typename J>
+__global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGroup<J> g) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= g.begin[g.n]) return;
   long loc;
-  const BlkResizeJob& p = g.job[kd_find(g, e, loc)];
+  const J& p = g.job[kd_find(g, e, loc)];
   const int Hi = p.Hi, Wi = p.Wi, Ho = p.Ho, Wo = p.Wo;
   const int wi = (int)(loc % Wi);
   const long t = loc / Wi;
@@ -132,6 +154,7 @@ __global__ __launch_bounds__(256) void blk_upsample_bwd_group_kernel(const KdGro
     for (int k = 0; k < 8; ++k)
       if (p.arg[pl * 8 + k] == sp) acc[k] += p.dpool[pl * 8 + k];
   }
+  blk_scale_cell(p, pl, acc);
   ((u32x4*)p.dst)[loc] = blk_cell_pack(acc);
 }
 
@@ -206,13 +229,37 @@ int rsis_l_blk_upsample_fwd(const BlkResizeJob* jobs, int n, hipStream_t st) {
   long cells[64];
   if (n > 64) return RSIS_ERR_ARG;
   for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Ho * jobs[j].Wo;
-  return kd_launch(blk_upsample_fwd_group_kernel, jobs, cells, n, st);
+  return kd_launch(blk_upsample_fwd_group_kernel<BlkResizeJob>, jobs, cells, n, st);
+}
+// (no job with a scale: the unscaled launch itself, so that a NULL scale gives its bits whatever the compiler makes of the two kernels)
+static bool kd_unscaled(const BlkResizeScaledJob* jobs, int n, BlkResizeJob* plain) {
+  for (int j = 0; j < n; ++j) {
+    if (jobs[j].scale) return false;
+    plain[j] = jobs[j];
+  }
+  return true;
+}
+int rsis_l_blk_upsample_fwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st) {
+  long cells[64];
+  BlkResizeJob plain[64];
+  if (n > 64) return RSIS_ERR_ARG;
+  if (kd_unscaled(jobs, n, plain)) return rsis_l_blk_upsample_fwd(plain, n, st);
+  for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Ho * jobs[j].Wo;
+  return kd_launch(blk_upsample_fwd_group_kernel<BlkResizeScaledJob>, jobs, cells, n, st);
 }
 int rsis_l_blk_upsample_bwd(const BlkResizeJob* jobs, int n, hipStream_t st) {
   long cells[64];
   if (n > 64) return RSIS_ERR_ARG;
   for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Hi * jobs[j].Wi;
-  return kd_launch(blk_upsample_bwd_group_kernel, jobs, cells, n, st);
+  return kd_launch(blk_upsample_bwd_group_kernel<BlkResizeJob>, jobs, cells, n, st);
+}
+int rsis_l_blk_upsample_bwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st) {
+  long cells[64];
+  BlkResizeJob plain[64];
+  if (n > 64) return RSIS_ERR_ARG;
+  if (kd_unscaled(jobs, n, plain)) return rsis_l_blk_upsample_bwd(plain, n, st);
+  for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Hi * jobs[j].Wi;
+  return kd_launch(blk_upsample_bwd_group_kernel<BlkResizeScaledJob>, jobs, cells, n, st);
 }
 int rsis_l_blk_lstm_bwd(const BlkLstmBwdJob* jobs, int n, hipStream_t st) {
   long cells[64];

@@ -257,6 +257,11 @@ struct BlkResizeJob {
   const int* arg;
   int planes, Hi, Wi, Ho, Wo;
 };
+// ... with the result of channel plane (b, c) multiplied by scale[b][c] ([B][C] fp32, null = 1): the decoder's Dropout2d scale,
+// applied in fp32 before the one rounding of the store
+struct BlkResizeScaledJob : BlkResizeJob {
+  const float* scale;
+};
 // ConvLSTM pointwise backward on blk tensors: dh / dh2 [B][hid/8][HW][8] (dh2 may be null), act / da [B][4 hid / 8][HW][8] (rows
 // 4 j + gate), c / c_prev / dc_next / dc_prev fp32 [B][hid][HW] (c_prev, dc_next, dc_prev may be null)
 struct BlkLstmBwdJob {

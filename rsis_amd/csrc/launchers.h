@@ -45,15 +45,18 @@ int rsis_l_pack(PackMode mode, const float* W, void* out, int Cout, int Ctot, in
 int rsis_l_lstm_bwd(const float* dh, const float* dh2, const float* dc_next, const float* act, const float* c_prev, const float* c, float* da, float* dc_prev,
                     float* da_sum, int B, int hid, int HW, hipStream_t st);
 int rsis_l_lstm_bwd_group(const void* const* ptrs, const int* dims, int n, hipStream_t st);
-int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, hipStream_t st);
-int rsis_l_upsample_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int Ho, int Wo, const float* pool_g, const int* pool_arg, hipStream_t st);
+// (scale: [BC] factors of the planes of the result, null = none -- the kernels without the argument)
+int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st);
+int rsis_l_upsample_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int Ho, int Wo, const float* pool_g, const int* pool_arg, const float* scale,
+                        hipStream_t st);
+int rsis_l_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, hipStream_t st);
 int rsis_l_gmax_fwd(const float* x, float* y, int* arg, long BC, int HW, hipStream_t st);
 int rsis_l_gmax_bwd(const float* dy, const int* arg, float* dx, long BC, int HW, hipStream_t st);
 int rsis_l_bn_fwd(const float* x, const float* res, float* y, unsigned char* mask, double* stats, const float* gamma, const float* beta, float* run_mean,
                   float* run_var, float* save_mean, float* save_rstd, int B, int C, int HW, float eps, float momentum, int relu, int train_flags, hipStream_t st);
 int rsis_l_bn_bwd(const float* dy, const float* x, const float* y, const unsigned char* mask, const float* mean, const float* rstd, const float* gamma,
                   double* stats, float* dx, float* dres, float* dgamma, float* dbeta, int B, int C, int HW, int relu_flags, float eval_eps, hipStream_t st);
-int rsis_l_gmax_bwd_add(const float* dy, const int* arg, float* dx, long BC, int HW, hipStream_t st);
+int rsis_l_gmax_bwd_add(const float* dy, const int* arg, float* dx, long BC, int HW, const float* scale, hipStream_t st);
 int rsis_l_subsample(const float* x, float* y, long BC, int H, int W, int Ho, int Wo, int s, hipStream_t st);
 int rsis_l_maxpool_fwd(const float* x, float* y, unsigned char* arg, long BC, int H, int W, int Ho, int Wo, hipStream_t st);
 int rsis_l_maxpool_bwd(const float* dy, const unsigned char* arg, float* dx, long BC, int H, int W, int Ho, int Wo, int accumulate, hipStream_t st);
@@ -73,12 +76,18 @@ int rsis_l_blk_subsample(const void* x, void* y, long BCb, int H, int W, int Ho,
 int rsis_l_blk_upscatter(const void* dy, void* dx, long BCb, int H, int W, int Ho, int Wo, int stride, hipStream_t st);
 int rsis_l_blk_upsample_fwd(const BlkResizeJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_upsample_bwd(const BlkResizeJob* jobs, int n, hipStream_t st);
+int rsis_l_blk_upsample_fwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st);
+int rsis_l_blk_upsample_bwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_lstm_bwd(const BlkLstmBwdJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_sum_leading(const void* x, void* y, int T, long n, hipStream_t st);
 int rsis_l_blk_channel_sum(const void* dy, float* db, int B, int C, int HW, int hid, hipStream_t st);
 int rsis_l_blk_c1_fwd(const void* x, const float* w, const float* bias, float* y, int T, int B, int H, int W, hipStream_t st);
 int rsis_l_blk_c1_dgrad(const float* dy, const float* w, void* dx, int T, int B, int H, int W, hipStream_t st);
 int rsis_l_blk_c1_wgrad(const float* dy, const void* x, float* dw, float* db, int T, int B, int H, int W, hipStream_t st);
+// dropout.hip: the decoder's dropout scales (include/rsis_hip.h: rsis_dropout_scales) and the head masks
+int rsis_l_dropout_scales(unsigned* state, float* s2, float* mc, float* ms, long n, float p2, float pc, float ps, hipStream_t st);
+int rsis_l_dropout_heads_mask(float* side, const float* s2, const float* mc, const float* ms, float* side_c, float* side_s, long n, hipStream_t st);
+int rsis_l_dropout_heads_mask_bwd(const float* dc, const float* ds, const float* mc, const float* ms, float* dside, long n, hipStream_t st);
 // losses.hip (the default arguments of rsis_l_heads_fwd stand here, on the declaration, only)
 int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, hipStream_t st);
 int rsis_l_softiou_bwd(const float* logits, const float* y, const long long* perm, int perm_ld, const float* ca, const float* cb, float* dlogits, int B, int T,

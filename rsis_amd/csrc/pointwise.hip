@@ -5,6 +5,7 @@
 #include "common.h"
 #include "launchers.h"
 #include <cstdlib>
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // ConvLSTM pointwise backward (derivative of reference clstm.py:47-58; formulas in SURVEY.md 8(a))
@@ -121,8 +122,11 @@ __global__ __launch_bounds__(256) void lstm_bwd_group_v4_kernel(const LstmBwdGro
 // ------------------------------------------------------------------------------------------------
 // (ac_coord / ac_scale: common.h)
 
+// SC (every upsample / pool-backward kernel below): the result of plane bc is multiplied by scale[bc] (the decoder's Dropout2d scale,
+// model.py:141: interpolate in fp32, then scale); SC = false is the kernel without the argument.
+template <bool SC>
 __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi, int Ho, int Wo,
-                                    float sh, float sw, long total) {
+                                    float sh, float sw, long total, const float* __restrict__ scale) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int wo = (int)(e % Wo);
     const long t = e / Wo;
@@ -133,15 +137,18 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restri
     ac_coord(wo, sw, Wi, w0, w1, lw);
     const float* xb = x + bc * Hi * Wi;
     const float v00 = xb[h0 * Wi + w0], v01 = xb[h0 * Wi + w1], v10 = xb[h1 * Wi + w0], v11 = xb[h1 * Wi + w1];
-    y[e] = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
+    const float o = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
+    y[e] = SC ? o * scale[bc] : o;
   }
 }
 
 // Wo % 4 == 0: one thread = 4 consecutive outputs of a row (float4 store).  A block covers 256 / (Wo/4) consecutive output
 // rows of the flattened (bc, ho) row space (or a 256-thread slice of one long row); the only division left is one per thread
 // (row -> bc, ho).  Same arithmetic per element as upsample_fwd_kernel (bit-identical results).
+template <bool SC>
 __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi,
-                                                              int Ho, int Wo, float sh, float sw, long rows, int Wq, int wq_shift) {
+                                                              int Ho, int Wo, float sh, float sw, long rows, int Wq, int wq_shift,
+                                                              const float* __restrict__ scale) {
   // wq_shift >= 0: Wq is a power of two <= 256 and a block spans 256 >> wq_shift rows; -2: any Wq <= 256, the (row, float4)
   // space is walked flat (one division per thread: the 7 / 14 / 28-float4 rows of the 224 x 224 pyramid had one 256-thread block
   // per ROW before, 3-11 % of the lanes active: 22 us per launch instead of 6); otherwise blockIdx.y walks the row
@@ -172,6 +179,11 @@ __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __res
     ac_coord(wq * 4 + k, sw, Wi, w0, w1, lw);
     o[k] = (1.f - lh) * ((1.f - lw) * r0[w0] + lw * r0[w1]) + lh * ((1.f - lw) * r1[w0] + lw * r1[w1]);
   }
+  if (SC) {
+    const float s = scale[bc];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] *= s;
+  }
   *reinterpret_cast<f32x4*>(y + ((size_t)row * Wq + wq) * 4) = o;
 }
 
@@ -180,9 +192,10 @@ __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __res
 // writes two float4s.  The v4 kernel issues 16 scalar loads per float4 of output and is bound by the vector-memory pipe
 // (34 us for the 8 x 256^2 x 32 level, a 67 MB write); this one is bound by the write.  Same arithmetic, bit-identical results.
 // Tile shapes: 16 x 128 outputs (512-byte output rows; <= 12 x 69 inputs) on maps at least 128 wide, 32 x 64 (<= 20 x 45) below.
-template <int UF_TOH, int UF_TOW, int UF_RH, int UF_RQ>
+template <int UF_TOH, int UF_TOW, int UF_RH, int UF_RQ, bool SC = false>
 __global__ __launch_bounds__(256) void upsample_fwd_lds_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi,
-                                                               int Ho, int Wo, float sh, float sw, int tiles_x, int tiles_y) {
+                                                               int Ho, int Wo, float sh, float sw, int tiles_x, int tiles_y,
+                                                               const float* __restrict__ scale) {
   __shared__ __attribute__((aligned(16))) float src[UF_RH][UF_RQ * 4];
   const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
   const long bc = blockIdx.x / (tiles_x * tiles_y);
@@ -220,6 +233,11 @@ __global__ __launch_bounds__(256) void upsample_fwd_lds_kernel(const float* __re
       w1 -= wa;
       o[k] = (1.f - lh) * ((1.f - lw) * r0[w0] + lw * r0[w1]) + lh * ((1.f - lw) * r1[w0] + lw * r1[w1]);
     }
+    if (SC) {
+      const float s = scale[bc];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] *= s;
+    }
     *reinterpret_cast<f32x4*>(y + (bc * Ho + ho) * (size_t)Wo + wo) = o;
   }
 }
@@ -230,11 +248,11 @@ __global__ __launch_bounds__(256) void upsample_fwd_lds_kernel(const float* __re
 // ac_coord, so membership is bit-consistent with it); the block then stages the dy region the tile needs in LDS with
 // row-coalesced loads and reduces it separably: rows first (tmp[hi][wo]), then columns.
 #define UK 6   // consecutive candidate outputs per input index: covers scale factors >= ~0.46 (checked by the launcher)
-template <int UT, int RM>
+template <int UT, int RM, bool SC = false>
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int Hi, int Wi,
                                                            int Ho, int Wo, float sh, float sw, int tiles_x, int tiles_y, long BC,
                                                            int planes_per_block, int vec, const float* __restrict__ pool_g,
-                                                           const int* __restrict__ pool_arg) {
+                                                           const int* __restrict__ pool_arg, const float* __restrict__ scale) {
   constexpr int RQ = RM / 4 + 1, RP = RQ * 4;      // staged row: RQ aligned float4s = RM + 4 columns (the region starts 0..3 columns in)
   __shared__ float wgt[2][UT][UK];
   __shared__ int st[2][UT];          // first candidate of each input index (absolute output index)
@@ -333,7 +351,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 #pragma unroll
       for (int k = 0; k < UK; ++k) acc = fmaf(wgt[1][lx][k], tmp[ly * RP + min(max(c0 + k, 0), ex - 1)], acc);
       if (pool_g && hi * Wi + wi == pool_arg[bc]) acc += pool_g[bc];     // + the global max-pool's gradient at its arg-max pixel
-      dx[bc * Hi * Wi + (size_t)hi * Wi + wi] = acc;
+      dx[bc * Hi * Wi + (size_t)hi * Wi + wi] = SC ? acc * scale[bc] : acc;
     }
     // (the next plane's `reg` fill is ordered after this plane's last `reg` read by the barrier above; `tmp` is rewritten only
     //  after the next barrier)
@@ -341,9 +359,10 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 }
 
 // general fallback (any scale): per-thread candidate scan
+template <bool SC>
 __global__ void upsample_bwd_generic_kernel(const float* __restrict__ dy, float* __restrict__ dx, int Hi, int Wi, int Ho, int Wo,
                                             float sh, float sw, long total, const float* __restrict__ pool_g,
-                                            const int* __restrict__ pool_arg) {
+                                            const int* __restrict__ pool_arg, const float* __restrict__ scale) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int wi = (int)(e % Wi);
     const long t = e / Wi;
@@ -369,7 +388,7 @@ __global__ void upsample_bwd_generic_kernel(const float* __restrict__ dy, float*
       acc += wh * row;
     }
     if (pool_g && hi * Wi + wi == pool_arg[bc]) acc += pool_g[bc];
-    dx[e] = acc;
+    dx[e] = SC ? acc * scale[bc] : acc;
   }
 }
 
@@ -432,10 +451,17 @@ __global__ void global_maxpool_bwd_kernel(const float* __restrict__ dy, const in
 }
 
 // dx[bc][argmax[bc]] += dy[bc]: the max-pool gradient added into a gradient that already holds another path's contribution
+template <bool SC>
 __global__ void global_maxpool_bwd_add_kernel(const float* __restrict__ dy, const int* __restrict__ arg, float* __restrict__ dx,
-                                              int HW, long BC) {
+                                              int HW, long BC, const float* __restrict__ scale) {
   const long bc = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (bc < BC) dx[bc * HW + arg[bc]] += dy[bc];
+  if (bc < BC) dx[bc * HW + arg[bc]] += SC ? scale[bc] * dy[bc] : dy[bc];
+}
+
+// y[bc][:] = scale[bc] * x[bc][:]: the scaled form of the copy an align-corners resize to the SAME size is (either direction)
+__global__ __launch_bounds__(256) void scale_planes_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ y,
+                                                           int HW, long total) {
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) y[e] = scale[e / HW] * x[e];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1211,7 +1237,12 @@ int rsis_l_lstm_bwd_group(const void* const* ptrs, const int* dims, int n, hipSt
   }
   return RSIS_OK;
 }
-int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, hipStream_t st) {
+// f(std::true_type) with a scale, f(std::false_type) without: picks the SC instantiation of a kernel
+template <typename F>
+static inline void sc_pick(const float* scale, F f) {
+  if (scale) f(std::true_type{}); else f(std::false_type{});
+}
+int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st) {
   const long total = BC * Ho * Wo;
   {
     // the LDS-tiled kernel needs its output tile to read at most RH x (RQ * 4 - 3) input pixels
@@ -1219,14 +1250,22 @@ int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int H
     const bool al = Wo % 4 == 0 && Wi % 4 == 0;
     if (al && Ho >= 16 && Wo >= 128 && fh * 15 + 3.f <= 12 && fw * 127 + 6.f <= 72 && BC * ((Wo + 127) / 128) * ((Ho + 15) / 16) < (1L << 31)) {
       const int tiles_x = (Wo + 127) / 128, tiles_y = (Ho + 15) / 16;
-      hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
-                         Wi, Ho, Wo, fh, fw, tiles_x, tiles_y);
+      if (!scale)
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
+                           Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
+      else
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18, true>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+                           Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       return rsis_check_launch();
     }
     if (al && Ho >= 32 && Wo >= 64 && fh * 31 + 3.f <= 20 && fw * 63 + 6.f <= 48 && BC * ((Wo + 63) / 64) * ((Ho + 31) / 32) < (1L << 31)) {
       const int tiles_x = (Wo + 63) / 64, tiles_y = (Ho + 31) / 32;
-      hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
-                         Wi, Ho, Wo, fh, fw, tiles_x, tiles_y);
+      if (!scale)
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
+                           Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
+      else
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12, true>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+                           Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       return rsis_check_launch();
     }
   }
@@ -1238,16 +1277,20 @@ int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int H
     if (shift < 0 && Wq <= 256) shift = -2;
     const dim3 grid = shift >= 0 ? dim3((unsigned)((rows + (256 >> shift) - 1) / (256 >> shift)))
                                  : (shift == -2 ? dim3((unsigned)((rows * Wq + 255) / 256)) : dim3((unsigned)rows, (Wq + 255) / 256));
-    hipLaunchKernelGGL(upsample_fwd_v4_kernel, grid, dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo, ac_scale(Hi, Ho), ac_scale(Wi, Wo), rows,
-                       Wq, shift);
+    sc_pick(scale, [&](auto sc) {
+      hipLaunchKernelGGL((upsample_fwd_v4_kernel<decltype(sc)::value>), grid, dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo, ac_scale(Hi, Ho),
+                         ac_scale(Wi, Wo), rows, Wq, shift, scale);
+    });
   } else {
-    hipLaunchKernelGGL(upsample_fwd_kernel, dim3(ew_grid(total)), dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo, ac_scale(Hi, Ho),
-                       ac_scale(Wi, Wo), total);
+    sc_pick(scale, [&](auto sc) {
+      hipLaunchKernelGGL((upsample_fwd_kernel<decltype(sc)::value>), dim3(ew_grid(total)), dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo,
+                         ac_scale(Hi, Ho), ac_scale(Wi, Wo), total, scale);
+    });
   }
   return rsis_check_launch();
 }
 int rsis_l_upsample_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int Ho, int Wo, const float* pool_g, const int* pool_arg,
-                        hipStream_t st) {
+                        const float* scale, hipStream_t st) {
   const float sh = ac_scale(Hi, Ho), sw = ac_scale(Wi, Wo);
   // the tiled kernel keeps UK = 6 consecutive candidate outputs per input index (< 2/scale + 1 touch it) and a dy region of
   // at most (UT + 1)/scale + UK outputs per axis in LDS
@@ -1263,16 +1306,24 @@ int rsis_l_upsample_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int
     if (ppb > 16) ppb = 16;
     const long blocks = (BC + ppb - 1) / ppb * tiles_x * tiles_y;
     const int vec = Wo % 4 == 0;
-    if (ut == 32)
+    if (ut == 32 && !scale)
       hipLaunchKernelGGL((upsample_bwd_kernel<32, 80>), dim3((unsigned)blocks), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw, tiles_x,
-                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg);
-    else
+                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg, scale);
+    else if (ut == 32)
+      hipLaunchKernelGGL((upsample_bwd_kernel<32, 80, true>), dim3((unsigned)blocks), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw, tiles_x,
+                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg, scale);
+    else if (!scale)
       hipLaunchKernelGGL((upsample_bwd_kernel<16, 44>), dim3((unsigned)blocks), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw, tiles_x,
-                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg);
+                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg, scale);
+    else
+      hipLaunchKernelGGL((upsample_bwd_kernel<16, 44, true>), dim3((unsigned)blocks), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw, tiles_x,
+                         tiles_y, BC, (int)ppb, vec, pool_g, pool_arg, scale);
   } else {
     const long total = BC * Hi * Wi;
-    hipLaunchKernelGGL(upsample_bwd_generic_kernel, dim3(ew_grid(total)), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw, total, pool_g,
-                       pool_arg);
+    sc_pick(scale, [&](auto sc) {
+      hipLaunchKernelGGL((upsample_bwd_generic_kernel<decltype(sc)::value>), dim3(ew_grid(total)), dim3(256), 0, st, dy, dx, Hi, Wi, Ho, Wo, sh, sw,
+                         total, pool_g, pool_arg, scale);
+    });
   }
   return rsis_check_launch();
 }
@@ -1357,8 +1408,16 @@ int rsis_l_bn_bwd(const float* dy, const float* x, const float* y, const unsigne
   }
   return rsis_check_launch();
 }
-int rsis_l_gmax_bwd_add(const float* dy, const int* arg, float* dx, long BC, int HW, hipStream_t st) {
-  hipLaunchKernelGGL(global_maxpool_bwd_add_kernel, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, st, dy, arg, dx, HW, BC);
+int rsis_l_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, hipStream_t st) {
+  const long total = BC * HW;
+  hipLaunchKernelGGL(scale_planes_kernel, dim3(ew_grid(total)), dim3(256), 0, st, x, scale, y, HW, total);
+  return rsis_check_launch();
+}
+int rsis_l_gmax_bwd_add(const float* dy, const int* arg, float* dx, long BC, int HW, const float* scale, hipStream_t st) {
+  sc_pick(scale, [&](auto sc) {
+    hipLaunchKernelGGL((global_maxpool_bwd_add_kernel<decltype(sc)::value>), dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, st, dy, arg, dx, HW, BC,
+                       scale);
+  });
   return rsis_check_launch();
 }
 int rsis_l_subsample(const float* x, float* y, long BC, int H, int W, int Ho, int Wo, int s, hipStream_t st) {

@@ -30,12 +30,14 @@ import os
 
 import torch
 
-from . import _lib, decoder_fused, ops
+from . import _lib, decoder_fused, dropout, ops
 from ._lib import check, int_array, lib, ptr, ptr_array, stream
 
 ENABLED = [os.environ.get("RSIS_DECODER_SEQ", "1") != "0"]
 # test hook: RECORD[0] = True keeps a copy of the arg-max pixels of the side max-pools of the last sequence in LAST["arg"] (per level,
-# [T][B][hid] int32) -- what the per-step path's callers can read off the returned hidden states
+# [T][B][hid] int32) -- what the per-step path's callers can read off the returned hidden states -- and, when any dropout rate is above 0,
+# clones of the scales the sequence drew in LAST["drop"] = {"s2": per level [T][B][hid] (None at -dropout 0), "mc", "ms": per level
+# [T][B][hid]: the head masks of row (t, b) are the concatenation over the levels}
 RECORD, LAST = [False], {}
 
 
@@ -49,10 +51,12 @@ def _chan(t):
 
 
 def supported(decoder, skip_feats, T):
-    """the explicit sequence covers the product configuration: concat skips, 3x3 gates, no dropout, the fused heads kernel"""
+    """the explicit sequence covers the product configuration: concat skips, 3x3 gates, any dropout rates in [0, 1), the fused heads kernel"""
     n = len(decoder.clstm_list)
-    if not (ENABLED[0] and decoder_fused.WAVEFRONT[0] and decoder_fused.FUSED_POOL[0] and decoder.fused and decoder.skip_mode == "concat" and decoder.dropout == 0 and decoder.dropout_cls == 0 and
-            decoder.dropout_stop == 0 and len(skip_feats) == n and T >= 1 and "forward" not in decoder.__dict__):
+    if not (ENABLED[0] and decoder_fused.WAVEFRONT[0] and decoder_fused.FUSED_POOL[0] and decoder.fused and decoder.skip_mode == "concat" and
+            len(skip_feats) == n and T >= 1 and "forward" not in decoder.__dict__):
+        return False
+    if not all(0 <= p < 1 for p in dropout.rates(decoder)):
         return False
     if not all(f.is_cuda and ((f.dtype == torch.float32 and f.dim() == 4) or _is_blk(f)) for f in skip_feats):
         return False
@@ -141,6 +145,49 @@ def _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, probs_tb, dp_tb, ds_tb,
         check(call(T * B, slice(None), True), "rsis_heads_wide_bwd(all steps)")
 
 
+class _Side(object):
+    """stands in for a level where only its pooled features are read (_heads_bwd_all_steps on the masked copies)"""
+    __slots__ = ("SIDE",)
+
+    def __init__(self, side):
+        self.SIDE = side
+
+
+class _Drop(object):
+    """the dropout scales of one sequence (rsis_amd.dropout: one generator launch) and the masked head features.  S2 / MC / MS and SIDEC /
+    SIDES are flat [T * B * sum(hid)] buffers in the layout of SIDE; s2 = the per-level views of S2, None at -dropout 0 (then no launch
+    of the recurrence differs from the ones made without dropout: only the heads see masks)"""
+    __slots__ = ("S2", "MC", "MS", "s2", "SIDEC", "SIDES")
+
+
+def _heads_fwd_masked(L, SIDE, drop, hs, T, B, Wc, bc, Ws, bs, probs_tb, stop_tb):
+    """the heads under dropout, on the decoded features SIDE (flat, all levels): SIDE <- s2 * SIDE, then the class head on mc * SIDE and
+    the stop head on ms * SIDE (model.py:169-179) -- the existing heads launch once per masked copy (a few us each; the half of each
+    launch that the other one owns goes to scratch), composed with one masking kernel"""
+    check(L.rsis_dropout_heads_mask(ptr(SIDE), ptr(drop.S2), ptr(drop.MC), ptr(drop.MS), ptr(drop.SIDEC), ptr(drop.SIDES), SIDE.numel(), stream()),
+          "rsis_dropout_heads_mask")
+    ops.heads_fwd_launch(L, _per_level(drop.SIDEC, hs, T, B), hs, T * B, Wc, bc, Ws, bs, probs_tb, torch.empty_like(stop_tb))
+    ops.heads_fwd_launch(L, _per_level(drop.SIDES, hs, T, B), hs, T * B, Wc, bc, Ws, bs, torch.empty_like(probs_tb), stop_tb)
+
+
+def _heads_bwd_masked(L, drop, hs, T, B, Wc, Ws, probs_tb, dp_tb, ds_tb, DSIDE, hb):
+    """backward of _heads_fwd_masked into DSIDE (flat) = d(s2 * decode(KEY)): one heads backward per masked copy (dstop == NULL on the
+    class copy, dprobs == NULL on the stop copy), so dWc / dWs are taken against the masked features; then dside = mc * d(class copy) +
+    ms * d(stop copy).  hb: the targets of dWc, dbc, dWs, dbs (None: not wanted)"""
+    n = len(hs)
+    dsc = dss = None
+    if dp_tb is not None:
+        dsc = torch.empty_like(DSIDE)
+        _heads_bwd_all_steps(L, [_Side(v) for v in _per_level(drop.SIDEC, hs, T, B)], hs, n, T, B, Wc, Ws, probs_tb, dp_tb, None,
+                             _per_level(dsc, hs, T, B), [hb[0], hb[1], None, None])
+    if ds_tb is not None:
+        dss = torch.empty_like(DSIDE)
+        _heads_bwd_all_steps(L, [_Side(v) for v in _per_level(drop.SIDES, hs, T, B)], hs, n, T, B, Wc, Ws, probs_tb, None, ds_tb,
+                             _per_level(dss, hs, T, B), [None, None, hb[2], hb[3]])
+    check(L.rsis_dropout_heads_mask_bwd(ptr(dsc), ptr(dss), ptr(drop.MC), ptr(drop.MS), ptr(DSIDE), DSIDE.numel(), stream()),
+          "rsis_dropout_heads_mask_bwd")
+
+
 def _per_level(buf, hs, T, B):
     """views [T][B][hid] of one flat buffer, level after level"""
     return [v.view(T, B, h) for v, h in zip(buf.split([T * B * h for h in hs]), hs)]
@@ -202,23 +249,31 @@ class _Nchw(_Layout):
                             ops.FORCE_TILE[0], lv.dyn.dtype, lv.KEY[t].data_ptr())
         check(self.L.rsis_convlstm_fwd_batch(jobs, len(cells), stream()), "rsis_convlstm_fwd_batch")
 
-    def up(self, levels, cells):
+    def up(self, levels, cells, s2=None):
+        """UP[i + 1][t] = up(h[i][t]); s2 (per level [T][B][hid], the Dropout2d scales): s2 * up(h), model.py:141,149-150"""
         for i, t in cells:
             if i + 1 < len(levels):
                 lv, nx = levels[i], levels[i + 1]
-                if (nx.H, nx.W) == (lv.H, lv.W):          # align-corners resize to the same size is the identity (ops.upsample_bilinear_ac)
+                if s2 is not None:                        # (equal sizes: the scaled copy)
+                    check(self.L.rsis_upsample_bilinear_ac_scaled_fwd(ptr(lv.Hs[t]), ptr(s2[i][t]), ptr(nx.UP[t]), self.B * lv.hid, lv.H, lv.W, nx.H,
+                                                                      nx.W, stream()), "rsis_upsample_scaled_fwd")
+                elif (nx.H, nx.W) == (lv.H, lv.W):        # align-corners resize to the same size is the identity (ops.upsample_bilinear_ac)
                     nx.UP[t].copy_(lv.Hs[t])
                 else:
                     check(self.L.rsis_upsample_bilinear_ac_fwd(ptr(lv.Hs[t]), ptr(nx.UP[t]), self.B * lv.hid, lv.H, lv.W, nx.H, nx.W, stream()),
                           "rsis_upsample_fwd")
 
-    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads):
-        """the x2 upsample of the last level over all steps, heads() (the launch of the class / stop heads, which each layout issues
-        where it always has), then conv_out: stacked over T where rsis_conv_out_seq_* covers the shape (3 launches instead of 3 T),
-        per step otherwise"""
+    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads, sc=None):
+        """the x2 upsample of the last level over all steps (times its Dropout2d scales sc [T][B][hid], if any), heads() (the launch of
+        the class / stop heads, which each layout issues where it always has), then conv_out: stacked over T where rsis_conv_out_seq_*
+        covers the shape (3 launches instead of 3 T), per step otherwise"""
         L, T, B = self.L, self.T, self.B
         H5, W5 = 2 * last.H, 2 * last.W
-        check(L.rsis_upsample_bilinear_ac_fwd(ptr(last.Hs), ptr(UP5), T * B * last.hid, last.H, last.W, H5, W5, stream()), "rsis_upsample_fwd(all steps)")
+        if sc is not None:
+            check(L.rsis_upsample_bilinear_ac_scaled_fwd(ptr(last.Hs), ptr(sc), ptr(UP5), T * B * last.hid, last.H, last.W, H5, W5, stream()),
+                  "rsis_upsample_scaled_fwd(all steps)")
+        else:
+            check(L.rsis_upsample_bilinear_ac_fwd(ptr(last.Hs), ptr(UP5), T * B * last.hid, last.H, last.W, H5, W5, stream()), "rsis_upsample_fwd(all steps)")
         heads()
         co_pack = conv_out._pack
         co_wp = co_pack.fwd(co_w)
@@ -258,16 +313,28 @@ class _Nchw(_Layout):
             if db is not None:
                 check(L.rsis_bias_grad(ptr(dy), ptr(db), B, 1, H5 * W5, 0, stream()), "rsis_bias_grad(conv_out)")
 
-    def up5_bwd(self, dUP5, dside, last, DH_last):
+    def up5_bwd(self, dUP5, dside, last, DH_last, sc=None):
+        if sc is not None:
+            check(self.L.rsis_upsample_maxpool_scaled_bwd(ptr(dUP5), ptr(dside), ptr(last.ARG), ptr(sc), ptr(DH_last), self.T * self.B * last.hid,
+                                                          last.H, last.W, 2 * last.H, 2 * last.W, stream()), "rsis_upsample_maxpool_scaled_bwd(all steps)")
+            return
         check(self.L.rsis_upsample_maxpool_bwd(ptr(dUP5), ptr(dside), ptr(last.ARG), ptr(DH_last), self.T * self.B * last.hid, last.H, last.W,
                                                2 * last.H, 2 * last.W, stream()), "rsis_upsample_maxpool_bwd(all steps)")
 
-    def up_bwd(self, levels, cells, DUP, DH, dsides):
+    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None):
+        """dh[i][t] = up^T(dUP[i + 1][t]) + the side gradient at the arg-max; s2: times the Dropout2d scale of the plane"""
         B = self.B
         for i, t in cells:
             if i + 1 < len(levels):
                 lv, nx = levels[i], levels[i + 1]
-                if (nx.H, nx.W) == (lv.H, lv.W):
+                if s2 is not None and (nx.H, nx.W) == (lv.H, lv.W):
+                    check(self.L.rsis_scale_planes(ptr(DUP[i + 1]), ptr(s2[i][t]), ptr(DH[i]), B * lv.hid, lv.H * lv.W, stream()), "rsis_scale_planes")
+                    check(self.L.rsis_global_maxpool_scaled_bwd_add(ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(s2[i][t]), ptr(DH[i]), B * lv.hid,
+                                                                    lv.H * lv.W, stream()), "rsis_global_maxpool_scaled_bwd_add")
+                elif s2 is not None:
+                    check(self.L.rsis_upsample_maxpool_scaled_bwd(ptr(DUP[i + 1]), ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(s2[i][t]), ptr(DH[i]),
+                                                                  B * lv.hid, lv.H, lv.W, nx.H, nx.W, stream()), "rsis_upsample_maxpool_scaled_bwd")
+                elif (nx.H, nx.W) == (lv.H, lv.W):
                     DH[i].copy_(DUP[i + 1])
                     check(self.L.rsis_global_maxpool_bwd_add(ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(DH[i]), B * lv.hid, lv.H * lv.W, stream()),
                           "rsis_global_maxpool_bwd_add")
@@ -353,15 +420,16 @@ class _Blk(_Layout):
                                          shape=(self.B, lv.H, lv.W)))
         ops.blk_conv3x3_batch(jobs)
 
-    def up(self, levels, cells):
-        ups = [ops.blk_resize_job(levels[i].Hs[t], levels[i + 1].UP[t]) for i, t in cells if i + 1 < len(levels)]
+    def up(self, levels, cells, s2=None):
+        ups = [ops.blk_resize_job(levels[i].Hs[t], levels[i + 1].UP[t], scale=s2[i][t] if s2 is not None else None)
+               for i, t in cells if i + 1 < len(levels)]
         if ups:
             ops.blk_upsample_fwd_batch(ups)
 
-    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads):
-        """heads(), then the x2 upsample of the last level and conv_out, each over all steps at once"""
+    def tail(self, last, UP5, conv_out, co_w, co_b, out_masks, heads, sc=None):
+        """heads(), then the x2 upsample of the last level (times its Dropout2d scales sc, if any) and conv_out, each over all steps at once"""
         heads()
-        ops.blk_upsample_fwd_batch([ops.blk_resize_job(last.Hs.flatten(0, 1), UP5.flatten(0, 1))])
+        ops.blk_upsample_fwd_batch([ops.blk_resize_job(last.Hs.flatten(0, 1), UP5.flatten(0, 1), scale=sc)])
         check(self.L.rsis_blk_conv_out_seq_fwd(ptr(UP5), ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), self.T, self.B, 2 * last.H,
                                                2 * last.W, stream()), "rsis_blk_conv_out_seq_fwd")
 
@@ -374,11 +442,12 @@ class _Blk(_Layout):
             db = db() if db else None
             check(L.rsis_blk_conv_out_seq_wgrad(ptr(d_masks), ptr(UP5), ptr(dW), ptr(db), T, B, H5, W5, stream()), "rsis_blk_conv_out_seq_wgrad")
 
-    def up5_bwd(self, dUP5, dside, last, DH_last):
-        ops.blk_upsample_bwd_batch([ops.blk_resize_job(dUP5.flatten(0, 1), DH_last.flatten(0, 1), dside, last.ARG, backward=True)])
+    def up5_bwd(self, dUP5, dside, last, DH_last, sc=None):
+        ops.blk_upsample_bwd_batch([ops.blk_resize_job(dUP5.flatten(0, 1), DH_last.flatten(0, 1), dside, last.ARG, backward=True, scale=sc)])
 
-    def up_bwd(self, levels, cells, DUP, DH, dsides):
-        ups = [ops.blk_resize_job(DUP[i + 1], DH[i], dsides[i][t], levels[i].ARG[t], backward=True) for i, t in cells if i + 1 < len(levels)]
+    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None):
+        ups = [ops.blk_resize_job(DUP[i + 1], DH[i], dsides[i][t], levels[i].ARG[t], backward=True, scale=s2[i][t] if s2 is not None else None)
+               for i, t in cells if i + 1 < len(levels)]
         if ups:
             ops.blk_upsample_bwd_batch(ups)
 
@@ -439,10 +508,20 @@ class _DecoderSeqFn(torch.autograd.Function):
         for lv, key, side, arg in zip(levels, _per_level(KEY, hs, T, B), _per_level(SIDE, hs, T, B), _per_level(ARG, hs, T, B)):
             lv.KEY, lv.SIDE, lv.ARG = key, side, arg
         # G_i = W[:, skip channels] * skip_i + b, once per iteration (the skip features do not depend on t)
+        # the dropout scales of the whole sequence (model.py:141,172,177), drawn once; all rates 0: nothing is allocated or drawn
+        drop = None
+        p2, pc, ps = dropout.rates(decoder)
+        if p2 > 0 or pc > 0 or ps > 0:
+            drop = _Drop()
+            drop.S2, drop.MC, drop.MS = dropout.draw(dropout.decoder_state(decoder, dev), T * B * tot, p2, pc, ps)
+            drop.s2 = _per_level(drop.S2, hs, T, B) if p2 > 0 else None
+            drop.SIDEC, drop.SIDES = torch.empty(T * B * tot, **f32), torch.empty(T * B * tot, **f32)
+        s2 = drop.s2 if drop is not None else None
         lay.hoist(levels, feats, gates_w, gates_b, need_grad)
         last = levels[-1]
         H5, W5 = 2 * last.H, 2 * last.W
-        upc = UPCONV[0] and L.rsis_upconv_out_supported(last.hid, last.H, last.W, H5, W5) == 1
+        # (-dropout > 0: the last level goes through the unfused tail, whose upsample takes the scale)
+        upc = UPCONV[0] and s2 is None and L.rsis_upconv_out_supported(last.hid, last.H, last.W, H5, W5) == 1
         UP5 = None if upc else lay.empty((T, B), last.hid, H5, W5)            # model.py:163-164, all timesteps
         probs_tb = torch.empty((T, B, Wc.shape[0]), **f32)
         stop_tb = torch.empty((T, B, 1), **f32)
@@ -450,7 +529,10 @@ class _DecoderSeqFn(torch.autograd.Function):
         for d in range(T + n - 1):
             cells = _diagonal(d, n, T)
             lay.gates(levels, cells, wps)
-            lay.up(levels, cells)
+            if s2 is not None:
+                lay.up(levels, cells, s2)
+            else:
+                lay.up(levels, cells)
             # (the x2 upsample of the last level, model.py:163-164, feeds conv_out only, and the heads only the losses: both run once
             #  over all T steps after the loop)
 
@@ -459,6 +541,8 @@ class _DecoderSeqFn(torch.autograd.Function):
             key / feature / arg-max arrays are [T][B][hid] contiguous, i.e. T * B rows; the launch decodes the pooled keys (writes SIDE / ARG)"""
             ops.heads_fwd_launch(L, [v.SIDE for v in levels], hs, T * B, Wc, bc, Ws, bs, probs_tb, stop_tb,
                                  ([v.KEY for v in levels], [v.ARG for v in levels]))
+            if drop is not None:
+                _heads_fwd_masked(L, SIDE, drop, hs, T, B, Wc, bc, Ws, bs, probs_tb, stop_tb)
         # conv_out (model.py:167) on every timestep at once, logits straight into (B, T, N)
         out_masks = torch.empty((B, T, H5 * W5), **f32)
         if upc:       # upsample + conv_out in one pass, the upsampled tensor never formed (nor rounded to bf16)
@@ -466,7 +550,10 @@ class _DecoderSeqFn(torch.autograd.Function):
             check(L.rsis_upconv_out_fwd(ptr(last.Hs), lay.blk, ptr(co_w.detach()), ptr(co_b.detach()), ptr(out_masks), T, B, last.hid, last.H, last.W,
                                         H5, W5, stream()), "rsis_upconv_out_fwd")
         else:
-            lay.tail(last, UP5, decoder.conv_out, co_w, co_b, out_masks, heads)
+            if s2 is not None:
+                lay.tail(last, UP5, decoder.conv_out, co_w, co_b, out_masks, heads, s2[n - 1])
+            else:
+                lay.tail(last, UP5, decoder.conv_out, co_w, co_b, out_masks, heads)
         out_probs = probs_tb.transpose(0, 1).contiguous()            # (B, T, C)   train.py:119
         out_stops = stop_tb.transpose(0, 1).contiguous()             # (B, T, 1)   train.py:120
         hidden = []
@@ -475,10 +562,14 @@ class _DecoderSeqFn(torch.autograd.Function):
                 hidden += [lay.to_nchw(lv.Hs[T - 1]), lv.Cs[T - 1]]
         if RECORD[0]:
             LAST["arg"] = [lv.ARG.clone() for lv in levels]
+            if drop is not None:
+                LAST["drop"] = {"s2": [v.clone() for v in s2] if s2 is not None else None, "mc": [v.clone() for v in _per_level(drop.MC, hs, T, B)],
+                                "ms": [v.clone() for v in _per_level(drop.MS, hs, T, B)]}
         ctx.set_materialize_grads(False)
         if need_grad:
             ctx.lay, ctx.decoder, ctx.T, ctx.levels, ctx.upc = lay, decoder, T, levels, upc
             ctx.UP5, ctx.probs_tb, ctx.feats, ctx.params = UP5, probs_tb, feats, params
+            ctx.drop = drop
         else:
             for lv in levels:
                 lv.G = lv.ACT = lv.UP = lv.skip = None
@@ -502,6 +593,8 @@ class _DecoderSeqFn(torch.autograd.Function):
         last = levels[-1]
         H5, W5 = 2 * last.H, 2 * last.W
         UP5 = ctx.UP5
+        drop = ctx.drop
+        s2 = drop.s2 if drop is not None else None
         grads_par = [None] * len(params)
 
         def target(k):
@@ -535,7 +628,10 @@ class _DecoderSeqFn(torch.autograd.Function):
             dp_tb = d_probs.transpose(0, 1).contiguous() if d_probs is not None else None
             ds_tb = d_stops.transpose(0, 1).contiguous() if d_stops is not None else None
             hb = [target(2 * n + 2 + k)[0] if need_par[2 * n + 2 + k] else None for k in range(4)]
-            _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, ctx.probs_tb, dp_tb, ds_tb, dsides, hb)
+            if drop is None:
+                _heads_bwd_all_steps(L, levels, hs, n, T, B, Wc, Ws, ctx.probs_tb, dp_tb, ds_tb, dsides, hb)
+            else:
+                _heads_bwd_masked(L, drop, hs, T, B, Wc, Ws, ctx.probs_tb, dp_tb, ds_tb, DSIDE, hb)
         # ---- reverse wavefront ----
         DA = [torch.empty_like(lv.ACT) for lv in levels]
         DH = [lay.empty((B,), lv.hid, lv.H, lv.W) for lv in levels]                  # gradient of h[i][t] from above (upsample + pool)
@@ -557,11 +653,17 @@ class _DecoderSeqFn(torch.autograd.Function):
             check(L.rsis_upconv_out_bwd(ptr(d_masks), ptr(last.Hs), lay.blk, ptr(co_w.detach()), ptr(DH_last), ptr(dW), ptr(db), ptr(dsides[n - 1]),
                                         ptr(last.ARG), ptr(partial), T, B, last.hid, last.H, last.W, H5, W5, stream()), "rsis_upconv_out_bwd")
         else:
-            lay.up5_bwd(dUP5, dsides[n - 1], last, DH_last)
+            if s2 is not None:
+                lay.up5_bwd(dUP5, dsides[n - 1], last, DH_last, s2[n - 1])
+            else:
+                lay.up5_bwd(dUP5, dsides[n - 1], last, DH_last)
         for d in range(T + n - 2, -1, -1):
             cells = _diagonal(d, n, T)
             # gradient reaching h[i][t] through its upsample into the next level and its side max-pool
-            lay.up_bwd(levels, cells, DUP, DH, dsides)
+            if s2 is not None:
+                lay.up_bwd(levels, cells, DUP, DH, dsides, s2)
+            else:
+                lay.up_bwd(levels, cells, DUP, DH, dsides)
             lstm, dg = [], []
             for i, t in cells:
                 lv = levels[i]
@@ -611,7 +713,7 @@ class _DecoderSeqFn(torch.autograd.Function):
                                          hid, dt, "rsis_conv2d_wgrad(batched h)", direct)
         for lv in levels:
             lv.G = lv.Hs = lv.Cs = lv.ACT = lv.UP = lv.skip = None
-        ctx.lay = ctx.levels = ctx.UP5 = ctx.feats = ctx.params = ctx.decoder = None
+        ctx.lay = ctx.levels = ctx.UP5 = ctx.feats = ctx.params = ctx.decoder = ctx.drop = None
         return (None, None, None, None, None) + tuple(dfeats) + tuple(grads_par)
 
 

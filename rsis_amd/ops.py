@@ -1207,26 +1207,36 @@ def blk_conv3x3_batch(jobs):
     check(lib().rsis_blk_conv3x3_batch(arr, len(jobs), stream()), "rsis_blk_conv3x3_batch")
 
 
-def blk_resize_job(src, dst, dpool=None, arg=None, backward=False):
-    """forward: src = x [B][C/8][Hi][Wi][8] -> dst = y [B][C/8][Ho][Wo][8]; backward: src = dy (Ho x Wo) -> dst = dx (Hi x Wi), + dpool / arg"""
+def blk_resize_job(src, dst, dpool=None, arg=None, backward=False, scale=None):
+    """forward: src = x [B][C/8][Hi][Wi][8] -> dst = y [B][C/8][Ho][Wo][8]; backward: src = dy (Ho x Wo) -> dst = dx (Hi x Wi), + dpool / arg.
+    scale ([B][C] fp32): the job of the scaled entry points (the result's channel planes multiplied by it); all jobs of a batch alike"""
     _blk_ok(src, dst)
-    j = _lib.BlkResizeJob()
+    j = _lib.BlkResizeJob() if scale is None else _lib.BlkResizeScaledJob()
+    if scale is not None:
+        j.scale = scale.data_ptr()
     small, big = (dst, src) if backward else (src, dst)
     j.src, j.dst = src.data_ptr(), dst.data_ptr()
     j.dpool = dpool.data_ptr() if dpool is not None else None
     j.arg = arg.data_ptr() if arg is not None else None
     j.B, j.C, j.Hi, j.Wi, j.Ho, j.Wo = small.shape[0], small.shape[1] * 8, small.shape[2], small.shape[3], big.shape[2], big.shape[3]
-    return j, (src, dst, dpool, arg)
+    return j, (src, dst, dpool, arg, scale)
+
+
+def _blk_resize_batch(jobs, name):
+    kind = type(jobs[0][0])
+    assert all(type(j) is kind for j, _keep in jobs)
+    if kind is _lib.BlkResizeScaledJob:
+        name = name.replace("_batch", "_scaled_batch")
+    arr = (kind * len(jobs))(*[j for j, _keep in jobs])
+    check(getattr(lib(), name)(arr, len(jobs), stream()), name)
 
 
 def blk_upsample_fwd_batch(jobs):
-    arr = (_lib.BlkResizeJob * len(jobs))(*[j for j, _keep in jobs])
-    check(lib().rsis_blk_upsample_fwd_batch(arr, len(jobs), stream()), "rsis_blk_upsample_fwd_batch")
+    _blk_resize_batch(jobs, "rsis_blk_upsample_fwd_batch")
 
 
 def blk_upsample_bwd_batch(jobs):
-    arr = (_lib.BlkResizeJob * len(jobs))(*[j for j, _keep in jobs])
-    check(lib().rsis_blk_upsample_bwd_batch(arr, len(jobs), stream()), "rsis_blk_upsample_bwd_batch")
+    _blk_resize_batch(jobs, "rsis_blk_upsample_bwd_batch")
 
 
 def blk_lstm_bwd_job(dh, dh2, dc_next, act, c_prev, c, da, dc_prev):
