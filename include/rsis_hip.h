@@ -48,6 +48,13 @@ extern "C" {
  * geometry, and the weight gradient, behaves exactly as under RSIS_DTYPE_F32.  Results differ from the direct kernel by fp32
  * rounding only (measured closer to float64 than a sequential fp32 sum: the 2304-deep chain becomes 16 chains of 256). */
 #define RSIS_DTYPE_F32_WINO 3
+/* fp32 operands as RSIS_DTYPE_F32, but the TRAINING calls (rsis_conv2d_fwd with tile + 100, rsis_conv2d_dgrad, rsis_convlstm_fwd with
+ * act_out, and their batch forms) of a 3x3 / stride 1 / pad 1 conv whose sources are multiples of 8 channels (data gradient: Cout % 8 == 0)
+ * run on v_mfma_f32_32x32x16_bf16 with each operand split into three bf16 limbs (six of the nine limb products, those of weight
+ * >= 2^-16, fp32 accumulation: conv3x3_limb.h).  The packed copies then hold the weight's three limbs (1.5 x the bytes of the f32 copy);
+ * an inference call on such a copy returns RSIS_ERR_UNSUPPORTED (it belongs on the RSIS_DTYPE_F32 copy).  Every other geometry, and the
+ * weight gradient, behaves exactly as under RSIS_DTYPE_F32.  Never split over K: one contributor per address in either mode. */
+#define RSIS_DTYPE_F32_LIMB 4
 
 int rsis_version(void);
 const char* rsis_error_string(int code);

@@ -46,6 +46,16 @@ static inline bool wino_geom_dgrad(int ks, int stride, int pad, int Cin, int Cou
 static inline bool use_wino(int dtype, int ks, int stride, int pad, int Cin, int Cout, int nseg, int lstm_hid) {
   return dtype == RSIS_DTYPE_F32_WINO && wino_geom(ks, stride, pad, Cin, Cout, nseg, lstm_hid);
 }
+// -- RSIS_DTYPE_F32_LIMB: the limb flavour of the direct 3x3 kernel (conv3x3_limb.h) for the TRAINING calls of 3x3 / stride 1 / pad 1
+//    convs whose reduction channels come in multiples of 8 per source (forward: every concat source; data gradient: the rows of dy);
+//    anything else under that dtype is plain RSIS_DTYPE_F32.  An inference call on a limb copy is refused: it keeps the f32 copy.
+static inline bool limb_geom(int ks, int stride, int pad, int Cout, int nseg, const int* Cseg) {
+  if (!(ks == 3 && stride == 1 && pad == 1 && Cout > 1)) return false;
+  for (int s = 0; s < nseg; ++s)
+    if (Cseg[s] % 8 != 0) return false;
+  return true;
+}
+static inline bool limb_geom_dgrad(int ks, int stride, int pad, int Cout) { return ks == 3 && stride == 1 && pad == 1 && Cout > 1 && Cout % 8 == 0; }
 // cell rows of a bf16 packed copy whose reduction axis is the concat of nseg channel segments
 static inline int bf16_rows(int ks, int nseg, const int* Cseg) {
   const int ckb = bf16_ckb(ks * ks);
@@ -125,7 +135,11 @@ static PackPlan pack_plan(bool dgrad, int dtype, int Cout, int Ctot, int ks, int
     return p;
   }
   long cell = 4;                      // bytes per row and column: one f32, or a 16-byte cell of 8 bf16 reduction channels
-  if (use_bf16(dtype, ks, stride, pad, Cout)) {
+  if (dtype == RSIS_DTYPE_F32_LIMB && (dgrad ? limb_geom_dgrad(ks, stride, pad, Cout) : limb_geom(ks, stride, pad, Cout, nseg, Cseg))) {
+    p.mode = dgrad ? PACK_LIMB_DGRAD : PACK_LIMB_FWD;         // three limb planes of bf16 cells per 16-channel chunk: 1.5 x the f32 rows
+    p.krows = 3 * (dgrad ? bf16_rows(ks, 1, &Cout) : bf16_rows(ks, nseg, Cseg));
+    cell = 16;
+  } else if (use_bf16(dtype, ks, stride, pad, Cout)) {
     p.mode = dgrad ? PACK_BF16_DGRAD : PACK_BF16_FWD;
     p.krows = dgrad ? bf16_rows(ks, 1, &Cout) : bf16_rows(ks, nseg, Cseg);
     cell = 16;
@@ -310,6 +324,11 @@ static int conv2d_fwd_impl(const float* const* src, const int* Csrc, int nsrc, i
   }
   if (use_wino(dtype, ks, stride, pad, Csrc[0], Cout, nsrc, 0))
     return rsis_launch_conv_wino(src[0], Wp, bias, addend, out, B, Csrc[0], Cout, H, W, (hipStream_t)stream, a.precise);
+  if (dtype == RSIS_DTYPE_F32_LIMB && limb_geom(ks, stride, pad, Cout, nsrc, Csrc)) {
+    if (!allow_splitk) return RSIS_ERR_UNSUPPORTED;          // (an inference / parity call: the f32 kernel on the f32 copy)
+    a.limb = 1;                                              // unsplit in either mode
+    return rsis_launch_conv3x3_direct(a, 0, direct_variant(tile), (hipStream_t)stream);
+  }
   if (use_bf16(dtype, ks, stride, pad, Cout)) {
     if (stride != 1) return RSIS_ERR_UNSUPPORTED;      // strided 1x1: run the stride-1 form on a sub-sampled input
     if (ks == 1 && nsrc != 1) return RSIS_ERR_UNSUPPORTED;
@@ -385,6 +404,11 @@ int rsis_conv2d_dgrad(const float* dy, int B, int Cout, int Hy, int Wy, const vo
     const float* xs[1] = {dy}; const void* us[1] = {Wd}; float* y0[1] = {dx[0]}; float* y1[1] = {dx[1]};
     const int b1[1] = {B}, c1[1] = {Cout}, co1[1] = {ctot}, c01[1] = {Cdx[0]}, h1[1] = {Hy}, w1[1] = {Wy};
     return rsis_launch_conv_wino_group(1, xs, us, y0, y1, b1, c1, co1, c01, h1, w1, (hipStream_t)stream);
+  }
+  if (dtype == RSIS_DTYPE_F32_LIMB && limb_geom_dgrad(ks, stride, pad, Cout)) {
+    if (Hx != Hy || Wx != Wy) return RSIS_ERR_ARG;
+    a.limb = 1;
+    return rsis_launch_conv3x3_direct(a, 0, direct_variant(tile), (hipStream_t)stream);
   }
   if (use_bf16(dtype, ks, stride, pad, Cout)) {
     if (ks == 3) {
@@ -528,6 +552,10 @@ static int lstm_fill(ConvArgs& a, int& route, const float* const* src, const int
   route = use_bf16(dtype, ks, 1, pad, 4 * hid) ? 0 : (use_direct(ks, 1, pad) ? 1 : 2);
   a.side_key = side_key;
   a.precise = act_out ? 0 : 1;            // no saved gates: an inference call
+  if (dtype == RSIS_DTYPE_F32_LIMB && limb_geom(ks, 1, pad, 4 * hid, nsrc, Csrc)) {
+    if (!act_out) return RSIS_ERR_UNSUPPORTED;           // (the limb copy serves training calls only)
+    a.limb = 1;
+  }
   if (side_key && (route == 2 || (long)H * W >= 0x7FFFFFFFL)) return RSIS_ERR_UNSUPPORTED;   // the fused side max-pool lives in the 3x3 epilogues
   return RSIS_OK;
 }
@@ -1158,7 +1186,8 @@ int rsis_conv2d_dgrad_batch(const rsis_dgrad_job* jobs, int njobs, void* stream)
     }
     // grouped: the exact-f32 direct kernel (3x3 / stride 1 / pad 1, no addend) with 32-bit epilogue addressing; everything else -- and
     // every job in the deterministic mode, where launches stay as the single-call path issues them -- through rsis_conv2d_dgrad
-    const bool groupable = q.dtype == RSIS_DTYPE_F32 && use_direct(q.ks, q.stride, q.pad) && !q.addend && q.Hx == q.Hy && q.Wx == q.Wy &&
+    const bool limb = q.dtype == RSIS_DTYPE_F32_LIMB && limb_geom_dgrad(q.ks, q.stride, q.pad, q.Cout);
+    const bool groupable = (q.dtype == RSIS_DTYPE_F32 || limb) && use_direct(q.ks, q.stride, q.pad) && !q.addend && q.Hx == q.Hy && q.Wx == q.Wy &&
                            !(q.Cout == 1) && ctot <= q.Cin_packed && (size_t)q.B * (ctot > q.Cout ? ctot : q.Cout) * q.Hy * q.Wy * 4 < (1ull << 31) &&
                            !rsis_deterministic();
     if (!groupable) {
@@ -1168,6 +1197,7 @@ int rsis_conv2d_dgrad_batch(const rsis_dgrad_job* jobs, int njobs, void* stream)
     }
     rc = dgrad_fill(grp[ng], q.dy, q.B, q.Cout, q.Hy, q.Wy, q.Wd, q.Cin_packed, q.ks, q.stride, q.pad, q.dx, q.Cdx, q.ndst, q.Hx, q.Wx, q.addend);
     if (rc) break;
+    grp[ng].limb = limb ? 1 : 0;
     force[ng++] = direct_variant(q.tile);
   }
   if (rc == RSIS_OK && nw > 0) rc = rsis_launch_conv_wino_group(nw, wx, wu, wy0, wy1, wb, wc, wco, wc0, wh, ww, (hipStream_t)stream);

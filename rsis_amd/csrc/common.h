@@ -16,8 +16,8 @@
 #define RSIS_MAX_SRC 3      // channel-concatenated sources / split destinations per conv
 
 // Layouts of a packed weight copy (pack.hip): chosen by pack_plan() of api.hip, carried to the device in rsis_pack_job.imode.  The values
-// are part of that struct's contract and the ORDER is used: f32 rows < PACK_BF16_FWD <= bf16 cells < PACK_WINO_FWD <= Winograd blocks, and
-// from PACK_DIRECT_DGRAD on the f32 rows come in 72-row chunks.
+// are part of that struct's contract and the ORDER is used: f32 rows < PACK_BF16_FWD <= bf16 cells < PACK_WINO_FWD <= Winograd blocks < PACK_LIMB_FWD <=
+// limb planes, and from PACK_DIRECT_DGRAD on the f32 rows come in 72-row chunks.
 enum PackMode {
   PACK_IGEMM_FWD = 0,         // implicit GEMM, forward
   PACK_IGEMM_DGRAD = 1,       // implicit GEMM, data gradient
@@ -27,7 +27,9 @@ enum PackMode {
   PACK_BF16_FWD = 5,          // bf16 cells of conv_bf16.hip, forward
   PACK_BF16_DGRAD = 6,        // bf16 cells, data gradient
   PACK_WINO_FWD = 7,          // Winograd F(2x2, 3x3) blocks of conv_wino.hip, forward
-  PACK_WINO_DGRAD = 8         // Winograd blocks, data gradient
+  PACK_WINO_DGRAD = 8,        // Winograd blocks, data gradient
+  PACK_LIMB_FWD = 9,          // three bf16 limb planes per 16-channel chunk of conv3x3_limb.h, forward (cells as PACK_BF16_FWD)
+  PACK_LIMB_DGRAD = 10        // limb planes, data gradient (cells as PACK_BF16_DGRAD)
 };
 // bf16 path: input channels per packed chunk of a conv with KK = ks * ks taps
 __host__ __device__ __forceinline__ int bf16_ckb(int KK) { return KK == 1 ? RSIS_CKB1 : RSIS_CKB3; }
@@ -130,6 +132,7 @@ struct ConvArgs {
   float* act_out;                  // [B][4*hid][Ho][Wo] post-nonlinearity gates (interleaved rows) or null
   unsigned long long* side_key;    // [B][hid] or null: global max-pool of h fused into the epilogue (rsis_side_key, zeroed by the caller)
   int precise;                     // direct 3x3 kernel: sum the reduction in segments whatever its length (inference calls; conv3x3_direct.hip)
+  int limb;                        // direct 3x3 kernel: wp is the limb copy (PACK_LIMB_*), the call runs the limb flavour (conv3x3_limb.h)
 };
 
 // ---- global max-pool of the hidden state (reference model.py:143) fused into the ConvLSTM epilogue ----

@@ -26,13 +26,13 @@
 // immediate offset per MFMA (2-way LDS bank conflicts from the pixel stride of 2), plain epilogue on the output grid.
 #include "common.h"
 #include "launchers.h"
+#include "conv3x3_limb.h"
 #include <stdlib.h>
 #ifndef XCD_CHUNKED
 #define XCD_CHUNKED 1
 #endif
 
 enum { EPI_PLAIN = 0, EPI_LSTM = 1, EPI_S2 = 2, EPI_F2 = 3 };
-typedef __attribute__((address_space(3))) void* lds_vp_t;
 #define CK RSIS_CK
 #ifndef RSIS_ACC_FLUSH
 #define RSIS_ACC_FLUSH 4      // chunks (of 8 channels x 9 taps) per accumulation segment; a power of two
@@ -60,7 +60,9 @@ constexpr int direct_lds_floats() {
 
 // The block program.  bid: the block's index inside its launch (or inside its job of a grouped launch); kz / ksplit: its slice of
 // the channel chunks (grid split-K); lds: the block's LDS, direct_lds_floats<...>() floats.
-template <int BM, int TW, int TH, int NI, int EPI, int KSP = 1, int NWV = 4, bool FLUSH = false, bool BNE = false>
+// LIMB: the staging and the MFMA loop of conv3x3_limb.h (split-bf16 limbs, `lds`: limb_lds_floats<BM, TW, TH>() floats) in front of
+// the same epilogue; p.wp is then the limb copy of the weights (PACK_LIMB_FWD / PACK_LIMB_DGRAD)
+template <int BM, int TW, int TH, int NI, int EPI, int KSP = 1, int NWV = 4, bool FLUSH = false, bool BNE = false, bool LIMB = false>
 __device__ __forceinline__ void conv3x3_direct_body(const ConvArgs& p, const int bid, const int kz, const int ksplit, float* const lds) {
 #if __HIP_DEVICE_COMPILE__   // (the host pass only needs the launch stub; the buffer-resource builtins do not exist there)
   constexpr int BN = TW * TH * NI;
@@ -79,6 +81,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const ConvArgs& p, const int
   static_assert(TN >= 1 && BN % (WGN * 32) == 0 && WGM * WGN * KSP == NWV && (CK / 2) % KSP == 0 && (KSP == 1 || EPI != EPI_S2), "tile");
 
   static_assert(2 * (XSP + WS) == direct_lds_floats<BM, TW, TH, NI, EPI, NWV>(), "LDS size helper out of sync");
+  static_assert(!LIMB || (KSP == 1 && NWV == 4 && NI == 1 && !FLUSH && !BNE && (EPI == EPI_PLAIN || EPI == EPI_LSTM)), "limb flavour: 256 threads, plain / LSTM");
   float* const Xs0 = lds;
   float* const Ws0 = lds + 2 * XSP;
 
@@ -161,6 +164,9 @@ __device__ __forceinline__ void conv3x3_direct_body(const ConvArgs& p, const int
       for (int r = 0; r < 16; ++r) accs[c][j][r] = 0.f;
   f32x16 (&acc)[TN] = accs[0];
 
+  if constexpr (LIMB) {
+    rsis_limb_mainloop<BM, TW, TH, TN>(p, b0, x0, y0, co_t, wm, wn, lds, acc);
+  } else {
   const gcf_t wbase = (gcf_t)p.wp + co_t * BM;
 
   // scalar chunk cursor, positioned on this block's first chunk
@@ -251,6 +257,7 @@ __device__ __forceinline__ void conv3x3_direct_body(const ConvArgs& p, const int
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] += tot[j][r];
   }
+  }     // (!LIMB)
 
   if constexpr (BNE) {
     // inference, eval-mode BatchNorm folded into the epilogue (rsis_conv2d_fwd_bn_eval): the block's BM (scale, shift) pairs, computed
@@ -482,6 +489,12 @@ __global__ __launch_bounds__(NWV * 64) void conv3x3_direct_kernel(const ConvArgs
   conv3x3_direct_body<BM, TW, TH, NI, EPI, KSP, NWV, FLUSH, BNE>(p, blockIdx.x, blockIdx.y, gridDim.y, lds);
 }
 
+template <int BM, int TW, int TH, int EPI>
+__global__ __launch_bounds__(256) void conv3x3_limb_kernel(const ConvArgs p) {
+  __shared__ __attribute__((aligned(16))) float lds[limb_lds_floats<BM, TW, TH>()];
+  conv3x3_direct_body<BM, TW, TH, 1, EPI, 1, 4, false, false, true>(p, blockIdx.x, 0, 1, lds);
+}
+
 // ---- grouped launch: several INDEPENDENT convs in ONE grid (rsis_convlstm_fwd_batch: the ConvLSTM levels of one diagonal of the
 // decoder's (level, timestep) wavefront -- level i at step t depends on level i-1 at step t and on itself at step t-1, so the cells
 // (i, d - i) of a diagonal d are independent).  Alone, each gate launch pays its ramp, prologue, per-chunk barrier stalls and
@@ -499,11 +512,17 @@ struct DirectGroup {
 };
 static_assert(sizeof(DirectGroup) <= 4000, "kernel arguments are limited to 4 KB");
 
-template <int EPI, bool FLUSH = false>
-__global__ __launch_bounds__(256) void conv3x3_direct_group_kernel(const DirectGroup g) {
-  constexpr int LMAX = cmax(cmax(direct_lds_floats<32, 16, 8, 1, EPI, 4>(), direct_lds_floats<32, 32, 8, 1, EPI, 4>()),
+// LIMB (conv3x3_limb_group_kernel): the grid also holds jobs on the limb body (variant codes 14 / 15: 16 x 8 / 32 x 8 pixels, 32 rows),
+// selected per job; its LDS footprint is then the limb body's (45 / 60 KB instead of 40: two blocks per CU instead of four, for the f32
+// jobs of the grid as well).  A diagonal without limb jobs keeps conv3x3_direct_group_kernel, unchanged.
+template <int EPI, bool LIMB>
+constexpr int group_lds_floats() {
+  constexpr int LF32 = cmax(cmax(direct_lds_floats<32, 16, 8, 1, EPI, 4>(), direct_lds_floats<32, 32, 8, 1, EPI, 4>()),
                             direct_lds_floats<32, 8, 8, 1, EPI, 4>());
-  __shared__ __attribute__((aligned(16))) float lds[LMAX];
+  return LIMB ? cmax(LF32, cmax(limb_lds_floats<32, 16, 8>(), limb_lds_floats<32, 32, 8>())) : LF32;
+}
+template <int EPI, bool FLUSH, bool LIMB>
+__device__ __forceinline__ void direct_group_program(const DirectGroup& g, float* const lds) {
   const int b = blockIdx.x;
   int j = 0;
 #pragma unroll
@@ -513,8 +532,20 @@ __global__ __launch_bounds__(256) void conv3x3_direct_group_kernel(const DirectG
   switch (g.variant[j]) {
     case 4: conv3x3_direct_body<32, 16, 8, 1, EPI, 1, 4, FLUSH>(p, local, 0, 1, lds); break;
     case 5: conv3x3_direct_body<32, 32, 8, 1, EPI, 1, 4, FLUSH>(p, local, 0, 1, lds); break;
+    case 14: if constexpr (LIMB) { conv3x3_direct_body<32, 16, 8, 1, EPI, 1, 4, false, false, true>(p, local, 0, 1, lds); } break;
+    case 15: if constexpr (LIMB) { conv3x3_direct_body<32, 32, 8, 1, EPI, 1, 4, false, false, true>(p, local, 0, 1, lds); } break;
     default: conv3x3_direct_body<32, 8, 8, 1, EPI, 2, 4, FLUSH>(p, local, 0, 1, lds); break;
   }
+}
+template <int EPI, bool FLUSH = false>
+__global__ __launch_bounds__(256) void conv3x3_direct_group_kernel(const DirectGroup g) {
+  __shared__ __attribute__((aligned(16))) float lds[group_lds_floats<EPI, false>()];
+  direct_group_program<EPI, FLUSH, false>(g, lds);
+}
+template <int EPI>
+__global__ __launch_bounds__(256) void conv3x3_limb_group_kernel(const DirectGroup g) {
+  __shared__ __attribute__((aligned(16))) float lds[group_lds_floats<EPI, true>()];
+  direct_group_program<EPI, false, true>(g, lds);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -626,8 +657,32 @@ static int launch_direct_f2(ConvArgs& a, hipStream_t st, int force) {
   return launch_direct_cfg<32, 16, 8, 1, EPI_F2>(a, st);
 }
 
+// the limb flavour's tile for a job: 4 = 32 rows x 16 x 8 pixels (maps up to 16 wide), 5 = 32 rows x 32 x 8; a forced variant of the
+// f32 kernel maps to the tile of its width class
+static int pick_limb_variant(const ConvArgs& a, int force) {
+  if (force == 4 || force == 5) return force;
+  if (force == 3 || force == 7 || force == 8) return 5;
+  if (force > 0) return 4;
+  return a.W <= 16 ? 4 : 5;
+}
+template <int BM, int TW, int TH, int EPI>
+static int launch_limb_cfg(ConvArgs& a, hipStream_t st) {
+  a.n_co_tiles = rsis_cdiv(a.Cout, BM);
+  a.n_px_tiles = rsis_cdiv(a.W, TW) * rsis_cdiv(a.H, TH) * a.B;
+  a.ksplit = 1;           // never split: one contributor per address in either mode
+  hipLaunchKernelGGL((conv3x3_limb_kernel<BM, TW, TH, EPI>), dim3(a.n_co_tiles * 8 * rsis_cdiv(a.n_px_tiles, 8)), dim3(256), 0, st, a);
+  return rsis_check_launch();
+}
+static int launch_limb(ConvArgs& a, int epi, int force, hipStream_t st) {
+  if (epi != EPI_PLAIN && epi != EPI_LSTM) return RSIS_ERR_UNSUPPORTED;
+  const int v = pick_limb_variant(a, force);
+  if (epi == EPI_LSTM) return v == 4 ? launch_limb_cfg<32, 16, 8, EPI_LSTM>(a, st) : launch_limb_cfg<32, 32, 8, EPI_LSTM>(a, st);
+  return v == 4 ? launch_limb_cfg<32, 16, 8, EPI_PLAIN>(a, st) : launch_limb_cfg<32, 32, 8, EPI_PLAIN>(a, st);
+}
+
 int rsis_launch_conv3x3_direct(ConvArgs& a, int epi, int force_variant, hipStream_t st) {
   if (a.nsrc < 0 || a.nsrc > RSIS_MAX_SRC) return RSIS_ERR_ARG;
+  if (a.limb) return launch_limb(a, epi, force_variant, st);
   if (epi == EPI_F2) return launch_direct_f2(a, st, force_variant);
   if (epi == EPI_LSTM) return launch_direct_epi<EPI_LSTM>(a, st, force_variant);
   if (epi == EPI_S2) return launch_direct_epi<EPI_S2>(a, st, force_variant);
@@ -659,10 +714,11 @@ static int launch_direct_group(ConvArgs* jobs, int n, const int* force_variant, 
       int v = pick_direct_variant<EPI>(a, force_variant ? force_variant[j0 + j] : 0);
       // the grouped kernel's variants: 6 (8x8 maps), 4 (16 x 8 tiles), 5 (32 x 8 tiles), all 32 rows x 256 threads
       if (v == 1) v = 6; else if (v == 2 || v == 9) v = 4; else if (v == 3 || v == 7 || v == 8) v = 5;
+      if (a.limb) v = 10 + pick_limb_variant(a, force_variant ? force_variant[j0 + j] : 0);       // ... and 14 / 15: the limb body
       var[j] = v;
       int nq = 0;
       for (int s = 0; s < a.nsrc; ++s) nq += (a.C[s] + RSIS_CK - 1) / RSIS_CK;
-      work[j] = (long)nq * (v == 6 ? 64 : (v == 5 ? 256 : 128));
+      work[j] = (long)nq * (v == 6 ? 64 : (v % 10 == 5 ? 256 : 128));
       order[j] = j;
     }
     for (int x = 1; x < m; ++x)                        // insertion sort, descending work per block
@@ -674,7 +730,7 @@ static int launch_direct_group(ConvArgs* jobs, int n, const int* force_variant, 
       const int j = order[k];
       ConvArgs a = jobs[j0 + j];
       const int v = var[j];
-      const int bm = 32, tw = v == 6 ? 8 : (v == 5 ? 32 : 16);
+      const int bm = 32, tw = v == 6 ? 8 : (v % 10 == 5 ? 32 : 16);
       a.n_co_tiles = rsis_cdiv(a.Cout, bm);
       a.n_px_tiles = rsis_cdiv(a.W, tw) * rsis_cdiv(a.H, 8) * a.B;
       a.ksplit = 1;
@@ -684,9 +740,11 @@ static int launch_direct_group(ConvArgs* jobs, int n, const int* force_variant, 
       blocks += a.n_co_tiles * 8 * rsis_cdiv(a.n_px_tiles, 8);
     }
     for (int k = m; k <= RSIS_DG_MAXJ; ++k) g.begin[k] = blocks;
-    bool precise = false;
-    for (int k = 0; k < m; ++k) precise = precise || g.job[k].precise != 0;
-    if (EPI == EPI_LSTM && precise) hipLaunchKernelGGL((conv3x3_direct_group_kernel<EPI_LSTM, true>), dim3(blocks), dim3(256), 0, st, g);
+    bool precise = false, limb = false;
+    for (int k = 0; k < m; ++k) { precise = precise || g.job[k].precise != 0; limb = limb || g.job[k].limb != 0; }
+    if (limb && precise) return RSIS_ERR_UNSUPPORTED;        // (limb jobs are training calls)
+    if (limb) hipLaunchKernelGGL((conv3x3_limb_group_kernel<EPI>), dim3(blocks), dim3(256), 0, st, g);
+    else if (EPI == EPI_LSTM && precise) hipLaunchKernelGGL((conv3x3_direct_group_kernel<EPI_LSTM, true>), dim3(blocks), dim3(256), 0, st, g);
     else hipLaunchKernelGGL((conv3x3_direct_group_kernel<EPI>), dim3(blocks), dim3(256), 0, st, g);
     if (rsis_check_launch() != RSIS_OK) return RSIS_ERR_LAUNCH;
   }

@@ -10,6 +10,7 @@
 //                          c0 + 2*c2 + h, tap rs.  FWD columns = co_p; DGRAD rows = chunks of co_p, columns = cg, tap 8-rs.
 // co_p -> reference row: (co_p&3)*hid + (co_p>>2) for gate-interleaved ConvLSTM rows (clstm.py:47), identity otherwise.
 #include "blk_cell.h"
+#include "limb_split.h"
 #include "../../include/rsis_hip.h"
 #include "launchers.h"
 
@@ -94,6 +95,17 @@ __global__ void pack_kernel(int mode, const float* __restrict__ W, float* __rest
 //   PACK_BF16_FWD: reduction channel = input channel of the concat, col = co_p.
 //   PACK_BF16_DGRAD: reduction channel = dy channel co_p, col = cg (index in the concat), 3x3 taps flipped.
 __device__ __forceinline__ unsigned short to_bf16(float v) { return (unsigned short)(blk_pack2(v, 0.f) & 0xFFFFu); }
+// ---- limb layouts (conv3x3_limb.h; 3x3 only): the same cells, three times -- limb l of rsis_limb_split3 (truncation: the three add up
+//   to the fp32 weight bit for bit) instead of the rounded value.  A 16-channel chunk q owns 3 x 18 consecutive cell rows:
+//   cell row kb = q * 18 + (rs * 2 + cb) of the bf16 layout becomes row (q * 3 + l) * 18 + (rs * 2 + cb) for limb l.
+//   PACK_LIMB_FWD / PACK_LIMB_DGRAD index the reference weight as PACK_BF16_FWD / PACK_BF16_DGRAD do.  limb < 0: the bf16 layouts.
+__device__ __forceinline__ unsigned short pack_cvt(float v, int limb) {
+  if (limb < 0) return to_bf16(v);
+  float l0, l1, l2;
+  rsis_limb_split3(v, l0, l1, l2);
+  return (unsigned short)(__float_as_uint(limb == 0 ? l0 : (limb == 1 ? l1 : l2)) >> 16);
+}
+__device__ __forceinline__ int pack_limb_row(int kb, int limb) { return limb < 0 ? kb : ((kb / 18) * 3 + limb) * 18 + kb % 18; }
 
 __device__ __forceinline__ int pack_bf16_idx(int mode, int kb, int col, int e, int Cout, int Ctot, int KK, const SegMap& m, int hid) {
   const int CKB = bf16_ckb(KK), NCB = CKB / 8;
@@ -128,13 +140,13 @@ __device__ __forceinline__ float pack_bf16_src(int mode, const float* __restrict
 }
 
 __global__ void pack_bf16_kernel(int mode, const float* __restrict__ W, unsigned short* __restrict__ out, int Cout, int Ctot, int KK,
-                                 SegMap m, int ldw, int nkb, int hid) {
+                                 SegMap m, int ldw, int nkb, int hid, int limb) {
   const long total = (long)nkb * ldw * 8;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int e = (int)(i & 7);
     const long cell = i >> 3;
     const int kb = (int)(cell / ldw), col = (int)(cell - (long)kb * ldw);
-    out[i] = to_bf16(pack_bf16_src(mode, W, kb, col, e, Cout, Ctot, KK, m, hid));
+    out[((long)pack_limb_row(kb, limb) * ldw + col) * 8 + e] = pack_cvt(pack_bf16_src(mode, W, kb, col, e, Cout, Ctot, KK, m, hid), limb);
   }
 }
 
@@ -142,7 +154,7 @@ __global__ void pack_bf16_kernel(int mode, const float* __restrict__ W, unsigned
 // column the chunk's KK * CKB source weights are one contiguous run of the reference weight, read with the lanes running along
 // it, converted, parked in LDS in cell order and written out as full 1 KB rows.  Data gradient (PACK_BF16_DGRAD): 16 cell rows x 64
 // columns per block; the lanes run along the columns (= the reference weight's input channels), reads and writes coalesce.
-__device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, unsigned short* lds16) {
+__device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, unsigned short* lds16, const int limb = -1) {
   SegMap m;
   m.n = j.nseg;
 #pragma unroll
@@ -151,7 +163,8 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
   const int nct = j.ldw / 64;
   const int c0 = (tb % nct) * 64;
   unsigned short* out = (unsigned short*)j.out;
-  if (j.imode == PACK_BF16_FWD) {
+  const int nkb = limb < 0 ? j.krows : j.krows / 3;      // cell rows of one limb
+  if (j.imode == PACK_BF16_FWD || j.imode == PACK_LIMB_FWD) {
     const int R = KK * NCB;                          // cell rows of one chunk (18 or 8)
     const int q = tb / nct;
     const int run = KK * CKB;                        // source floats per column
@@ -171,19 +184,19 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
       for (int u = 0; u < 4; ++u) v[u] = j.W[src[u] < 0 ? 0 : src[u]];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (dst[u] >= 0) lds16[dst[u]] = to_bf16(src[u] < 0 ? 0.f : v[u]);
+        if (dst[u] >= 0) lds16[dst[u]] = pack_cvt(src[u] < 0 ? 0.f : v[u], limb);
     }
     __syncthreads();
     const u32x4* src = (const u32x4*)lds16;
     for (int i = threadIdx.x; i < R * 64; i += 256) {
       const int rr = i >> 6, cl = i & 63;
-      *(u32x4*)(out + ((long)(q * R + rr) * j.ldw + c0 + cl) * 8) = src[i];
+      *(u32x4*)(out + ((long)pack_limb_row(q * R + rr, limb) * j.ldw + c0 + cl) * 8) = src[i];
     }
   } else {
     const int r0 = (tb / nct) * 16;
     for (int i = threadIdx.x; i < 16 * 64; i += 256) {
       const int rr = i >> 6, cl = i & 63;
-      if (r0 + rr >= j.krows) continue;
+      if (r0 + rr >= nkb) continue;
       int src[8];
       float f[8];
 #pragma unroll
@@ -193,11 +206,11 @@ __device__ __forceinline__ void pack_tile_bf16(const rsis_pack_job& j, int tb, u
       unsigned v[4];
 #pragma unroll
       for (int e2 = 0; e2 < 4; ++e2) {
-        const unsigned lo = to_bf16(src[2 * e2] < 0 ? 0.f : f[2 * e2]), hi = to_bf16(src[2 * e2 + 1] < 0 ? 0.f : f[2 * e2 + 1]);
+        const unsigned lo = pack_cvt(src[2 * e2] < 0 ? 0.f : f[2 * e2], limb), hi = pack_cvt(src[2 * e2 + 1] < 0 ? 0.f : f[2 * e2 + 1], limb);
         v[e2] = lo | (hi << 16);
       }
       const u32x4 cell = {v[0], v[1], v[2], v[3]};
-      *(u32x4*)(out + ((long)(r0 + rr) * j.ldw + c0 + cl) * 8) = cell;
+      *(u32x4*)(out + ((long)pack_limb_row(r0 + rr, limb) * j.ldw + c0 + cl) * 8) = cell;
     }
   }
 }
@@ -350,7 +363,13 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const rsis_pack_job* __
       next_begin = lo + 1 < njobs ? jobs[lo + 1].block_begin : total_tiles;
     }
     const int tb = b - j.block_begin;
-    if (j.imode >= PACK_WINO_FWD) {
+    if (j.imode >= PACK_LIMB_FWD) {
+      for (int l = 0; l < 3; ++l) {         // one pass per limb over the same tile of the reference weight (the re-reads hit L2)
+        pack_tile_bf16(j, tb, (unsigned short*)&tile[0][0], l);
+        if (l < 2) __syncthreads();
+      }
+    }
+    else if (j.imode >= PACK_WINO_FWD) {
       SegMap wm;
       wm.n = j.nseg;
 #pragma unroll
@@ -370,6 +389,8 @@ int rsis_l_pack_batch(const rsis_pack_job* jobs, int njobs, int total_blocks, hi
   return rsis_check_launch();
 }
 int rsis_l_pack_blocks(PackMode mode, int krows, int ldw, int ks) {
+  if (mode == PACK_LIMB_FWD) return rsis_l_pack_blocks(PACK_BF16_FWD, krows / 3, ldw, ks);           // (the blocks of ONE limb: a block writes all three)
+  if (mode == PACK_LIMB_DGRAD) return rsis_l_pack_blocks(PACK_BF16_DGRAD, krows / 3, ldw, ks);
   if (mode >= PACK_WINO_FWD) return krows;                              // Winograd copies: krows carries the number of (ot, q) blocks
   if (mode == PACK_BF16_FWD) return krows / (ks * ks * (bf16_ckb(ks * ks) / 8)) * (ldw / 64);     // one chunk x 64 columns per block
   if (mode == PACK_BF16_DGRAD) return (krows + 15) / 16 * (ldw / 64);
@@ -391,13 +412,22 @@ int rsis_l_pack(PackMode mode, const float* W, void* out, int Cout, int Ctot, in
   for (int s = 0; s < nseg; ++s) { m.C[s] = Cseg[s]; m.off[s] = Coff ? Coff[s] : base; base += Cseg[s]; }
   const long total = (long)krows * ldw;
   const dim3 g(pack_grid(total)), b(256);
+  if (mode >= PACK_LIMB_FWD) {      // limb copies: the bf16 cell kernel once per limb; krows = 3 x the cell rows of one limb
+    const int nkb = krows / 3;
+    for (int l = 0; l < 3; ++l) {
+      hipLaunchKernelGGL(pack_bf16_kernel, dim3(pack_grid((long)nkb * ldw * 8)), b, 0, st, mode == PACK_LIMB_FWD ? PACK_BF16_FWD : PACK_BF16_DGRAD, W,
+                         (unsigned short*)out, Cout, Ctot, ks * ks, m, ldw, nkb, hid, l);
+      if (rsis_check_launch() != RSIS_OK) return RSIS_ERR_LAUNCH;
+    }
+    return RSIS_OK;
+  }
   if (mode >= PACK_WINO_FWD) {      // Winograd copies (one source covering every input channel; krows = (ot, q) blocks)
     hipLaunchKernelGGL(pack_wino_kernel, dim3(krows), b, 0, st, mode, W, (float*)out, Cout, Ctot, m, hid);
     return rsis_check_launch();
   }
   if (mode >= PACK_BF16_FWD) {     // bf16 cell layouts: krows = cell rows, out = bf16
     hipLaunchKernelGGL(pack_bf16_kernel, dim3(pack_grid(total * 8)), b, 0, st, mode, W, (unsigned short*)out, Cout, Ctot, ks * ks, m, ldw,
-                       krows, hid);
+                       krows, hid, -1);
     return rsis_check_launch();
   }
   hipLaunchKernelGGL(pack_kernel, g, b, 0, st, mode, W, (float*)out, Cout, Ctot, ks * ks, m, ldw, krows, hid);

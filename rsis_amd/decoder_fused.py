@@ -104,7 +104,28 @@ def _packs(cell, c_up, c_skip):
     return cell._packs[key]
 
 
-def dyn_dgrad_pack(cell, c_up, c_skip, H, W):
+def _limb_pack(cell, dyn, what):
+    """the DTYPE_F32_LIMB copy set of a dynamic gate pack (same segments), one per direction"""
+    key = ("fused-limb", what) + tuple(dyn.segs)
+    if key not in cell._packs:
+        cell._packs[key] = ops.PackedConv(3, list(dyn.segs), lstm_hid=cell.hidden_size, stride=1, pad=1, offs=list(dyn.offs), dtype=ops.DTYPE_F32_LIMB)
+    return cell._packs[key]
+
+
+def _limb_ok(cell, dyn):
+    return dyn.dtype == ops.DTYPE_F32 and cell.kernel_size == 3 and cell.padding == 1 and all(s % 8 == 0 for s in dyn.segs)
+
+
+def dyn_fwd_pack(cell, c_up, c_skip, level, training):
+    """The copy set the gate conv's TRAINING forward reads: the limb copy where ops.limb_class("f<level>") routes the level to the limb
+    kernel (fp32, 3x3, sources in multiples of 8 channels), otherwise -- and for every inference call -- the dynamic pack itself."""
+    _hoist, dyn = _packs(cell, c_up, c_skip)
+    if not training or level is None or not ops.limb_class("f%d" % level) or not _limb_ok(cell, dyn):
+        return dyn
+    return _limb_pack(cell, dyn, "fwd")
+
+
+def dyn_dgrad_pack(cell, c_up, c_skip, H, W, level=None):
     """The copy set the gate conv's DATA GRADIENT (d(up) | dh_prev, explicit BPTT of decoder_seq) reads: under fp32, on levels whose
     sources are 32-channel multiples and whose map holds at least 12 x 12 pixels, a Winograd F(2x2, 3x3) copy (ops.DTYPE_F32_WINO,
     RSIS_WINOGRAD_GATES, default on: the 16 x 16 and 32 x 32 levels at 256 x 256 input, hidden 128) -- otherwise the dynamic pack itself.
@@ -113,6 +134,9 @@ def dyn_dgrad_pack(cell, c_up, c_skip, H, W):
     hid = cell.hidden_size
     if (dyn.dtype != ops.DTYPE_F32 or not ops.WINOGRAD_GATES[0] or cell.kernel_size != 3 or cell.padding != 1 or min(H, W) < 12
             or (c_up + hid) % 32 or c_up % 32 or c_up == 0 or (4 * hid) % 32):
+        # ... or, where ops.limb_class("d<level>") says so, the limb copy (the rows of dy, 4 hid, are a multiple of 8 from hid = 2 on)
+        if level is not None and ops.limb_class("d%d" % level) and _limb_ok(cell, dyn) and (4 * hid) % 8 == 0:
+            return _limb_pack(cell, dyn, "dgrad")
         return dyn
     key = ("fused-dgrad-wino", c_up, c_skip)
     if key not in cell._packs:

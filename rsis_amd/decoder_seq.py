@@ -122,7 +122,7 @@ def blk_supported(decoder, skip_feats):
 
 
 class _Level(object):
-    __slots__ = ("cell", "hid", "c_up", "c_skip", "H", "W", "hoist", "dyn", "G", "Hs", "Cs", "ACT", "UP", "KEY", "SIDE", "ARG", "skip")
+    __slots__ = ("cell", "hid", "c_up", "c_skip", "H", "W", "hoist", "dyn", "fwd_pack", "G", "Hs", "Cs", "ACT", "UP", "KEY", "SIDE", "ARG", "skip")
 
 
 UPCONV = [os.environ.get("RSIS_UPCONV", "1") != "0"]       # the last level's upsample + conv_out as one op per direction (upconv_out.hip)
@@ -246,7 +246,7 @@ class _Nchw(_Layout):
             (j.B, j.H, j.W, j.Wp, j.bias_packed, j.addend, j.c_prev, j.h_out, j.c_out, j.act_out, j.hid, j.ks, j.pad, j.tile, j.dtype,
              j.side_key) = (self.B, lv.H, lv.W, wps[i].data_ptr(), None, lv.G.data_ptr(), lv.Cs[t - 1].data_ptr() if t > 0 else None,
                             lv.Hs[t].data_ptr(), lv.Cs[t].data_ptr(), lv.ACT[t].data_ptr() if lv.ACT is not None else None, lv.hid, 3, 1,
-                            ops.FORCE_TILE[0], lv.dyn.dtype, lv.KEY[t].data_ptr())
+                            ops.FORCE_TILE[0], lv.fwd_pack.dtype, lv.KEY[t].data_ptr())
         check(self.L.rsis_convlstm_fwd_batch(jobs, len(cells), stream()), "rsis_convlstm_fwd_batch")
 
     def up(self, levels, cells, s2=None):
@@ -525,7 +525,9 @@ class _DecoderSeqFn(torch.autograd.Function):
         UP5 = None if upc else lay.empty((T, B), last.hid, H5, W5)            # model.py:163-164, all timesteps
         probs_tb = torch.empty((T, B, Wc.shape[0]), **f32)
         stop_tb = torch.empty((T, B, 1), **f32)
-        wps = [lv.dyn.fwd(w) for lv, w in zip(levels, gates_w)]
+        for i, lv in enumerate(levels):          # (the limb copy where the routing puts the level's training forward on the limb kernel)
+            lv.fwd_pack = decoder_fused.dyn_fwd_pack(lv.cell, lv.c_up, lv.c_skip, i, need_grad and not lay.blk)
+        wps = [lv.fwd_pack.fwd(w) for lv, w in zip(levels, gates_w)]
         for d in range(T + n - 1):
             cells = _diagonal(d, n, T)
             lay.gates(levels, cells, wps)
@@ -638,7 +640,7 @@ class _DecoderSeqFn(torch.autograd.Function):
         DHP = [lay.empty((B,), lv.hid, lv.H, lv.W) for lv in levels]                 # ... through the recurrence, from step t + 1
         DC = [[torch.empty((B, lv.hid, lv.H, lv.W), **f32) for _ in range(2)] for lv in levels]
         DUP = [lay.empty((B,), lv.c_up, lv.H, lv.W) if lv.c_up > 0 else None for lv in levels]
-        dpk = [decoder_fused.dyn_dgrad_pack(lv.cell, lv.c_up, lv.c_skip, lv.H, lv.W) for lv in levels]
+        dpk = [decoder_fused.dyn_dgrad_pack(lv.cell, lv.c_up, lv.c_skip, lv.H, lv.W, level=i) for i, lv in enumerate(levels)]
         wds = [pk.dgrad(w) for pk, w in zip(dpk, gates_w)]
         # gradients a caller put on the returned final state (none in runIter: train.py never reads it)
         d_hidden = d_hidden or (None,) * (2 * n)

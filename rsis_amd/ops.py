@@ -38,6 +38,7 @@ def _direct_target(param):
 # arithmetic of the MFMA conv kernels (include/rsis_hip.h RSIS_DTYPE_*); a property of each PackedConv, set from `-dtype`
 DTYPE_F32, DTYPE_BF16 = 0, 1
 DTYPE_F32_WINO = 3      # include/rsis_hip.h RSIS_DTYPE_F32_WINO: exact-f32 arithmetic, eligible 3x3 convs as Winograd F(2x2, 3x3)
+DTYPE_F32_LIMB = 4      # include/rsis_hip.h RSIS_DTYPE_F32_LIMB: fp32 operands as three bf16 limbs each, training calls of eligible 3x3 convs
 
 
 def _wino_rule():
@@ -55,6 +56,31 @@ def _wino_rule():
 
 
 WINOGRAD = [_wino_rule()]
+
+# the classes of the fp32 step whose training-call 3x3 convs run the limb flavour of the direct kernel (csrc/conv3x3_limb.h,
+# DTYPE_F32_LIMB).  A class is a decoder level, forward and gradient separately: "f<i>" = the gate forward of ConvLSTM level i (i = 0 the
+# coarsest map), "d<i>" = its gate data gradient where the Winograd rule does not take it.  RSIS_CONV_LIMBS: "0" = none (every conv on the
+# f32 MFMA, the routing before the limb kernel existed), "all" = every class, or a comma list of classes.  The default is what measured
+# faster inside a replayed 256 x 256 / T = 10 / B = 32 step (NOTES.md (95)).
+LIMB_DEFAULT = "f1,f2,f3,f4,d3,d4"
+
+
+def _limb_rule():
+    v = os.environ.get("RSIS_CONV_LIMBS", LIMB_DEFAULT).strip().lower()
+    if v in ("0", "", "off", "none"):
+        return frozenset()
+    if v == "all":
+        return "all"
+    return frozenset(t.strip() for t in v.split(",") if t.strip())
+
+
+LIMBS = [_limb_rule()]
+
+
+def limb_class(name):
+    """does the routing put class `name` ("f2", "d4", ...) on the limb kernel?"""
+    rule = LIMBS[0]
+    return rule == "all" or name in rule
 # Winograd also on the inference / parity path (no_grad calls: test(), eval.py)?  Default off: those calls keep the direct kernel with
 # segmented accumulation, bit for bit what they computed before the Winograd kernel existed.  Measured with it on (round 6): every
 # e2e golden still within 1e-4 of the reference, but on the HOT fixture (e2e_256_hot: |logit| to 5.5, half the gates saturated) the
@@ -121,7 +147,7 @@ def repack_all():
             todo.append((p, w, b, p.wd, 1))
     if not todo:
         return
-    sig = tuple((id(p), w.data_ptr(), out.data_ptr(), d) for p, w, _b, out, d in todo)
+    sig = tuple(p._job_sig(w, out, d) for p, w, _b, out, d in todo)
     if _BATCH["sig"] != sig:                       # (re)build the device-side job table: pointers are stable across steps
         jobs = (_lib.PackJob * len(todo))()
         blocks = 0
@@ -208,6 +234,13 @@ class PackedConv(object):
             j.Coff[i] = self.offs[i] if self.offs is not None else off
             off += c
         return j
+
+    def _job_sig(self, w, out, dgrad):
+        """everything _job() puts into a pack job, as a tuple: repack_all() keeps its device-side job table while these stay the same.
+        (Not id(self) and the two addresses alone: a PackedConv created after another was freed can get its id AND the addresses of its
+        weight and its copy from the allocator's free lists, with another geometry -- the table of the dead one then packed the new one.)"""
+        return (w.data_ptr(), out.data_ptr(), int(dgrad), self.dtype, tuple(w.shape), self.ks, self.stride, self.pad, tuple(self.segs),
+                tuple(self.offs) if self.offs is not None else None, self.lstm_hid)
 
     def _seg_args(self):
         return len(self.segs), int_array(self.segs), (int_array(self.offs) if self.offs is not None else None)
