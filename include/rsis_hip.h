@@ -250,6 +250,19 @@ int rsis_upsample_maxpool_scaled_bwd(const float* dy, const float* dpool, const 
 int rsis_global_maxpool_scaled_bwd_add(const float* dy, const int* argmax, const float* scale, float* dx, long BC, int HW, void* stream);
 int rsis_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, void* stream);
 
+/* ---- `-skip_mode mul` (model.py:156): level i >= 1 consumes resize(h[i-1]) * skip[i].
+ *   rsis_upsample_bilinear_ac_mul_fwd : y = resize(x) * m, m [BC][Ho][Wo]: interpolated in fp32 as rsis_upsample_bilinear_ac_fwd does on
+ *                                       the same launch paths, then ONE fp32 product per element.  Equal sizes: y = x * m.
+ *   rsis_upsample_mul_bwd_prep        : the backward's preparation, one launch at the fine resolution.  With u = resize(x) recomputed
+ *                                       (the unscaled forward's bits),
+ *                                           dm[e] = accumulate ? fmaf(dy[e], u[e], dm[e]) : dy[e] * u[e]     (accumulate: 0 or 1)
+ *                                           dy[e] = dy[e] * m[e]                                             (in place)
+ *                                       after which rsis_upsample_maxpool_bwd / rsis_upsample_bilinear_ac_bwd run unchanged on dy.
+ * Wo % 4 == 0: y, m, dy and dm must be 16-byte aligned. ---- */
+int rsis_upsample_bilinear_ac_mul_fwd(const float* x, const float* m, float* y, long BC, int Hi, int Wi, int Ho, int Wo, void* stream);
+int rsis_upsample_mul_bwd_prep(float* dy, const float* x, const float* m, float* dm, long BC, int Hi, int Wi, int Ho, int Wo, int accumulate,
+                               void* stream);
+
 /* The mask generator: ONE launch fills the three scale arrays of a whole sequence, n floats each,
  *   array 0 = s2 (Dropout2d, rate p2), array 1 = mc (class head, rate pc), array 2 = ms (stop head, rate ps),
  * all in the layout of the decoder's pooled side features: level after level, each [T][B][hid_i] (n = T * B * sum hid_i).
@@ -730,6 +743,28 @@ typedef struct rsis_blk_resize_scaled_job {
 } rsis_blk_resize_scaled_job;
 int rsis_blk_upsample_fwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream);
 int rsis_blk_upsample_bwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, int njobs, void* stream);
+
+/* `-skip_mode mul` on blk tensors.  Forward: y = resize(x) * mul, mul a blk tensor of y's shape; blend and product in fp32, ONE rounding
+ * to bf16 at the store. */
+typedef struct rsis_blk_resize_mul_job {
+  const void* src;
+  void* dst;
+  int B, C, Hi, Wi, Ho, Wo;
+  const void* mul;
+} rsis_blk_resize_mul_job;
+int rsis_blk_upsample_mul_fwd_batch(const rsis_blk_resize_mul_job* jobs, int njobs, void* stream);
+/* Backward preparation at the fine resolution, in front of rsis_blk_upsample_bwd_batch.  With u = resize(x) as rsis_blk_upsample_fwd_batch
+ * stores it (rounded to bf16):  dm = accumulate ? fmaf(dy, u, dm) : dy * u  into the fp32 NCHW accumulator dm [B][C][Ho][Wo] (the caller
+ * rounds it to bf16 once, after the last step), then dy <- dy * m in place with one rounding. */
+typedef struct rsis_blk_mul_prep_job {
+  void* dy;              /* blk [B][C][Ho][Wo], read and overwritten */
+  const void* x;         /* blk [B][C][Hi][Wi] */
+  const void* m;         /* blk [B][C][Ho][Wo] */
+  float* dm;
+  int B, C, Hi, Wi, Ho, Wo;
+  int accumulate;        /* 0 = store, 1 = add */
+} rsis_blk_mul_prep_job;
+int rsis_blk_upsample_mul_bwd_prep_batch(const rsis_blk_mul_prep_job* jobs, int njobs, void* stream);
 
 /* rsis_convlstm_bwd_gates on blk tensors: dh, dh2 (may be NULL) blk [B][hid]; act, da blk [B][4 hid] (rows 4 j + gate); c, c_prev,
  * dc_next, dc_prev fp32 [B][hid][HW] (c_prev / dc_next / dc_prev may be NULL). */

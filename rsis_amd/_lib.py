@@ -73,6 +73,18 @@ class BlkResizeScaledJob(ctypes.Structure):
     _fields_ = BlkResizeJob._fields_ + [("scale", ctypes.c_void_p)]
 
 
+class BlkResizeMulJob(ctypes.Structure):
+    """struct rsis_blk_resize_mul_job of include/rsis_hip.h"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + [(k, ctypes.c_int) for k in ("B", "C", "Hi", "Wi", "Ho", "Wo")] + \
+               [("mul", ctypes.c_void_p)]
+
+
+class BlkMulPrepJob(ctypes.Structure):
+    """struct rsis_blk_mul_prep_job of include/rsis_hip.h"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("dy", "x", "m", "dm")] + \
+               [(k, ctypes.c_int) for k in ("B", "C", "Hi", "Wi", "Ho", "Wo", "accumulate")]
+
+
 class BlkLstmBwdJob(ctypes.Structure):
     """struct rsis_blk_lstm_bwd_job of include/rsis_hip.h"""
     _fields_ = [(k, ctypes.c_void_p) for k in ("dh", "dh2", "dc_next", "act", "c_prev", "c", "da", "dc_prev")] + \
@@ -200,6 +212,10 @@ SIGNATURES = {
     "rsis_dropout_scales": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _vp]),
     "rsis_dropout_heads_mask": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rsis_dropout_heads_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rsis_upsample_bilinear_ac_mul_fwd": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
+    "rsis_upsample_mul_bwd_prep": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "rsis_blk_upsample_mul_fwd_batch": (_i, [ctypes.POINTER(BlkResizeMulJob), _i, _vp]),
+    "rsis_blk_upsample_mul_bwd_prep_batch": (_i, [ctypes.POINTER(BlkMulPrepJob), _i, _vp]),
     "rsis_blk_upsample_fwd_scaled_batch": (_i, [ctypes.POINTER(BlkResizeScaledJob), _i, _vp]),
     "rsis_blk_upsample_bwd_scaled_batch": (_i, [ctypes.POINTER(BlkResizeScaledJob), _i, _vp]),
 }

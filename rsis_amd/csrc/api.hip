@@ -617,6 +617,18 @@ int rsis_upsample_bilinear_ac_scaled_fwd(const float* x, const float* scale, flo
   if (scale && Hi == Ho && Wi == Wo) return rsis_l_scale_planes(x, scale, y, BC, Hi * Wi, (hipStream_t)stream);
   return rsis_l_upsample_fwd(x, y, BC, Hi, Wi, Ho, Wo, scale, (hipStream_t)stream);
 }
+// y = resize(x) * m, m of y's shape (`-skip_mode mul`); the float4 paths read m as they write y: both 16-byte aligned when Wo % 4 == 0
+int rsis_upsample_bilinear_ac_mul_fwd(const float* x, const float* m, float* y, long BC, int Hi, int Wi, int Ho, int Wo, void* stream) {
+  if (!x || !m || !y || BC < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return RSIS_ERR_ARG;
+  if (Wo % 4 == 0 && (((size_t)m | (size_t)y) & 15)) return RSIS_ERR_ARG;
+  return rsis_l_upsample_fwd(x, y, BC, Hi, Wi, Ho, Wo, nullptr, (hipStream_t)stream, m);
+}
+int rsis_upsample_mul_bwd_prep(float* dy, const float* x, const float* m, float* dm, long BC, int Hi, int Wi, int Ho, int Wo, int accumulate,
+                               void* stream) {
+  if (!dy || !x || !m || !dm || BC < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || (accumulate != 0 && accumulate != 1)) return RSIS_ERR_ARG;
+  if (Wo % 4 == 0 && (((size_t)dy | (size_t)m | (size_t)dm) & 15)) return RSIS_ERR_ARG;
+  return rsis_l_upsample_mul_bwd_prep(dy, x, m, dm, BC, Hi, Wi, Ho, Wo, accumulate, (hipStream_t)stream);
+}
 int rsis_upsample_maxpool_scaled_bwd(const float* dy, const float* dpool, const int* argmax, const float* scale, float* dx, long BC, int Hi, int Wi,
                                      int Ho, int Wo, void* stream) {
   if (!dy || !dx || !dpool || !argmax || BC < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return RSIS_ERR_ARG;
@@ -1113,6 +1125,33 @@ int rsis_blk_upsample_bwd_scaled_batch(const rsis_blk_resize_scaled_job* jobs, i
   BlkResizeScaledJob a[64];
   const int rc = blk_resize_scaled_jobs(jobs, njobs, a, true);
   return rc ? rc : rsis_l_blk_upsample_bwd_scaled(a, njobs, (hipStream_t)stream);
+}
+// (the checks of blk_resize_jobs, job by job; the multiplier rides along)
+int rsis_blk_upsample_mul_fwd_batch(const rsis_blk_resize_mul_job* jobs, int njobs, void* stream) {
+  if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;
+  BlkResizeMulJob a[64];
+  for (int j = 0; j < njobs; ++j) {
+    const rsis_blk_resize_mul_job& q = jobs[j];
+    if (!q.mul) return RSIS_ERR_ARG;
+    const rsis_blk_resize_job plain = {q.src, q.dst, nullptr, nullptr, q.B, q.C, q.Hi, q.Wi, q.Ho, q.Wo};
+    const int rc = blk_resize_jobs(&plain, 1, &a[j], false);
+    if (rc) return rc;
+    a[j].mul = q.mul;
+  }
+  return rsis_l_blk_upsample_mul_fwd(a, njobs, (hipStream_t)stream);
+}
+int rsis_blk_upsample_mul_bwd_prep_batch(const rsis_blk_mul_prep_job* jobs, int njobs, void* stream) {
+  if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;
+  BlkMulPrepJob a[64];
+  for (int j = 0; j < njobs; ++j) {
+    const rsis_blk_mul_prep_job& q = jobs[j];
+    if (!q.dy || !q.x || !q.m || !q.dm || q.B < 1 || q.C < 8 || (q.C & 7) || q.Hi < 1 || q.Wi < 1 || q.Ho < 1 || q.Wo < 1) return RSIS_ERR_ARG;
+    if (q.accumulate != 0 && q.accumulate != 1) return RSIS_ERR_ARG;
+    if ((long)q.Hi * q.Wi >= (1L << 27) || (long)q.Ho * q.Wo >= (1L << 27)) return RSIS_ERR_UNSUPPORTED;
+    a[j].dy = q.dy; a[j].x = q.x; a[j].m = q.m; a[j].dm = q.dm; a[j].planes = q.B * (q.C >> 3);
+    a[j].Hi = q.Hi; a[j].Wi = q.Wi; a[j].Ho = q.Ho; a[j].Wo = q.Wo; a[j].accumulate = q.accumulate;
+  }
+  return rsis_l_blk_upsample_mul_bwd_prep(a, njobs, (hipStream_t)stream);
 }
 int rsis_blk_lstm_bwd_batch(const rsis_blk_lstm_bwd_job* jobs, int njobs, void* stream) {
   if (!jobs || njobs < 1 || njobs > 64) return RSIS_ERR_ARG;

@@ -43,12 +43,9 @@ __device__ __forceinline__ void blk_scale_cell(const J& p, long pl, float v[8]) 
   }
 }
 
+// the fp32 blend of output cell `loc` of a resize job (any job type derived from BlkResizeJob's geometry); returns the cell plane
 template <typename J>
-__global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGroup<J> g) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= g.begin[g.n]) return;
-  long loc;
-  const J& p = g.job[kd_find(g, e, loc)];
+__device__ __forceinline__ long blk_resize_cell(const J& p, const void* src, long loc, float (&o)[8]) {
   const int Hi = p.Hi, Wi = p.Wi, Ho = p.Ho, Wo = p.Wo;
   const int wo = (int)(loc % Wo);
   const long t = loc / Wo;
@@ -58,8 +55,8 @@ __global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGro
   int h0, h1, w0, w1; float lh, lw;
   ac_coord(ho, sh, Hi, h0, h1, lh);
   ac_coord(wo, sw, Wi, w0, w1, lw);
-  const u32x4* xb = (const u32x4*)p.src + pl * Hi * Wi;
-  float v00[8], v01[8], v10[8], v11[8], o[8];
+  const u32x4* xb = (const u32x4*)src + pl * Hi * Wi;
+  float v00[8], v01[8], v10[8], v11[8];
   blk_cell_unpack(xb[h0 * Wi + w0], v00); blk_cell_unpack(xb[h0 * Wi + w1], v01);
   blk_cell_unpack(xb[h1 * Wi + w0], v10); blk_cell_unpack(xb[h1 * Wi + w1], v11);
 #pragma unroll
@@ -70,8 +67,51 @@ __global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGro
     const float top = __builtin_fmaf(1.f - lw, v00[k], lw * v01[k]), bot = __builtin_fmaf(1.f - lw, v10[k], lw * v11[k]);
     o[k] = __builtin_fmaf(1.f - lh, top, lh * bot);
   }
+  return pl;
+}
+
+// J = BlkResizeMulJob: the cell is multiplied, channel by channel, with the cell of p.mul at the same place (one fp32 product behind the
+// blend, then the one rounding of the store)
+template <typename J>
+__global__ __launch_bounds__(256) void blk_upsample_fwd_group_kernel(const KdGroup<J> g) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= g.begin[g.n]) return;
+  long loc;
+  const J& p = g.job[kd_find(g, e, loc)];
+  float o[8];
+  const long pl = blk_resize_cell(p, p.src, loc, o);
   blk_scale_cell(p, pl, o);
+  if constexpr (std::is_same<J, BlkResizeMulJob>::value) {
+    float m[8];
+    blk_cell_unpack(((const u32x4*)p.mul)[loc], m);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] *= m[k];
+  }
   ((u32x4*)p.dst)[loc] = blk_cell_pack(o);
+}
+
+// backward preparation of y = resize(x) * m (BlkMulPrepJob, common.h): one thread = one cell of dy at the fine resolution.  u = the blend
+// above rounded to bf16 -- the cell the unscaled forward stores -- then, per channel, dm = accumulate ? fmaf(dy, u, dm) : dy * u in the
+// fp32 NCHW accumulator (rounded to bf16 by the caller once, after the last step) and dy <- dy * m with one rounding.  A cell is read
+// and written by one thread; the jobs of a launch are cells of different levels: no atomics.
+__global__ __launch_bounds__(256) void blk_upsample_mul_prep_group_kernel(const KdGroup<BlkMulPrepJob> g) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= g.begin[g.n]) return;
+  long loc;
+  const BlkMulPrepJob& p = g.job[kd_find(g, e, loc)];
+  float u[8], dy[8], m[8];
+  const long pl = blk_resize_cell(p, p.x, loc, u);
+  blk_cell_unpack(blk_cell_pack(u), u);
+  blk_cell_unpack(((const u32x4*)p.dy)[loc], dy);
+  blk_cell_unpack(((const u32x4*)p.m)[loc], m);
+  const long HWo = (long)p.Ho * p.Wo;
+  float* dm = p.dm + pl * 8 * HWo + (loc - pl * HWo);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    dm[k * HWo] = p.accumulate ? __builtin_fmaf(dy[k], u[k], dm[k * HWo]) : dy[k] * u[k];
+    dy[k] *= m[k];
+  }
+  ((u32x4*)p.dy)[loc] = blk_cell_pack(dy);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -246,6 +286,18 @@ int rsis_l_blk_upsample_fwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStr
   if (kd_unscaled(jobs, n, plain)) return rsis_l_blk_upsample_fwd(plain, n, st);
   for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Ho * jobs[j].Wo;
   return kd_launch(blk_upsample_fwd_group_kernel<BlkResizeScaledJob>, jobs, cells, n, st);
+}
+int rsis_l_blk_upsample_mul_fwd(const BlkResizeMulJob* jobs, int n, hipStream_t st) {
+  long cells[64];
+  if (n > 64) return RSIS_ERR_ARG;
+  for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Ho * jobs[j].Wo;
+  return kd_launch(blk_upsample_fwd_group_kernel<BlkResizeMulJob>, jobs, cells, n, st);
+}
+int rsis_l_blk_upsample_mul_bwd_prep(const BlkMulPrepJob* jobs, int n, hipStream_t st) {
+  long cells[64];
+  if (n > 64) return RSIS_ERR_ARG;
+  for (int j = 0; j < n; ++j) cells[j] = (long)jobs[j].planes * jobs[j].Ho * jobs[j].Wo;
+  return kd_launch(blk_upsample_mul_prep_group_kernel, jobs, cells, n, st);
 }
 int rsis_l_blk_upsample_bwd(const BlkResizeJob* jobs, int n, hipStream_t st) {
   long cells[64];

@@ -265,6 +265,21 @@ struct BlkResizeJob {
 struct BlkResizeScaledJob : BlkResizeJob {
   const float* scale;
 };
+// ... or multiplied element by element with a blk tensor of the result's shape (forward only): y = resize(x) * mul, the level input of
+// `-skip_mode mul` (model.py:156), the product taken in fp32 before the one rounding of the store
+struct BlkResizeMulJob : BlkResizeJob {
+  const void* mul;       // [planes][Ho][Wo][8]
+};
+// backward preparation of y = resize(x) * m at the fine resolution: dm (+)= dy * u, then dy <- dy * m in place, where u = resize(x) as the
+// unscaled forward stores it (rounded to bf16).  dm is an fp32 NCHW accumulator [B][C][Ho][Wo] (plane 8 pl + k of cell plane pl)
+struct BlkMulPrepJob {
+  void* dy;              // [planes][Ho][Wo][8], read and overwritten
+  const void* x;         // [planes][Hi][Wi][8]
+  const void* m;         // [planes][Ho][Wo][8]
+  float* dm;
+  int planes, Hi, Wi, Ho, Wo;
+  int accumulate;        // 0: dm = dy * u; 1: dm = fmaf(dy, u, dm)
+};
 // ConvLSTM pointwise backward on blk tensors: dh / dh2 [B][hid/8][HW][8] (dh2 may be null), act / da [B][4 hid / 8][HW][8] (rows
 // 4 j + gate), c / c_prev / dc_next / dc_prev fp32 [B][hid][HW] (c_prev, dc_next, dc_prev may be null)
 struct BlkLstmBwdJob {

@@ -46,7 +46,10 @@ int rsis_l_lstm_bwd(const float* dh, const float* dh2, const float* dc_next, con
                     float* da_sum, int B, int hid, int HW, hipStream_t st);
 int rsis_l_lstm_bwd_group(const void* const* ptrs, const int* dims, int n, hipStream_t st);
 // (scale: [BC] factors of the planes of the result, null = none -- the kernels without the argument)
-int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st);
+int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st,
+                        const float* mul = nullptr);
+int rsis_l_upsample_mul_bwd_prep(float* dy, const float* x, const float* m, float* dm, long BC, int Hi, int Wi, int Ho, int Wo, int accumulate,
+                                 hipStream_t st);
 int rsis_l_upsample_bwd(const float* dy, float* dx, long BC, int Hi, int Wi, int Ho, int Wo, const float* pool_g, const int* pool_arg, const float* scale,
                         hipStream_t st);
 int rsis_l_scale_planes(const float* x, const float* scale, float* y, long BC, int HW, hipStream_t st);
@@ -78,6 +81,8 @@ int rsis_l_blk_upsample_fwd(const BlkResizeJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_upsample_bwd(const BlkResizeJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_upsample_fwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_upsample_bwd_scaled(const BlkResizeScaledJob* jobs, int n, hipStream_t st);
+int rsis_l_blk_upsample_mul_fwd(const BlkResizeMulJob* jobs, int n, hipStream_t st);
+int rsis_l_blk_upsample_mul_bwd_prep(const BlkMulPrepJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_lstm_bwd(const BlkLstmBwdJob* jobs, int n, hipStream_t st);
 int rsis_l_blk_sum_leading(const void* x, void* y, int T, long n, hipStream_t st);
 int rsis_l_blk_channel_sum(const void* dy, float* db, int B, int C, int HW, int hid, hipStream_t st);

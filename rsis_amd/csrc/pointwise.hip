@@ -123,10 +123,19 @@ __global__ __launch_bounds__(256) void lstm_bwd_group_v4_kernel(const LstmBwdGro
 // (ac_coord / ac_scale: common.h)
 
 // SC (every upsample / pool-backward kernel below): the result of plane bc is multiplied by scale[bc] (the decoder's Dropout2d scale,
-// model.py:141: interpolate in fp32, then scale); SC = false is the kernel without the argument.
-template <bool SC>
+// model.py:141: interpolate in fp32, then scale); SC = false is the kernel without the argument.  The forward kernels have a third
+// mode, SC = 2: `scale` is then a multiplier of the OUTPUT's shape (the skip feature of `-skip_mode mul`, model.py:156) and element e
+// of the result is multiplied by scale[e] -- the same blend, then one fp32 product.
+// The scalar kernel alone has SC = 3 / 4, the backward preparation of that product on maps the float4 kernels do not take (see
+// upsample_mul_bwd_prep_kernel): y is then dy, `scale` the multiplier m, and with o = the blend of this very loop
+//   dm[e] = dy[e] * o (SC = 3)  or  fmaf(dy[e], o, dm[e]) (SC = 4);      dy[e] <- dy[e] * m[e].
+// (The compiler unrolls the loop of SC = 0 .. 2 by two and rounds the blend of a thread's PAIRED trips with another contraction than
+// that of its last, odd trip; SC = 3 / 4 read what they write, are not unrolled and round every element as that last trip does.  Up to
+// 2^20 elements per launch every thread makes at most one trip and o has the bits the unscaled kernel stores; beyond, it may differ
+// from them in the last place for the elements of paired trips.)
+template <int SC>
 __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi, int Ho, int Wo,
-                                    float sh, float sw, long total, const float* __restrict__ scale) {
+                                    float sh, float sw, long total, const float* __restrict__ scale, float* __restrict__ dm) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int wo = (int)(e % Wo);
     const long t = e / Wo;
@@ -138,14 +147,20 @@ __global__ void upsample_fwd_kernel(const float* __restrict__ x, float* __restri
     const float* xb = x + bc * Hi * Wi;
     const float v00 = xb[h0 * Wi + w0], v01 = xb[h0 * Wi + w1], v10 = xb[h1 * Wi + w0], v11 = xb[h1 * Wi + w1];
     const float o = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
-    y[e] = SC ? o * scale[bc] : o;
+    if (SC >= 3) {
+      const float g = y[e];
+      dm[e] = SC == 4 ? __builtin_fmaf(g, o, dm[e]) : g * o;
+      y[e] = g * scale[e];
+    } else {
+      y[e] = SC == 2 ? o * scale[e] : (SC ? o * scale[bc] : o);
+    }
   }
 }
 
 // Wo % 4 == 0: one thread = 4 consecutive outputs of a row (float4 store).  A block covers 256 / (Wo/4) consecutive output
 // rows of the flattened (bc, ho) row space (or a 256-thread slice of one long row); the only division left is one per thread
 // (row -> bc, ho).  Same arithmetic per element as upsample_fwd_kernel (bit-identical results).
-template <bool SC>
+template <int SC>
 __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi,
                                                               int Ho, int Wo, float sh, float sw, long rows, int Wq, int wq_shift,
                                                               const float* __restrict__ scale) {
@@ -179,7 +194,11 @@ __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __res
     ac_coord(wq * 4 + k, sw, Wi, w0, w1, lw);
     o[k] = (1.f - lh) * ((1.f - lw) * r0[w0] + lw * r0[w1]) + lh * ((1.f - lw) * r1[w0] + lw * r1[w1]);
   }
-  if (SC) {
+  if (SC == 2) {
+    const f32x4 m = *reinterpret_cast<const f32x4*>(scale + ((size_t)row * Wq + wq) * 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] *= m[k];
+  } else if (SC) {
     const float s = scale[bc];
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] *= s;
@@ -192,7 +211,7 @@ __global__ __launch_bounds__(256) void upsample_fwd_v4_kernel(const float* __res
 // writes two float4s.  The v4 kernel issues 16 scalar loads per float4 of output and is bound by the vector-memory pipe
 // (34 us for the 8 x 256^2 x 32 level, a 67 MB write); this one is bound by the write.  Same arithmetic, bit-identical results.
 // Tile shapes: 16 x 128 outputs (512-byte output rows; <= 12 x 69 inputs) on maps at least 128 wide, 32 x 64 (<= 20 x 45) below.
-template <int UF_TOH, int UF_TOW, int UF_RH, int UF_RQ, bool SC = false>
+template <int UF_TOH, int UF_TOW, int UF_RH, int UF_RQ, int SC = 0>
 __global__ __launch_bounds__(256) void upsample_fwd_lds_kernel(const float* __restrict__ x, float* __restrict__ y, int Hi, int Wi,
                                                                int Ho, int Wo, float sh, float sw, int tiles_x, int tiles_y,
                                                                const float* __restrict__ scale) {
@@ -233,12 +252,57 @@ __global__ __launch_bounds__(256) void upsample_fwd_lds_kernel(const float* __re
       w1 -= wa;
       o[k] = (1.f - lh) * ((1.f - lw) * r0[w0] + lw * r0[w1]) + lh * ((1.f - lw) * r1[w0] + lw * r1[w1]);
     }
-    if (SC) {
+    if (SC == 2) {
+      const f32x4 m = *reinterpret_cast<const f32x4*>(scale + (bc * Ho + ho) * (size_t)Wo + wo);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] *= m[k];
+    } else if (SC) {
       const float s = scale[bc];
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[k] *= s;
     }
     *reinterpret_cast<f32x4*>(y + (bc * Ho + ho) * (size_t)Wo + wo) = o;
+  }
+}
+
+// the align-corners blend of the forward kernels above with the fused multiply-adds the compiler forms for their plain expression
+// written out, for kernels that must reproduce their bits behind further arithmetic (blk_dec.hip pins the same three)
+__device__ __forceinline__ float ac_blend(float lh, float lw, float v00, float v01, float v10, float v11) {
+  const float top = __builtin_fmaf(1.f - lw, v00, lw * v01), bot = __builtin_fmaf(1.f - lw, v10, lw * v11);
+  return __builtin_fmaf(1.f - lh, top, lh * bot);
+}
+// backward preparation of y = resize(x) * m (rsis_l_upsample_mul_bwd_prep) on rows of whole float4s (Wo % 4 == 0): dm (+)= dy * resize(x),
+// dy <- dy * m.  The accumulate form is fmaf(dy, u, dm): ONE rounding per step; the store form is the plain product.  One thread = four
+// consecutive elements of a row: 16-byte accesses of dy, m and dm; the taps of x are scalar gathers of a small tensor.  (Other maps:
+// SC = 3 / 4 of upsample_fwd_kernel.)
+template <bool ACC>
+__global__ __launch_bounds__(256) void upsample_mul_bwd_prep_kernel(float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ m,
+                                                                    float* __restrict__ dm, int Hi, int Wi, int Ho, int Wo, float sh, float sw,
+                                                                    long items) {
+  const int Wq = Wo / 4;
+  for (long it = blockIdx.x * (long)blockDim.x + threadIdx.x; it < items; it += (long)gridDim.x * blockDim.x) {
+    const int wq = (int)(it % Wq);
+    const long t = it / Wq;
+    const int ho = (int)(t % Ho);
+    const long bc = t / Ho;
+    int h0, h1; float lh;
+    ac_coord(ho, sh, Hi, h0, h1, lh);
+    const float* r0 = x + bc * Hi * Wi + (long)h0 * Wi;
+    const float* r1 = x + bc * Hi * Wi + (long)h1 * Wi;
+    const long e = it * 4;
+    const f32x4 g = *reinterpret_cast<const f32x4*>(dy + e), mv = *reinterpret_cast<const f32x4*>(m + e);
+    f32x4 d, o;
+    if (ACC) d = *reinterpret_cast<const f32x4*>(dm + e);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      int w0, w1; float lw;
+      ac_coord(wq * 4 + k, sw, Wi, w0, w1, lw);
+      const float u = ac_blend(lh, lw, r0[w0], r0[w1], r1[w0], r1[w1]);
+      d[k] = ACC ? __builtin_fmaf(g[k], u, d[k]) : g[k] * u;
+      o[k] = g[k] * mv[k];
+    }
+    *reinterpret_cast<f32x4*>(dm + e) = d;
+    *reinterpret_cast<f32x4*>(dy + e) = o;
   }
 }
 
@@ -1242,29 +1306,46 @@ template <typename F>
 static inline void sc_pick(const float* scale, F f) {
   if (scale) f(std::true_type{}); else f(std::false_type{});
 }
-int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st) {
+// ... and of a forward kernel with its third mode: f(integral_constant<int, 0 | 1 | 2>) = unscaled, per-plane scale, per-element multiplier
+template <typename F>
+static inline void sc_pick3(int mode, F f) {
+  if (mode == 2) f(std::integral_constant<int, 2>{});
+  else if (mode == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
+// mul (y's shape, may be null): y = resize(x) * mul element by element -- the same launch paths as the unscaled / scaled resize, `mul`
+// in the place of `scale` (the two exclude each other: api.hip)
+int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int Ho, int Wo, const float* scale, hipStream_t st, const float* mul) {
   const long total = BC * Ho * Wo;
+  const int mode = mul ? 2 : (scale ? 1 : 0);
+  if (mul) scale = mul;
   {
     // the LDS-tiled kernel needs its output tile to read at most RH x (RQ * 4 - 3) input pixels
     const float fh = ac_scale(Hi, Ho), fw = ac_scale(Wi, Wo);
     const bool al = Wo % 4 == 0 && Wi % 4 == 0;
     if (al && Ho >= 16 && Wo >= 128 && fh * 15 + 3.f <= 12 && fw * 127 + 6.f <= 72 && BC * ((Wo + 127) / 128) * ((Ho + 15) / 16) < (1L << 31)) {
       const int tiles_x = (Wo + 127) / 128, tiles_y = (Ho + 15) / 16;
-      if (!scale)
+      if (mode == 0)
         hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
                            Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
+      else if (mode == 1)
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18, 1>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+                           Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       else
-        hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18, true>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<16, 128, 12, 18, 2>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
                            Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       return rsis_check_launch();
     }
     if (al && Ho >= 32 && Wo >= 64 && fh * 31 + 3.f <= 20 && fw * 63 + 6.f <= 48 && BC * ((Wo + 63) / 64) * ((Ho + 31) / 32) < (1L << 31)) {
       const int tiles_x = (Wo + 63) / 64, tiles_y = (Ho + 31) / 32;
-      if (!scale)
+      if (mode == 0)
         hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y, Hi,
                            Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
+      else if (mode == 1)
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12, 1>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+                           Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       else
-        hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12, true>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
+        hipLaunchKernelGGL((upsample_fwd_lds_kernel<32, 64, 20, 12, 2>), dim3((unsigned)(BC * tiles_x * tiles_y)), dim3(256), 0, st, x, y,
                            Hi, Wi, Ho, Wo, fh, fw, tiles_x, tiles_y, scale);
       return rsis_check_launch();
     }
@@ -1277,15 +1358,36 @@ int rsis_l_upsample_fwd(const float* x, float* y, long BC, int Hi, int Wi, int H
     if (shift < 0 && Wq <= 256) shift = -2;
     const dim3 grid = shift >= 0 ? dim3((unsigned)((rows + (256 >> shift) - 1) / (256 >> shift)))
                                  : (shift == -2 ? dim3((unsigned)((rows * Wq + 255) / 256)) : dim3((unsigned)rows, (Wq + 255) / 256));
-    sc_pick(scale, [&](auto sc) {
+    sc_pick3(mode, [&](auto sc) {
       hipLaunchKernelGGL((upsample_fwd_v4_kernel<decltype(sc)::value>), grid, dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo, ac_scale(Hi, Ho),
                          ac_scale(Wi, Wo), rows, Wq, shift, scale);
     });
   } else {
-    sc_pick(scale, [&](auto sc) {
+    sc_pick3(mode, [&](auto sc) {
       hipLaunchKernelGGL((upsample_fwd_kernel<decltype(sc)::value>), dim3(ew_grid(total)), dim3(256), 0, st, x, y, Hi, Wi, Ho, Wo,
-                         ac_scale(Hi, Ho), ac_scale(Wi, Wo), total, scale);
+                         ac_scale(Hi, Ho), ac_scale(Wi, Wo), total, scale, (float*)nullptr);
     });
+  }
+  return rsis_check_launch();
+}
+// the backward preparation of y = resize(x) * m (`-skip_mode mul`), one launch at the fine resolution: with u = resize(x) recomputed from x
+// (the blend of upsample_fwd_kernel, its fused multiply-adds written out in ac_blend),
+//   dm[e] = accumulate ? fmaf(dy[e], u[e], dm[e]) : dy[e] * u[e];      dy[e] <- dy[e] * m[e]   (in place)
+// after which the unscaled transpose (rsis_l_upsample_bwd) runs on dy.  Every element is read and written by one thread: no atomics.
+int rsis_l_upsample_mul_bwd_prep(float* dy, const float* x, const float* m, float* dm, long BC, int Hi, int Wi, int Ho, int Wo, int accumulate,
+                                 hipStream_t st) {
+  const long total = BC * Ho * Wo;
+  const float sh = ac_scale(Hi, Ho), sw = ac_scale(Wi, Wo);
+  if (Wo % 4 == 0 && BC * Ho < (1L << 31)) {      // where the forward runs its float4 kernels (LDS or v4): their blend is ac_blend
+    const long items = total / 4;
+    if (accumulate)
+      hipLaunchKernelGGL((upsample_mul_bwd_prep_kernel<true>), dim3(ew_grid(items)), dim3(256), 0, st, dy, x, m, dm, Hi, Wi, Ho, Wo, sh, sw, items);
+    else
+      hipLaunchKernelGGL((upsample_mul_bwd_prep_kernel<false>), dim3(ew_grid(items)), dim3(256), 0, st, dy, x, m, dm, Hi, Wi, Ho, Wo, sh, sw, items);
+  } else if (accumulate) {                         // the forward's scalar kernel: its own loop, so that u has its bits
+    hipLaunchKernelGGL((upsample_fwd_kernel<4>), dim3(ew_grid(total)), dim3(256), 0, st, x, dy, Hi, Wi, Ho, Wo, sh, sw, total, m, dm);
+  } else {
+    hipLaunchKernelGGL((upsample_fwd_kernel<3>), dim3(ew_grid(total)), dim3(256), 0, st, x, dy, Hi, Wi, Ho, Wo, sh, sw, total, m, dm);
   }
   return rsis_check_launch();
 }

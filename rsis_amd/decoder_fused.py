@@ -89,15 +89,36 @@ class LevelTape(object):
                 self.UP = torch.empty((cap, B, self.c_up, Hh, Ww), dtype=torch.float32, device=device)
 
 
-def _packs(cell, c_up, c_skip):
-    """PackedConv triples of one cell: hoisted (skip channels), dynamic (up + h_prev channels)."""
-    key = ("fused", c_up, c_skip, getattr(cell, "dtype", ops.DTYPE_F32))
+SKIP_MODES = ("concat", "sum", "mul", "none")
+
+
+def pack_offsets(c_up, c_skip, mode="concat"):
+    """(first gate-weight column of the hoisted skip term, or None where nothing is hoisted; first column of h_prev) of a cell whose input
+    is x | h_prev with x = [up | skip] (concat), up + skip (sum), up * skip (mul) or up (none) -- reference model.py:151-158.  A cell without
+    an upsampled input (level 0: c_up == 0) takes its skip feature alone in every mode, which is the concat rule."""
+    if mode not in SKIP_MODES:
+        raise ValueError("skip mode %r" % (mode,))
+    if mode == "concat" or c_up == 0:
+        return c_up, c_up + c_skip
+    if mode == "sum":        # conv(up + skip, W_x) = conv(up, W_x) + conv(skip, W_x): both read columns [0, c_up)
+        if c_skip != c_up:
+            raise ValueError("skip mode sum: %d skip channels on %d upsampled ones" % (c_skip, c_up))
+        return 0, c_up
+    return None, c_up
+
+
+def _packs(cell, c_up, c_skip, mode="concat"):
+    """PackedConv pair of one cell: hoisted (skip channels; None where the mode hoists nothing), dynamic (up + h_prev channels)."""
+    skip_off, h_off = pack_offsets(c_up, c_skip, mode)
+    if mode != "concat" and c_up == 0:
+        mode = "concat"
+    key = ("fused", c_up, c_skip, getattr(cell, "dtype", ops.DTYPE_F32)) + (() if mode == "concat" else (mode,))
     if key not in cell._packs:
         hid, ks, pad = cell.hidden_size, cell.kernel_size, cell.padding
-        skip_off = c_up
-        h_off = c_up + c_skip
         dt = getattr(cell, "dtype", ops.DTYPE_F32)
-        hoist = ops.PackedConv(ks, [c_skip], lstm_hid=hid, stride=1, pad=pad, offs=[skip_off], dtype=dt)
+        hoist = None
+        if skip_off is not None:
+            hoist = ops.PackedConv(ks, [c_skip], lstm_hid=hid, stride=1, pad=pad, offs=[skip_off], dtype=dt)
         segs, offs = ([c_up], [0]) if c_up > 0 else ([], [])
         dyn = ops.PackedConv(ks, segs + [hid], lstm_hid=hid, stride=1, pad=pad, offs=offs + [h_off], dtype=dt)
         cell._packs[key] = (hoist, dyn)
@@ -116,21 +137,21 @@ def _limb_ok(cell, dyn):
     return dyn.dtype == ops.DTYPE_F32 and cell.kernel_size == 3 and cell.padding == 1 and all(s % 8 == 0 for s in dyn.segs)
 
 
-def dyn_fwd_pack(cell, c_up, c_skip, level, training):
+def dyn_fwd_pack(cell, c_up, c_skip, level, training, mode="concat"):
     """The copy set the gate conv's TRAINING forward reads: the limb copy where ops.limb_class("f<level>") routes the level to the limb
     kernel (fp32, 3x3, sources in multiples of 8 channels), otherwise -- and for every inference call -- the dynamic pack itself."""
-    _hoist, dyn = _packs(cell, c_up, c_skip)
+    _hoist, dyn = _packs(cell, c_up, c_skip, mode)
     if not training or level is None or not ops.limb_class("f%d" % level) or not _limb_ok(cell, dyn):
         return dyn
     return _limb_pack(cell, dyn, "fwd")
 
 
-def dyn_dgrad_pack(cell, c_up, c_skip, H, W, level=None):
+def dyn_dgrad_pack(cell, c_up, c_skip, H, W, level=None, mode="concat"):
     """The copy set the gate conv's DATA GRADIENT (d(up) | dh_prev, explicit BPTT of decoder_seq) reads: under fp32, on levels whose
     sources are 32-channel multiples and whose map holds at least 12 x 12 pixels, a Winograd F(2x2, 3x3) copy (ops.DTYPE_F32_WINO,
     RSIS_WINOGRAD_GATES, default on: the 16 x 16 and 32 x 32 levels at 256 x 256 input, hidden 128) -- otherwise the dynamic pack itself.
     The forward keeps the direct kernel with the fused LSTM epilogue on every level."""
-    _hoist, dyn = _packs(cell, c_up, c_skip)
+    _hoist, dyn = _packs(cell, c_up, c_skip, mode)
     hid = cell.hidden_size
     if (dyn.dtype != ops.DTYPE_F32 or not ops.WINOGRAD_GATES[0] or cell.kernel_size != 3 or cell.padding != 1 or min(H, W) < 12
             or (c_up + hid) % 32 or c_up % 32 or c_up == 0 or (4 * hid) % 32):

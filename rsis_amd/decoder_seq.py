@@ -25,6 +25,15 @@ launches, picked per call by blk_supported():
 
 Arithmetic and kernels per cell are those of the per-step path (tests/test_gpu_modules.py compares them); only the launch
 schedule differs.  The per-timestep `RSIS.forward` stays for callers that thread the state themselves.
+
+`-skip_mode` (model.py:151-158) changes how up = up(h[i-1][t]) meets skip[i] in front of the gate conv of levels 1-4 (_Level.mode):
+  * concat: [up | skip | h]; the skip columns are hoisted (G);
+  * sum: the conv is linear, conv(up + skip, W_x) = conv(up, W_x) + conv(skip, W_x) -- the concat schedule with the hoisted pack and the
+    dynamic up segment both on columns [0, c_up) (decoder_fused.pack_offsets);
+  * none: no hoisted term (G, hoist are None): the gate launches take the bias instead of the addend, skip[1..4] get no gradient;
+  * mul: as none, and UP[i][t] holds the product up * skip (the mul form of the upsample launches); the backward runs one preparation
+    launch in front of the unchanged upsample transposes: DM[i] (+)= dUP * up, dUP <- dUP * skip, DM an fp32 NCHW accumulator that is the
+    skip feature's gradient after the last step.  `-dropout > 0` with mul stays on the per-step path (supported()).
 """
 import os
 
@@ -51,12 +60,16 @@ def _chan(t):
 
 
 def supported(decoder, skip_feats, T):
-    """the explicit sequence covers the product configuration: concat skips, 3x3 gates, any dropout rates in [0, 1), the fused heads kernel"""
+    """the explicit sequence covers the product configuration: the four skip modes, 3x3 gates, any dropout rates in [0, 1) (`-skip_mode mul`:
+    -dropout 0 only), the fused heads kernel"""
     n = len(decoder.clstm_list)
-    if not (ENABLED[0] and decoder_fused.WAVEFRONT[0] and decoder_fused.FUSED_POOL[0] and decoder.fused and decoder.skip_mode == "concat" and
+    mode = decoder.skip_mode
+    if not (ENABLED[0] and decoder_fused.WAVEFRONT[0] and decoder_fused.FUSED_POOL[0] and decoder.fused and mode in decoder_fused.SKIP_MODES and
             len(skip_feats) == n and T >= 1 and "forward" not in decoder.__dict__):
         return False
     if not all(0 <= p < 1 for p in dropout.rates(decoder)):
+        return False
+    if mode == "mul" and dropout.rates(decoder)[0] > 0:       # (s2 * up(h)) * skip: no launch of the node forms it
         return False
     if not all(f.is_cuda and ((f.dtype == torch.float32 and f.dim() == 4) or _is_blk(f)) for f in skip_feats):
         return False
@@ -69,11 +82,21 @@ def supported(decoder, skip_feats, T):
     hs = [c.hidden_size for c in decoder.clstm_list]
     if sum(hs) != decoder.fc_class.weight.shape[1] or not ops.heads_supported([skip_feats[0]] * n, decoder.fc_class, decoder.fc_stop, min_rows=1):
         return False
-    for i, c in enumerate(decoder.clstm_list):      # the channel pyramid of model.py:98-106 (level i consumes up(h[i-1]) | skip[i])
+    for i, c in enumerate(decoder.clstm_list):      # the channel pyramid of model.py:98-106,151-158, per mode
         c_up = 0 if i == 0 else hs[i - 1]
-        if c.input_size != c_up + _chan(skip_feats[i]):
+        if not channels_ok(mode, c.input_size, c_up, _chan(skip_feats[i])):
             return False
     return True
+
+
+def channels_ok(mode, input_size, c_up, c_skip):
+    """the input channels of a level's cell: level 0 (c_up == 0) takes its skip feature alone; above it up | skip (concat), up + skip or
+    up * skip (sum, mul: equal channel counts), up (none)"""
+    if c_up == 0 or mode == "concat":
+        return input_size == c_up + c_skip
+    if mode in ("sum", "mul"):
+        return input_size == c_up == c_skip
+    return mode == "none" and input_size == c_up
 
 
 class ShapeProbe(object):
@@ -122,7 +145,10 @@ def blk_supported(decoder, skip_feats):
 
 
 class _Level(object):
-    __slots__ = ("cell", "hid", "c_up", "c_skip", "H", "W", "hoist", "dyn", "fwd_pack", "G", "Hs", "Cs", "ACT", "UP", "KEY", "SIDE", "ARG", "skip")
+    """mode: how the level's input meets its skip feature ("concat" at level 0, decoder.skip_mode above).  hoist / G are None where the
+    mode has no time-invariant gate term (mul, none): the gate launches then take the bias instead of the addend.  skip: the feature in the
+    layout's storage (None under none); UP[t]: up(h[i-1][t]), under mul the product up(h[i-1][t]) * skip"""
+    __slots__ = ("cell", "mode", "hid", "c_up", "c_skip", "H", "W", "hoist", "dyn", "fwd_pack", "G", "Hs", "Cs", "ACT", "UP", "KEY", "SIDE", "ARG", "skip")
 
 
 UPCONV = [os.environ.get("RSIS_UPCONV", "1") != "0"]       # the last level's upsample + conv_out as one op per direction (upconv_out.hip)
@@ -229,7 +255,9 @@ class _Nchw(_Layout):
         """G_i = W[:, skip channels] * skip_i + b, one launch per level (on a tile of its own when a backward may follow)"""
         _lib.require_cuda_f32(*feats)
         for lv, f, w, b in zip(levels, feats, gates_w, gates_b):
-            lv.skip = f
+            lv.skip = f if lv.mode != "none" else None
+            if lv.hoist is None:
+                continue
             wp = lv.hoist.fwd(w, b)
             check(self.L.rsis_conv2d_fwd(ptr_array([f]), int_array([lv.c_skip]), 1, self.B, lv.H, lv.W, ptr(wp), 4 * lv.hid, 3, 1, 1,
                                          ptr(lv.hoist.bias_p), None, ptr(lv.G), lv.H, lv.W, ops.FORCE_TILE[0] + (100 if need_grad else 0),
@@ -244,7 +272,8 @@ class _Nchw(_Layout):
             for k, s in enumerate(srcs):
                 j.src[k], j.Csrc[k] = s.data_ptr(), s.shape[1]
             (j.B, j.H, j.W, j.Wp, j.bias_packed, j.addend, j.c_prev, j.h_out, j.c_out, j.act_out, j.hid, j.ks, j.pad, j.tile, j.dtype,
-             j.side_key) = (self.B, lv.H, lv.W, wps[i].data_ptr(), None, lv.G.data_ptr(), lv.Cs[t - 1].data_ptr() if t > 0 else None,
+             j.side_key) = (self.B, lv.H, lv.W, wps[i].data_ptr(), lv.fwd_pack.bias_p.data_ptr() if lv.G is None else None,
+                            lv.G.data_ptr() if lv.G is not None else None, lv.Cs[t - 1].data_ptr() if t > 0 else None,
                             lv.Hs[t].data_ptr(), lv.Cs[t].data_ptr(), lv.ACT[t].data_ptr() if lv.ACT is not None else None, lv.hid, 3, 1,
                             ops.FORCE_TILE[0], lv.fwd_pack.dtype, lv.KEY[t].data_ptr())
         check(self.L.rsis_convlstm_fwd_batch(jobs, len(cells), stream()), "rsis_convlstm_fwd_batch")
@@ -254,7 +283,10 @@ class _Nchw(_Layout):
         for i, t in cells:
             if i + 1 < len(levels):
                 lv, nx = levels[i], levels[i + 1]
-                if s2 is not None:                        # (equal sizes: the scaled copy)
+                if nx.mode == "mul":                      # up(h) * skip (equal sizes: the product itself)
+                    check(self.L.rsis_upsample_bilinear_ac_mul_fwd(ptr(lv.Hs[t]), ptr(nx.skip), ptr(nx.UP[t]), self.B * lv.hid, lv.H, lv.W, nx.H, nx.W,
+                                                                   stream()), "rsis_upsample_mul_fwd")
+                elif s2 is not None:                      # (equal sizes: the scaled copy)
                     check(self.L.rsis_upsample_bilinear_ac_scaled_fwd(ptr(lv.Hs[t]), ptr(s2[i][t]), ptr(nx.UP[t]), self.B * lv.hid, lv.H, lv.W, nx.H,
                                                                       nx.W, stream()), "rsis_upsample_scaled_fwd")
                 elif (nx.H, nx.W) == (lv.H, lv.W):        # align-corners resize to the same size is the identity (ops.upsample_bilinear_ac)
@@ -321,12 +353,16 @@ class _Nchw(_Layout):
         check(self.L.rsis_upsample_maxpool_bwd(ptr(dUP5), ptr(dside), ptr(last.ARG), ptr(DH_last), self.T * self.B * last.hid, last.H, last.W,
                                                2 * last.H, 2 * last.W, stream()), "rsis_upsample_maxpool_bwd(all steps)")
 
-    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None):
-        """dh[i][t] = up^T(dUP[i + 1][t]) + the side gradient at the arg-max; s2: times the Dropout2d scale of the plane"""
+    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None, DM=None):
+        """dh[i][t] = up^T(dUP[i + 1][t]) + the side gradient at the arg-max; s2: times the Dropout2d scale of the plane.  mul levels
+        first: DM[i + 1] (+)= dUP * up(h[i][t]) (stored at t = T - 1, the first step the reverse wavefront visits), dUP <- dUP * skip"""
         B = self.B
         for i, t in cells:
             if i + 1 < len(levels):
                 lv, nx = levels[i], levels[i + 1]
+                if nx.mode == "mul":
+                    check(self.L.rsis_upsample_mul_bwd_prep(ptr(DUP[i + 1]), ptr(lv.Hs[t]), ptr(nx.skip), ptr(DM[i + 1]), B * lv.hid, lv.H, lv.W, nx.H,
+                                                            nx.W, int(t != self.T - 1), stream()), "rsis_upsample_mul_bwd_prep")
                 if s2 is not None and (nx.H, nx.W) == (lv.H, lv.W):
                     check(self.L.rsis_scale_planes(ptr(DUP[i + 1]), ptr(s2[i][t]), ptr(DH[i]), B * lv.hid, lv.H * lv.W, stream()), "rsis_scale_planes")
                     check(self.L.rsis_global_maxpool_scaled_bwd_add(ptr(dsides[i][t]), ptr(lv.ARG[t]), ptr(s2[i][t]), ptr(DH[i]), B * lv.hid,
@@ -383,8 +419,8 @@ class _Nchw(_Layout):
         bf16 rows that are not a multiple of 4 pixels (the 7 / 14-pixel levels of a 224 x 224 input) go through channel-blocked bf16
         copies of the (small) stacks and the whole-cell loader, see decoder_fused._StepFn.backward"""
         if lv.dyn.dtype == ops.DTYPE_BF16 and decoder_fused._BLK_WGRAD[0] and lv.W % 4 != 0 and lv.hid % 8 == 0 and lv.c_up % 8 == 0:
-            return lv.hoist.dtype, ops.DTYPE_BF16_BLK, lambda x: ops.blk_from_nchw(x.flatten(0, 1))
-        return lv.hoist.dtype, lv.dyn.dtype, lambda x: x.flatten(0, 1)
+            return lv.dyn.dtype, ops.DTYPE_BF16_BLK, lambda x: ops.blk_from_nchw(x.flatten(0, 1))
+        return lv.dyn.dtype, lv.dyn.dtype, lambda x: x.flatten(0, 1)
 
 
 class _Blk(_Layout):
@@ -407,7 +443,9 @@ class _Blk(_Layout):
     def hoist(self, levels, feats, gates_w, gates_b, need_grad):
         jobs = []
         for lv, f, w, b in zip(levels, feats, gates_w, gates_b):
-            lv.skip = f if _is_blk(f) else ops.blk_from_nchw(f)
+            lv.skip = None if lv.mode == "none" else (f if _is_blk(f) else ops.blk_from_nchw(f))
+            if lv.hoist is None:
+                continue
             jobs.append(ops.blk_conv_job([lv.skip], lv.hoist.fwd(w, b), 4 * lv.hid, bias=lv.hoist.bias_p, dsts=[lv.G]))
         ops.blk_conv3x3_batch(jobs)
 
@@ -415,14 +453,18 @@ class _Blk(_Layout):
         jobs = []
         for i, t in cells:
             lv = levels[i]
-            jobs.append(ops.blk_conv_job(_gate_srcs(lv, t), wps[i], 4 * lv.hid, addend=lv.G, hid=lv.hid, c_prev=lv.Cs[t - 1] if t > 0 else None,
-                                         c_out=lv.Cs[t], h_out=lv.Hs[t], act_out=lv.ACT[t] if lv.ACT is not None else None, side_key=lv.KEY[t],
-                                         shape=(self.B, lv.H, lv.W)))
+            jobs.append(ops.blk_conv_job(_gate_srcs(lv, t), wps[i], 4 * lv.hid, bias=lv.fwd_pack.bias_p if lv.G is None else None, addend=lv.G,
+                                         hid=lv.hid, c_prev=lv.Cs[t - 1] if t > 0 else None, c_out=lv.Cs[t], h_out=lv.Hs[t],
+                                         act_out=lv.ACT[t] if lv.ACT is not None else None, side_key=lv.KEY[t], shape=(self.B, lv.H, lv.W)))
         ops.blk_conv3x3_batch(jobs)
 
     def up(self, levels, cells, s2=None):
-        ups = [ops.blk_resize_job(levels[i].Hs[t], levels[i + 1].UP[t], scale=s2[i][t] if s2 is not None else None)
-               for i, t in cells if i + 1 < len(levels)]
+        cells = [(i, t) for i, t in cells if i + 1 < len(levels)]
+        muls = [ops.blk_resize_mul_job(levels[i].Hs[t], levels[i + 1].UP[t], levels[i + 1].skip) for i, t in cells if levels[i + 1].mode == "mul"]
+        if muls:            # (every level above 0 has the decoder's mode: a diagonal's upsamples are all of one kind)
+            ops.blk_upsample_mul_fwd_batch(muls)
+            return
+        ups = [ops.blk_resize_job(levels[i].Hs[t], levels[i + 1].UP[t], scale=s2[i][t] if s2 is not None else None) for i, t in cells]
         if ups:
             ops.blk_upsample_fwd_batch(ups)
 
@@ -445,7 +487,11 @@ class _Blk(_Layout):
     def up5_bwd(self, dUP5, dside, last, DH_last, sc=None):
         ops.blk_upsample_bwd_batch([ops.blk_resize_job(dUP5.flatten(0, 1), DH_last.flatten(0, 1), dside, last.ARG, backward=True, scale=sc)])
 
-    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None):
+    def up_bwd(self, levels, cells, DUP, DH, dsides, s2=None, DM=None):
+        prep = [ops.blk_mul_prep_job(DUP[i + 1], levels[i].Hs[t], levels[i + 1].skip, DM[i + 1], t != self.T - 1)
+                for i, t in cells if i + 1 < len(levels) and levels[i + 1].mode == "mul"]
+        if prep:
+            ops.blk_upsample_mul_bwd_prep_batch(prep)
         ups = [ops.blk_resize_job(DUP[i + 1], DH[i], dsides[i][t], levels[i].ARG[t], backward=True, scale=s2[i][t] if s2 is not None else None)
                for i, t in cells if i + 1 < len(levels)]
         if ups:
@@ -497,9 +543,10 @@ class _DecoderSeqFn(torch.autograd.Function):
         for i, cell in enumerate(decoder.clstm_list):
             lv = _Level()
             lv.cell, lv.hid, lv.c_up, lv.c_skip = cell, hs[i], (0 if i == 0 else hs[i - 1]), _chan(feats[i])
+            lv.mode = "concat" if i == 0 else decoder.skip_mode
             lv.H, lv.W = feats[i].shape[2], feats[i].shape[3]
-            lv.hoist, lv.dyn = decoder_fused._packs(cell, lv.c_up, lv.c_skip)
-            lv.G = lay.empty((B,), 4 * lv.hid, lv.H, lv.W)
+            lv.hoist, lv.dyn = decoder_fused._packs(cell, lv.c_up, lv.c_skip, lv.mode)
+            lv.G = lay.empty((B,), 4 * lv.hid, lv.H, lv.W) if lv.hoist is not None else None
             lv.Hs = lay.empty((T, B), lv.hid, lv.H, lv.W)
             lv.Cs = torch.empty((T, B, lv.hid, lv.H, lv.W), **f32)
             lv.ACT = lay.empty((T, B), 4 * lv.hid, lv.H, lv.W) if need_grad else None
@@ -507,7 +554,7 @@ class _DecoderSeqFn(torch.autograd.Function):
             levels.append(lv)
         for lv, key, side, arg in zip(levels, _per_level(KEY, hs, T, B), _per_level(SIDE, hs, T, B), _per_level(ARG, hs, T, B)):
             lv.KEY, lv.SIDE, lv.ARG = key, side, arg
-        # G_i = W[:, skip channels] * skip_i + b, once per iteration (the skip features do not depend on t)
+        # G_i = W[:, skip channels] * skip_i + b, once per iteration (the skip features do not depend on t); mul / none: no such term
         # the dropout scales of the whole sequence (model.py:141,172,177), drawn once; all rates 0: nothing is allocated or drawn
         drop = None
         p2, pc, ps = dropout.rates(decoder)
@@ -526,8 +573,9 @@ class _DecoderSeqFn(torch.autograd.Function):
         probs_tb = torch.empty((T, B, Wc.shape[0]), **f32)
         stop_tb = torch.empty((T, B, 1), **f32)
         for i, lv in enumerate(levels):          # (the limb copy where the routing puts the level's training forward on the limb kernel)
-            lv.fwd_pack = decoder_fused.dyn_fwd_pack(lv.cell, lv.c_up, lv.c_skip, i, need_grad and not lay.blk)
-        wps = [lv.fwd_pack.fwd(w) for lv, w in zip(levels, gates_w)]
+            lv.fwd_pack = decoder_fused.dyn_fwd_pack(lv.cell, lv.c_up, lv.c_skip, i, need_grad and not lay.blk, lv.mode)
+        # (a level without a hoisted term gets its bias from the gate launch: packed with the copy that launch reads)
+        wps = [lv.fwd_pack.fwd(w) if lv.hoist is not None else lv.fwd_pack.fwd(w, b) for lv, w, b in zip(levels, gates_w, gates_b)]
         for d in range(T + n - 1):
             cells = _diagonal(d, n, T)
             lay.gates(levels, cells, wps)
@@ -640,7 +688,10 @@ class _DecoderSeqFn(torch.autograd.Function):
         DHP = [lay.empty((B,), lv.hid, lv.H, lv.W) for lv in levels]                 # ... through the recurrence, from step t + 1
         DC = [[torch.empty((B, lv.hid, lv.H, lv.W), **f32) for _ in range(2)] for lv in levels]
         DUP = [lay.empty((B,), lv.c_up, lv.H, lv.W) if lv.c_up > 0 else None for lv in levels]
-        dpk = [decoder_fused.dyn_dgrad_pack(lv.cell, lv.c_up, lv.c_skip, lv.H, lv.W, level=i) for i, lv in enumerate(levels)]
+        dpk = [decoder_fused.dyn_dgrad_pack(lv.cell, lv.c_up, lv.c_skip, lv.H, lv.W, level=i, mode=lv.mode) for i, lv in enumerate(levels)]
+        # mul: the gradient of the skip feature, summed over t in fp32 NCHW whatever the storage (rounded once, at the end)
+        DM = [torch.empty((B, lv.c_up, lv.H, lv.W), **f32) if lv.mode == "mul" else None for lv in levels]
+        mul = any(m is not None for m in DM)
         wds = [pk.dgrad(w) for pk, w in zip(dpk, gates_w)]
         # gradients a caller put on the returned final state (none in runIter: train.py never reads it)
         d_hidden = d_hidden or (None,) * (2 * n)
@@ -662,7 +713,9 @@ class _DecoderSeqFn(torch.autograd.Function):
         for d in range(T + n - 2, -1, -1):
             cells = _diagonal(d, n, T)
             # gradient reaching h[i][t] through its upsample into the next level and its side max-pool
-            if s2 is not None:
+            if mul:
+                lay.up_bwd(levels, cells, DUP, DH, dsides, None, DM)
+            elif s2 is not None:
                 lay.up_bwd(levels, cells, DUP, DH, dsides, s2)
             else:
                 lay.up_bwd(levels, cells, DUP, DH, dsides)
@@ -680,38 +733,43 @@ class _DecoderSeqFn(torch.autograd.Function):
             # data gradients of the gate convs: d(up[i][t]) for the level below, dh[i][t-1] through the recurrence -- ONE grouped launch
             lay.dgrad(dg)
         # ---- per level, once: the time-invariant skip term and the time-batched weight gradients ----
+        # (sum_t d(gates) feeds the hoisted term's data / weight gradient and the bias gradient; without a hoisted term only the latter)
         dG, dskip, dfeats = [None] * n, [None] * n, [None] * n
+        hoisted = [lv.hoist is not None for lv in levels]
         for grp in ([[i] for i in range(n)] if lay.by_level else [range(n)]):
             for i in grp:
                 if T == 1:
                     dG[i] = DA[i][0]
-                else:
-                    dG[i] = torch.empty_like(levels[i].G)
+                elif hoisted[i] or need_par[2 * i + 1]:
+                    dG[i] = torch.empty_like(DA[i][0])
                     lay.sum_t(DA[i], dG[i])
-                if need_feat[i]:
+                if need_feat[i] and hoisted[i]:
                     dskip[i] = torch.empty_like(levels[i].skip)
             lay.skip_dgrad([(dG[i], levels[i].hoist.dgrad(gates_w[i]), levels[i].hoist.cin, levels[i].hoist.dtype, [dskip[i]]) for i in grp
-                            if need_feat[i]])
+                            if need_feat[i] and hoisted[i]])
             for i in grp:
                 lv = levels[i]
                 kw, kb = 2 * i, 2 * i + 1
                 hid, H, W = lv.hid, lv.H, lv.W
-                if need_feat[i]:
+                if need_feat[i] and hoisted[i]:
                     dfeats[i] = dskip[i] if _is_blk(feats[i]) else lay.to_nchw(dskip[i])
+                elif need_feat[i] and lv.mode == "mul":      # (none: the feature is unused, its gradient stays None)
+                    dfeats[i] = ops.blk_from_nchw(DM[i]) if _is_blk(feats[i]) else DM[i]
                 if need_par[kb]:
                     lay.bias_grad(dG[i], target(kb)[0], lv)
                 if need_par[kw]:
                     dW, direct = target(kw)
                     Ctot = gates_w[i].shape[1]
                     dt_skip, dt, rows = lay.wgrad_formats(lv)
-                    ops.wgrad_launch(L, dG[i], lv.skip, dW, B, lv.c_skip, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up, hid, dt_skip,
-                                     "rsis_conv2d_wgrad(hoist)", direct)
+                    if hoisted[i]:      # (sum: into columns [0, c_up), which the batched-up launch below adds to)
+                        ops.wgrad_launch(L, dG[i], lv.skip, dW, B, lv.c_skip, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.hoist.offs[0], hid, dt_skip,
+                                         "rsis_conv2d_wgrad(hoist)", direct)
                     da = rows(DA[i])
                     if lv.c_up > 0:
                         ops.wgrad_launch(L, da, rows(lv.UP), dW, T * B, lv.c_up, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, 0, hid, dt,
                                          "rsis_conv2d_wgrad(batched up)", direct)
                     if T > 1:
-                        ops.wgrad_launch(L, da[B:], rows(lv.Hs[:T - 1]), dW, (T - 1) * B, hid, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.c_up + lv.c_skip,
+                        ops.wgrad_launch(L, da[B:], rows(lv.Hs[:T - 1]), dW, (T - 1) * B, hid, H, W, 4 * hid, H, W, 3, 1, 1, Ctot, lv.dyn.offs[-1],
                                          hid, dt, "rsis_conv2d_wgrad(batched h)", direct)
         for lv in levels:
             lv.G = lv.Hs = lv.Cs = lv.ACT = lv.UP = lv.skip = None

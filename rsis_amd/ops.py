@@ -1272,6 +1272,40 @@ def blk_upsample_bwd_batch(jobs):
     _blk_resize_batch(jobs, "rsis_blk_upsample_bwd_batch")
 
 
+def blk_resize_mul_job(src, dst, mul):
+    """y = resize(x) * mul (`-skip_mode mul`): src = x [B][C/8][Hi][Wi][8] -> dst = y [B][C/8][Ho][Wo][8], mul a blk tensor of y's shape"""
+    _blk_ok(src, dst, mul)
+    if mul.shape != dst.shape:
+        raise ValueError("blk_resize_mul_job: the multiplier has the result's shape")
+    j = _lib.BlkResizeMulJob()
+    j.src, j.dst, j.mul = src.data_ptr(), dst.data_ptr(), mul.data_ptr()
+    j.B, j.C, j.Hi, j.Wi, j.Ho, j.Wo = src.shape[0], src.shape[1] * 8, src.shape[2], src.shape[3], dst.shape[2], dst.shape[3]
+    return j, (src, dst, mul)
+
+
+def blk_upsample_mul_fwd_batch(jobs):
+    arr = (_lib.BlkResizeMulJob * len(jobs))(*[j for j, _keep in jobs])
+    check(lib().rsis_blk_upsample_mul_fwd_batch(arr, len(jobs), stream()), "rsis_blk_upsample_mul_fwd_batch")
+
+
+def blk_mul_prep_job(dy, x, m, dm, accumulate):
+    """backward preparation of y = resize(x) * m: dm (fp32 NCHW [B][C][Ho][Wo]) = dy * u, or fmaf(dy, u, dm) with accumulate, u = resize(x)
+    rounded to bf16; then dy <- dy * m in place (include/rsis_hip.h: rsis_blk_mul_prep_job)"""
+    _blk_ok(dy, x, m)
+    B, Cb, Ho, Wo, _ = dy.shape
+    if m.shape != dy.shape or dm.dtype != torch.float32 or tuple(dm.shape) != (B, Cb * 8, Ho, Wo) or not dm.is_contiguous() or x.shape[:2] != dy.shape[:2]:
+        raise ValueError("blk_mul_prep_job: m has dy's shape, dm is its fp32 NCHW twin, x has dy's planes")
+    j = _lib.BlkMulPrepJob()
+    j.dy, j.x, j.m, j.dm = dy.data_ptr(), x.data_ptr(), m.data_ptr(), dm.data_ptr()
+    j.B, j.C, j.Hi, j.Wi, j.Ho, j.Wo, j.accumulate = B, Cb * 8, x.shape[2], x.shape[3], Ho, Wo, int(bool(accumulate))
+    return j, (dy, x, m, dm)
+
+
+def blk_upsample_mul_bwd_prep_batch(jobs):
+    arr = (_lib.BlkMulPrepJob * len(jobs))(*[j for j, _keep in jobs])
+    check(lib().rsis_blk_upsample_mul_bwd_prep_batch(arr, len(jobs), stream()), "rsis_blk_upsample_mul_bwd_prep_batch")
+
+
 def blk_lstm_bwd_job(dh, dh2, dc_next, act, c_prev, c, da, dc_prev):
     _blk_ok(dh, dh2, act, da)
     j = _lib.BlkLstmBwdJob()

@@ -329,6 +329,10 @@ def build_optimizers(args, encoder, decoder):
     # fc_class / fc_stop receive no gradient until their loss is enabled: torch.optim leaves such parameters alone
     lazy = [] if args.use_class_loss else list(decoder.fc_class.parameters())
     lazy += [] if args.use_stop_loss else list(decoder.fc_stop.parameters())
+    if getattr(args, "skip_mode", "concat") == "none":
+        # model.py:158: levels 1-4 never read their skip features, so sk4..sk1 / bn4..bn1 never receive a gradient: as above
+        for name in ("sk4", "sk3", "sk2", "sk1", "bn4", "bn3", "bn2", "bn1"):
+            lazy += list(getattr(encoder, name).parameters()) if hasattr(encoder, name) else []
     dec_opt = _flat_optimizer(args.optim, decoder_params, args.lr, args.weight_decay, momentum, "dec", lazy=lazy)
     mult = base_param_multiplicity(encoder) if quirk else None
     enc_opt = _flat_optimizer(args.optim_cnn, list(get_base_params(args, encoder)), args.lr_cnn, args.weight_decay_cnn, momentum, "enc",
