@@ -259,6 +259,13 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _device(device, who):
+    """torch.device(device) for the evaluator module `who`; without a GPU there is nothing to run on"""
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s needs the GPU: the HIP library is the only compute path" % who)
+    return torch.device(device)
+
+
 def ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):

@@ -44,7 +44,7 @@ import sys
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream
+from ._lib import _device, check, lib, ptr, stream
 
 CLASS_IDS = (24, 25, 26, 27, 28, 31, 32, 33)                  # == eval_post.CITYSCAPES_CLASS_IDS
 CLASS_NAMES = ("person", "rider", "car", "truck", "bus", "train", "motorcycle", "bicycle")
@@ -56,12 +56,6 @@ JOB = 16                                                       # int64 entries p
 
 
 # ------------------------------------------------------------------ the two launches ------------------------------------------------------------------
-def _device(device):
-    if not torch.cuda.is_available():
-        raise RuntimeError("rsis_amd.cityscapes_eval needs the GPU: the HIP library is the only compute path")
-    return torch.device(device)
-
-
 def _gt_bytes(g, what, device):
     """2-d image of ids 0 .. 65535 (numpy or tensor, any integer type) -> flat uint8 tensor of its little-endian uint16 values"""
     if isinstance(g, torch.Tensor):
@@ -143,7 +137,7 @@ def overlap_counts_batch(gt_images, mask_sets, device="cuda", align=2, lead=0):
     (int64, S), counts (P_j + 1, S) int64 host array, counts[p, s] = non-zero pixels of mask p on ids[s], last row = pixels of ids[s].
     One host -> device copy of the pool, the presence launch, the lut (device), the overlap launch, one copy back.  `lead` bytes
     (even) are left free in front of the first image (tests: images at odd pool positions)."""
-    device = _device(device)
+    device = _device(device, "rsis_amd.cityscapes_eval")
     if len(gt_images) != len(mask_sets):
         raise ValueError("%d id images for %d mask sets" % (len(gt_images), len(mask_sets)))
     n = len(gt_images)

@@ -37,7 +37,7 @@ import warnings
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream
+from ._lib import _device, check, lib, ptr, stream
 
 SCORE_COLUMNS = ("SymmetricBestDice", "FgBgDice", "AbsDiffFGLabels", "DiffFGLabels", "BestDice_in_gt", "BestDice_gt_in")
 TABLE = 256 * 256            # uint32 counts of one pair in the dense global table: counts[i * 256 + j]
@@ -120,16 +120,10 @@ def _launch_scores(counts, jobs, n):
     return scores
 
 
-def _device(device):
-    if not torch.cuda.is_available():
-        raise RuntimeError("rsis_amd.cvppp_eval needs the GPU: the HIP library is the only compute path")
-    return torch.device(device)
-
-
 def contingency(in_images, gt_images, device="cuda", align=16):
     """lists of N uint8 (h, w) tensors / arrays, host or device, any sizes -> (N, 256, 256) int64 device tensor, [p, i, j] = number of
     pixels of pair p with in == i and gt == j (one grouped launch)"""
-    device = _device(device)
+    device = _device(device, "rsis_amd.cvppp_eval")
     if len(gt_images) == 0:
         return torch.zeros((0, 256, 256), dtype=torch.int64, device=device)
     pool, jobs, n, blocks = _pool(in_images, gt_images, align, device)
@@ -140,7 +134,7 @@ def contingency(in_images, gt_images, device="cuda", align=16):
 def score_pairs(in_images, gt_images, device="cuda", align=16):
     """lists of N uint8 (h, w) tensors / arrays -> (N, 6) float64 host tensor, columns SCORE_COLUMNS: the contingency launch, the scores
     launch, one device -> host copy"""
-    device = _device(device)
+    device = _device(device, "rsis_amd.cvppp_eval")
     if len(gt_images) == 0:
         return torch.zeros((0, 6), dtype=torch.float64)
     pool, jobs, n, blocks = _pool(in_images, gt_images, align, device)

@@ -44,6 +44,9 @@ painted over it in its sequence colour and the class name at the mask's centre -
 post-processing, rsis_amd/display.py.  The records drawn are those of eval.py:329-338: per timestep the class of maximum confidence when
 its score reaches -class_th; for leaves every record of a timestep whose objectness exceeds -stop_th.  Without --display nothing about a
 run changes.  A ground-truth FILE of another dataset is evaluated with `python -m rsis_amd.cocoeval`.
+Loading the models, opening the reader and loader (or the synthetic loader), the batch loop around `test()` and the `__main__` body are
+rsis_amd/eval_common.py, shared with eval_cityscapes.py and eval_leaves.py.  A lone last image is fed to `test()` twice for -dataset
+cityscapes and leaves (as eval_leaves.py does) and as it is for pascal, coco and --synthetic.
 """
 import json
 import os
@@ -52,13 +55,10 @@ import sys
 import numpy as np
 import torch
 
-from .args import get_parser
 from .cocoeval import COCOEvalDevice, rle_from_string, run_reference_protocol
+from .eval_common import EvalDriver, load_models, run_main  # noqa: F401  (load_models: importable from here as before)
 from .eval_post import encode_masks, resize_mask  # noqa: F401  (resize_mask: reference signature, eval.py:96-127)
-from .modules.model import RSIS, FeatureExtractor
-from .synthetic import SyntheticLoader
-from .test import test
-from .utils.utils import check_parallel, load_checkpoint, load_plain_pickle
+from .utils.utils import load_plain_pickle
 
 
 def create_annotation(args, imname, pred_mask, class_id, score, classes, is_valid=True):
@@ -69,67 +69,33 @@ def create_annotation(args, imname, pred_mask, class_id, score, classes, is_vali
             "score": score}
 
 
-def load_models(args):
-    """eval.py:229-246 (also eval_cityscapes.py:50-94, eval_leaves.py:45-89): the checkpoint of -model_name under -models_root ->
-    eval-mode encoder / decoder on the device, built from the LOADED args; args.num_classes / hidden_size follow the checkpoint.
-    Without a checkpoint directory the modules are randomly initialised (synthetic smoke runs), said on stderr."""
-    model_dir = os.path.join(args.models_root, args.model_name)
-    if os.path.exists(os.path.join(model_dir, "encoder.pt")):
-        encoder_dict, decoder_dict, _, _, load_args = load_checkpoint(args.model_name, args.use_gpu, root=args.models_root)
-        load_args.use_gpu = args.use_gpu
-        if getattr(args, "dtype", None):
-            load_args.dtype = args.dtype
-        encoder, decoder = FeatureExtractor(load_args), RSIS(load_args)
-        encoder_dict, decoder_dict = check_parallel(encoder_dict, decoder_dict)
-        encoder.load_state_dict(encoder_dict)
-        decoder.load_state_dict(decoder_dict)
-        args.num_classes, args.hidden_size = load_args.num_classes, load_args.hidden_size
-    else:
-        print("no checkpoint at %s: evaluating randomly initialised weights" % model_dir, file=sys.stderr)
-        encoder, decoder = FeatureExtractor(args), RSIS(args)
-    return encoder.cuda().eval(), decoder.cuda().eval()
-
-
-class Evaluate(object):
+class Evaluate(EvalDriver):
     def __init__(self, args):
-        self.args = args
-        self.split = args.eval_split
-        self.gt_records = self.ignore_rle = self.dataset = self.dataset_name = None
+        super().__init__(args)
+        self.gt_records = self.ignore_rle = None
         self.gt_images = self.category_ids = None                   # -dataset coco: the file's `images`, class index -> category id
         self.display = bool(getattr(args, "display", False))
         self.figures = []                                           # with --display: (path, records drawn, label rectangles) per image
-        if not getattr(args, "synthetic", False):
-            if args.dataset == "pascal":
-                self._init_pascal()
-            elif args.dataset in ("cityscapes", "leaves"):
-                self._init_files(args.dataset)
-            elif args.dataset == "coco":
-                self._init_coco()
-            else:
-                raise Exception("-dataset %s: only --synthetic inputs and -dataset pascal, cityscapes, leaves and coco are wired in this build"
-                                % args.dataset)
-            return
-        self.encoder, self.decoder = load_models(self.args)
-        self.class_names = ["<eos>"] + ["class%d" % i for i in range(1, self.args.num_classes)]
-        self.loader = SyntheticLoader(args, max(1, args.synthetic_batches // 4), args.seed + 7)
-        self.sample_list = ["synthetic_%06d" % i for i in range(len(self.loader) * args.batch_size)]
-
-    def _open(self, name):
-        """eval.py:191-218, the part every dataset shares: the reader of -eval_split, the models, the loader; -> args"""
-        from .dataloader import eval_loader, open_reader
-        args = self.args
-        self.dataset_name = name
-        self.dataset = open_reader(args, self.split, dataset=name)
-        self.class_names = self.dataset.get_classes()
-        self.encoder, self.decoder = load_models(args)
-        self.loader = eval_loader(args, self.dataset)
-        return args
+        self.dataset_name = None if getattr(args, "synthetic", False) else args.dataset
+        self.no_gt = self.dataset_name in ("cityscapes", "leaves")  # eval.py has no ground truth for them: nothing to evaluate against
+        if self.dataset_name is None:
+            self.open_synthetic()
+            self.class_names = ["<eos>"] + ["class%d" % i for i in range(1, args.num_classes)]
+        elif args.dataset == "pascal":
+            self._init_pascal()
+        elif self.no_gt:
+            self._init_files(args.dataset)
+        elif args.dataset == "coco":
+            self._init_coco()
+        else:
+            raise Exception("-dataset %s: only --synthetic inputs and -dataset pascal, cityscapes, leaves and coco are wired in this build"
+                            % args.dataset)
 
     def _init_pascal(self):
         """eval.py:191-218 for -dataset pascal"""
-        args = self._open("pascal")
+        self.open_dataset("pascal")
         self.sample_list = [s.rstrip() for s in self.dataset.get_sample_list()]
-        self.gt_records = load_plain_pickle(os.path.join(args.pascal_dir, "VOCGT_%s.pkl" % self.split))
+        self.gt_records = load_plain_pickle(os.path.join(self.args.pascal_dir, "VOCGT_%s.pkl" % self.split))
         self.ignore_rle = {}                                        # image id -> segmentation of its ignore mask (eval.py:198-209)
         for ann in self.gt_records:
             if ann["ignore"] == 1:
@@ -138,19 +104,19 @@ class Evaluate(object):
     def _init_coco(self):
         """-dataset coco: the reader of dataloader/coco.py; the ground truth is the annotation file itself, records and `images`"""
         from .cocoeval import load_coco_file
-        self._open("coco")
+        self.open_dataset("coco")
         self.sample_list = list(self.dataset.image_ids)             # the file's integer image ids
         self.category_ids = list(self.dataset.category_ids)
         self.gt_records, self.gt_images = load_coco_file(self.dataset.ann_file)
 
     def _init_files(self, name):
         """eval.py:191-218 for -dataset cityscapes / leaves: the reader and loader of eval_cityscapes.py / eval_leaves.py; no ground truth"""
-        args = self._open(name)
+        self.open_dataset(name)
         if name == "cityscapes":
             self.sample_list = [os.path.splitext(f)[0] for f in self.dataset.get_sample_list()]  # eval.py:288
         else:
             self.sample_list = list(self.dataset.get_sample_list())                             # eval.py:291
-        if not getattr(args, "no_run_coco_eval", False):
+        if not getattr(self.args, "no_run_coco_eval", False):
             print("-dataset %s has no ground-truth file in eval.py: the COCO evaluation is skipped" % name, file=sys.stderr)
 
     def _display_image(self, index, x):
@@ -172,98 +138,108 @@ class Evaluate(object):
         vals = np.arange(len(counts), dtype=np.uint8) & 1
         return np.ascontiguousarray(np.repeat(vals, counts.astype(np.int64)).reshape(w, h).T)
 
+    def _open_evaluator(self):
+        """the device evaluator holding the ground truth that comes from a file; None when nothing is evaluated"""
+        if getattr(self.args, "no_run_coco_eval", False) or self.no_gt:
+            return None
+        coco = COCOEvalDevice()
+        if self.gt_images is not None:                               # a COCO file: every record, the sizes from its `images`
+            coco.add_gt(self.gt_records, images=self.gt_images)
+        elif self.gt_records is not None:
+            mine = set(self.sample_list)
+            coco.add_gt([r for r in self.gt_records if r["image_id"] in mine])
+        return coco
+
+    def _image_records(self, sample_idx, segs, areas, raws, scores, stops, h, w):
+        """eval.py:303-333 for one image: segs / areas / raws of its T masks (encode_masks), scores (T, C), stops (T, 1) ->
+        (predictions: the records of the predictions file, shown: those kept for display, drawn: the same with their mask row,
+        rows / cats / recscores: mask row, category id and score of every prediction)"""
+        args = self.args
+        predictions, shown, drawn, rows, cats, recscores = [], [], [], [], [], []
+        classes = np.argmax(scores, axis=-1)
+
+        def record(seg, cls_id, score, is_valid):
+            ann = create_annotation(args, sample_idx, _jsonable(seg), cls_id, score, self.class_names, is_valid)
+            if ann is not None and self.category_ids is not None:    # a COCO results file: the ORIGINAL id
+                ann["category_id"] = self.category_ids[cls_id]
+            return ann
+
+        for i in range(scores.shape[0]):
+            objectness = float(stops[i][0])
+            if objectness < args.stop_th:                          # eval.py:303-304
+                continue
+            max_class = 1 if args.class_th == 0.0 else int(classes[i])
+            is_valid = not (areas[i] < args.min_size * h * w)                                    # eval.py:113-114
+            for cls_id in range(1, len(self.class_names)):                                       # eval.py:316-319 (0 = eos)
+                score = float(scores[i][cls_id]) * objectness
+                ann = record(segs[i], cls_id, score, is_valid)
+                if ann is None:
+                    continue
+                if self.dataset_name == "leaves":                                                # eval.py:329-331
+                    if objectness > args.stop_th:
+                        shown.append(ann)
+                        drawn.append(dict(ann, mask_row=i))
+                elif cls_id == max_class and score >= args.class_th:                             # eval.py:333
+                    shown.append(record(raws[i], cls_id, score, is_valid))
+                    drawn.append(dict(shown[-1], mask_row=i))
+                predictions.append(ann)
+                rows.append(i)
+                cats.append(ann["category_id"])
+                recscores.append(score)
+        return predictions, shown, drawn, rows, cats, recscores
+
+    def _feed_evaluator(self, sample_idx, targets, h, w, bits, rows, cats, recscores):
+        """one image into self.coco: its ground truth from the loader's `targets` (y_mask, y_class, sw_mask of the image) unless a file
+        gave it, in the detections' (column-major) element order; its detections as the bit-packed masks that have records"""
+        y_mask, y_class, sw_mask = targets
+        n_gt = int((sw_mask > 0).sum()) if self.gt_records is None else 0                        # (Pascal, COCO: the records of the file)
+        if n_gt:
+            gt_m = (y_mask[:n_gt].reshape(n_gt, h, w).transpose(1, 2) > 0.5).to(torch.uint8).reshape(n_gt, h * w)
+            self.coco.add_gt_masks(sample_idx, gt_m, [int(c) for c in y_class[:n_gt].cpu()])
+        if rows:
+            kept = sorted(set(rows))                                 # only the masks that have records go into the pool
+            sel = torch.as_tensor(kept, device=bits[0].device)
+            pos = {r: j for j, r in enumerate(kept)}
+            self.coco.add_dt_masks(sample_idx, None, cats, recscores, rows=[pos[r] for r in rows],
+                                   bits=(bits[0][sel], bits[1][sel], bits[2]))
+
     def _create_json(self):
         """eval.py:254-345: one record per (instance, class) with score = class probability * objectness"""
         args = self.args
-        predictions, shown, acc = [], [], 0
-        no_gt = self.dataset_name in ("cityscapes", "leaves")       # eval.py has no ground truth for them: nothing to evaluate against
-        coco = self.coco = None if (getattr(args, "no_run_coco_eval", False) or no_gt) else COCOEvalDevice()
-        figs_dir = None
+        predictions, shown = [], []
+        self.coco = self._open_evaluator()
         if self.display:
             from . import display
             figs_dir = display.figures_dir(args.models_root, args.model_name, self.split)       # eval.py:343-344
             os.makedirs(figs_dir, exist_ok=True)
-        if coco is not None and self.gt_images is not None:          # a COCO file: every record, the sizes from its `images`
-            coco.add_gt(self.gt_records, images=self.gt_images)
-        elif coco is not None and self.gt_records is not None:
-            mine = set(self.sample_list)
-            coco.add_gt([r for r in self.gt_records if r["image_id"] in mine])
-        for inputs, y_mask, y_class, sw_mask, _sw_class in self.loader:
-            x = inputs
-            if x.size(0) == 1 and no_gt:         # a lone tail image of the file readers is doubled, as eval_leaves.py does (test() needs B >= 2)
-                out_masks, out_scores, stop_probs = [t[:1] for t in test(args, self.encoder, self.decoder, torch.cat([x, x]))]
-            else:
-                out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)   # eval.py:262
+        # eval.py:262; a lone tail image is doubled for -dataset cityscapes / leaves, as eval_leaves.py does; pascal, coco, --synthetic: as it is
+        double_lone_tail = self.dataset_name in ("cityscapes", "leaves")
+        for first, (x, y_mask, y_class, sw_mask, _sw_class), out_masks, out_scores, stop_probs in self.batches(double_lone_tail):
             scores = out_scores.cpu().numpy()
             stops = stop_probs.cpu().numpy()
-            classes = np.argmax(scores, axis=-1)
-            h, w = x.size(-2), x.size(-1)                          # (synthetic images: the "original" size is the input size)
             for s in range(out_masks.shape[0]):
-                sample_idx = self.sample_list[s + acc]
-                ignore = None
-                if self.dataset is not None:                       # eval.py:280-295: the ORIGINAL size, the image's ignore pixels
-                    h, w = self.dataset.raw_size(s + acc)              # (eval.py:293-295)
-                    if self.ignore_rle is not None:
-                        ignore = self._ignore_mask(sample_idx)
+                sample_idx = self.sample_list[first + s]
+                # eval.py:280-295: the ORIGINAL size and the image's ignore pixels (synthetic images: the input size, none)
+                h, w = self.original_size(first + s, (x.size(-2), x.size(-1)))
+                ignore = self._ignore_mask(sample_idx) if self.ignore_rle is not None else None
                 # all T masks of the image in one launch each: resample + threshold + area, then run-length encoding
-                if self.display:
-                    segs, areas, raws, bits, dev_masks = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True,
-                                                                      want_masks=True)
-                else:
-                    segs, areas, raws, bits = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True)
-                rows, cats, recscores = [], [], []                  # of the records that reach the predictions file
-                drawn = []                                          # the image's records for display, each with its mask row
-                for i in range(out_masks.shape[1]):
-                    objectness = float(stops[s][i][0])
-                    if objectness < args.stop_th:                  # eval.py:303-304
-                        continue
-                    max_class = 1 if args.class_th == 0.0 else int(classes[s][i])
-                    is_valid = not (areas[i] < args.min_size * h * w)                            # eval.py:113-114
-                    for cls_id in range(1, len(self.class_names)):                               # eval.py:316-319 (0 = eos)
-                        score = float(scores[s][i][cls_id]) * objectness
-                        ann = create_annotation(args, sample_idx, _jsonable(segs[i]), cls_id, score, self.class_names, is_valid)
-                        if ann is None:
-                            continue
-                        if self.category_ids is not None:                                        # a COCO results file: the ORIGINAL id
-                            ann["category_id"] = self.category_ids[cls_id]
-                        if self.dataset_name == "leaves":                                        # eval.py:329-331
-                            if objectness > args.stop_th:
-                                shown.append(ann)
-                                drawn.append(dict(ann, mask_row=i))
-                        elif cls_id == max_class and score >= args.class_th:                     # eval.py:333
-                            shown.append(create_annotation(args, sample_idx, _jsonable(raws[i]), cls_id, score, self.class_names,
-                                                           is_valid))
-                            if self.category_ids is not None:
-                                shown[-1]["category_id"] = self.category_ids[cls_id]
-                            drawn.append(dict(shown[-1], mask_row=i))
-                        predictions.append(ann)
-                        rows.append(i)
-                        cats.append(ann["category_id"])
-                        recscores.append(score)
+                segs, areas, raws, bits, *dev_masks = encode_masks(out_masks[s], h, w, args.mask_th, ignore, want_bits=True,
+                                                                   want_masks=self.display)
+                new, kept, drawn, rows, cats, recscores = self._image_records(sample_idx, segs, areas, raws, scores[s], stops[s], h, w)
+                predictions += new
+                shown += kept
                 if self.display:                                    # eval.py:342-359: the RAW masks over the original image
-                    from . import display
                     fig = os.path.join(figs_dir, display.figure_name(sample_idx, self.dataset_name))
-                    rects = display.save_figure(fig, self._display_image(s + acc, x[s]), dev_masks[1], drawn,
+                    rects = display.save_figure(fig, self._display_image(first + s, x[s]), dev_masks[0][1], drawn,
                                                 no_display_text=args.no_display_text, display_route=args.display_route)
                     self.figures.append((fig, drawn, rects))
-                if coco is not None:
-                    # ground truth of the image from the loader's targets, in the detections' (column-major) element order
-                    n_gt = int((sw_mask[s] > 0).sum()) if self.gt_records is None else 0     # (Pascal: the records of the file)
-                    if n_gt:
-                        gt_m = (y_mask[s, :n_gt].reshape(n_gt, h, w).transpose(1, 2) > 0.5).to(torch.uint8).reshape(n_gt, h * w)
-                        coco.add_gt_masks(sample_idx, gt_m, [int(c) for c in y_class[s, :n_gt].cpu()])
-                    if rows:
-                        kept = sorted(set(rows))                     # only the masks that have records go into the pool
-                        sel = torch.as_tensor(kept, device=bits[0].device)
-                        pos = {r: j for j, r in enumerate(kept)}
-                        coco.add_dt_masks(sample_idx, None, cats, recscores, rows=[pos[r] for r in rows],
-                                          bits=(bits[0][sel], bits[1][sel], bits[2]))
-            acc += out_masks.shape[0]
+                if self.coco is not None:
+                    self._feed_evaluator(sample_idx, (y_mask[s], y_class[s], sw_mask[s]), h, w, bits, rows, cats, recscores)
         return predictions, shown
 
     def run_eval(self):
         predictions, shown = self._create_json()
-        out_dir = os.path.join(self.args.models_root, self.args.model_name)
+        out_dir = self.out_path()
         os.makedirs(out_dir, exist_ok=True)
         path = os.path.join(out_dir, "%s_%s_predictions.json" % (self.args.model_name, self.split))
         with open(path, "w") as f:
@@ -298,9 +274,4 @@ def _jsonable(rle):
 
 
 if __name__ == "__main__":
-    parser = get_parser()
-    a = parser.parse_args()
-    torch.manual_seed(a.seed)
-    if not a.use_gpu or not torch.cuda.is_available():
-        raise SystemExit("rsis_amd.eval needs the GPU: the HIP library is the only compute path")
-    Evaluate(a).run_eval()
+    run_main("rsis_amd.eval", lambda args: Evaluate(args).run_eval())

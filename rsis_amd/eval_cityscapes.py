@@ -27,18 +27,16 @@ contested pixel, the background is 7 (road: neither void nor an instance; 0 woul
 `python -m rsis_amd.cityscapes_eval --results <..._results> --gt <..._gt>` gives the same JSON from the files.
 `--display` is parsed and ignored here, as in the reference's eval_cityscapes.py (it stores the flag and never reads it); the figures of
 `--display` (display_cityscapes.sh) come from `python -m rsis_amd.eval -dataset cityscapes ... --display`.
+Opening the reader or the synthetic loader and the models, the batch loop around `test()` and the `__main__` body are
+rsis_amd/eval_common.py, shared with eval.py and eval_leaves.py; the two modes differ in `_ground_truth` alone.
 """
 import os
 import sys
 
 import numpy as np
-import torch
 
-from .args import get_parser
-from .eval import load_models
-from .eval_post import CITYSCAPES_CLASS_IDS, write_cityscapes_results
-from .synthetic import SyntheticLoader
-from .test import test
+from .eval_common import EvalDriver, run_main
+from .eval_post import CITYSCAPES_CLASS_IDS, cityscapes_result_columns, write_cityscapes_results
 
 
 BACKGROUND_ID = 7
@@ -60,96 +58,60 @@ def synthetic_instance_ids(y_mask, y_class, height, width, scale=2):
     return np.repeat(np.repeat(gt, scale, 0), scale, 1)
 
 
-class Evaluate(object):
+class Evaluate(EvalDriver):
     def __init__(self, args):
-        self.args, self.split, self.T = args, args.eval_split, args.maxseqlen
-        self.dataset = None
-        if not getattr(args, "synthetic", False):
-            self._init_files()
-            return
-        self.encoder, self.decoder = load_models(args)
-        self.loader = SyntheticLoader(args, max(1, args.synthetic_batches // 4), args.seed + 7)
-        self.sample_list = ["synthetic_%06d" % i for i in range(len(self.loader) * args.batch_size)]
+        super().__init__(args)
+        if getattr(args, "synthetic", False):
+            self.open_synthetic()
+        else:                                  # eval_cityscapes.py:38-51: the images of -eval_split through the reader, in file order
+            self.open_dataset("cityscapes")
+            self.sample_list = [os.path.basename(f).split(".")[0] for f in self.dataset.get_sample_list()]   # :114-120
 
-    def _init_files(self):
-        """eval_cityscapes.py:38-51: the images of -eval_split through the reader, in file order"""
-        from .dataloader import eval_loader, open_reader
-        args = self.args
-        self.dataset = open_reader(args, self.split, dataset="cityscapes")
-        self.sample_list = [os.path.basename(f).split(".")[0] for f in self.dataset.get_sample_list()]   # :114-120
-        self.encoder, self.decoder = load_models(args)
-        self.loader = eval_loader(args, self.dataset)
+    def _ground_truth(self, index, sample, y_mask, y_class, Hm, Wm, do_score):
+        """what one image is scored against and resized to: (instance-id array or None, height, width).  Files: the raw instanceIds array,
+        read only when it is scored, and the size in the PNG header.  --synthetic: the array made of the loader's targets, saved as the
+        benchmark stores it whether scored or not (nothing is read back), and twice the input size."""
+        from . import cityscapes_eval
+        if self.dataset is not None:
+            gt = cityscapes_eval.read_gt_png(self.dataset.ins_files[index]) if do_score else None
+        else:
+            from PIL import Image
+            gt = synthetic_instance_ids(y_mask, y_class, Hm, Wm)
+            Image.fromarray(gt).save(os.path.join(self.gt_dir, sample + cityscapes_eval.GT_SUFFIX))
+        return (gt,) + tuple(self.original_size(index, (2 * Hm, 2 * Wm)))                              # :115-118
 
-    def _create_figures_files(self):
-        """create_figures on the files of the dataset: original sizes from the PNG headers, ground truth = the raw instanceIds arrays"""
+    def create_figures(self):
         from . import cityscapes_eval
         args = self.args
-        results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results")     # eval_cityscapes.py:99-104
+        results_dir = self.out_path(args.model_name + "_results")                                       # eval_cityscapes.py:99-104
         masks_dir = args.model_name + "_masks"
         os.makedirs(os.path.join(results_dir, masks_dir), exist_ok=True)
         self.results_dir, self.gt_dir = results_dir, None
+        if self.dataset is None:
+            self.gt_dir = self.out_path(args.model_name + "_gt")
+            os.makedirs(self.gt_dir, exist_ok=True)
         do_score = not getattr(args, "no_run_coco_eval", False)
         self.records = []
         print("Creating annotations for cityscapes validation...")
-        acc, n_lines = 0, 0
-        for x, _y_mask, _y_class, _sw_mask, _sw_class in self.loader:
-            out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)               # :108
+        n_images = n_lines = 0
+        for first, (x, y_mask, y_class, *_sw), out_masks, out_scores, stop_probs in self.batches(False):   # :108; a lone tail image as it is
             Hm, Wm = x.size(-2), x.size(-1)
             gts, mask_sets, rows, labels, scores = [], [], [], [], []
             for s in range(out_masks.shape[0]):
-                sample, masks = self.sample_list[s + acc], []
-                h, w = self.dataset.raw_size(s + acc)                                                    # :115-118
+                sample, masks = self.sample_list[first + s], []
+                gt, h, w = self._ground_truth(first + s, sample, y_mask[s], y_class[s], Hm, Wm, do_score)
                 lines = write_cityscapes_results(args, sample, out_masks[s].view(self.T, Hm, Wm), out_scores[s],
                                                  stop_probs[s], h, w, results_dir, masks_dir, collect=masks)
                 n_lines += len(lines)
                 if do_score:
-                    gts.append(cityscapes_eval.read_gt_png(self.dataset.ins_files[s + acc]))
+                    gts.append(gt)
                     mask_sets.append(masks)
-                    rows.append([q // (len(lines) // len(masks)) for q in range(len(lines))])
-                    labels.append([int(l.split()[1]) for l in lines])
-                    scores.append([float(l.split()[2]) for l in lines])
+                    for column, values in zip((rows, labels, scores), cityscapes_result_columns(lines, len(masks))):
+                        column.append(values)
             if do_score:
                 self.records += cityscapes_eval.score_image_sets(gts, mask_sets, rows, labels, scores)
-            acc += out_masks.shape[0]
-        print("%d result lines for %d images -> %s" % (n_lines, acc, results_dir))
-        return n_lines
-
-    def create_figures(self):
-        if self.dataset is not None:
-            return self._create_figures_files()
-        args = self.args
-        results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results")     # eval_cityscapes.py:99-104
-        masks_dir = args.model_name + "_masks"
-        os.makedirs(os.path.join(results_dir, masks_dir), exist_ok=True)
-        self.results_dir = results_dir
-        self.gt_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_gt")
-        os.makedirs(self.gt_dir, exist_ok=True)
-        do_score = not getattr(args, "no_run_coco_eval", False)
-        self.records = []
-        print("Creating annotations for cityscapes validation...")
-        from PIL import Image
-        from . import cityscapes_eval
-        acc, n_lines = 0, 0
-        for x, y_mask, y_class, _sw_mask, _sw_class in self.loader:
-            out_masks, out_scores, stop_probs = test(args, self.encoder, self.decoder, x)               # :108
-            Hm, Wm = x.size(-2), x.size(-1)
-            gts, mask_sets, rows, labels, scores = [], [], [], [], []
-            for s in range(out_masks.shape[0]):
-                sample, masks = self.sample_list[s + acc], []
-                gt = synthetic_instance_ids(y_mask[s], y_class[s], Hm, Wm)
-                Image.fromarray(gt).save(os.path.join(self.gt_dir, sample + cityscapes_eval.GT_SUFFIX))
-                lines = write_cityscapes_results(args, sample, out_masks[s].view(self.T, Hm, Wm), out_scores[s],
-                                                 stop_probs[s], 2 * Hm, 2 * Wm, results_dir, masks_dir, collect=masks)
-                n_lines += len(lines)
-                gts.append(gt)
-                mask_sets.append(masks)
-                rows.append([q // (len(lines) // len(masks)) for q in range(len(lines))])
-                labels.append([int(l.split()[1]) for l in lines])
-                scores.append([float(l.split()[2]) for l in lines])
-            if do_score:                                           # the arrays that were just saved: nothing is read back
-                self.records += cityscapes_eval.score_image_sets(gts, mask_sets, rows, labels, scores)
-            acc += out_masks.shape[0]
-        print("%d result lines for %d images -> %s" % (n_lines, acc, results_dir))
+            n_images += out_masks.shape[0]
+        print("%d result lines for %d images -> %s" % (n_lines, n_images, results_dir))
         return n_lines
 
     def score(self):
@@ -163,17 +125,16 @@ class Evaluate(object):
         aps = cityscapes_eval.evaluate_matches(self.records)
         res = {"aps": aps, "averages": cityscapes_eval.compute_averages(aps), "images": len(self.records)}
         sys.stdout.write(cityscapes_eval.summary(res["averages"]))
-        name = os.path.join(args.models_root, args.model_name, args.model_name + "_cityscapes_eval.json")
+        name = self.out_path(args.model_name + "_cityscapes_eval.json")
         print("%d images -> %s" % (res["images"], cityscapes_eval.write_result_json(name, res)))
         return res
 
 
-if __name__ == "__main__":
-    a = get_parser().parse_args()
-    torch.manual_seed(a.seed)
-    if not a.use_gpu or not torch.cuda.is_available():
-        raise SystemExit("rsis_amd.eval_cityscapes needs the GPU: the HIP library is the only compute path")
-    ev = Evaluate(a)
+def _main(args):
+    ev = Evaluate(args)
     ev.create_figures()
     ev.score()
-    sys.exit(0)
+
+
+if __name__ == "__main__":
+    run_main("rsis_amd.eval_cityscapes", _main)

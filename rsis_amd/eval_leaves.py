@@ -14,46 +14,33 @@ Deviations from the reference script, all deliberate:
   * `-eval_split test` reads `-leaves_test_dir` and needs no ground truth (as the reference);
   * `--display` is parsed and ignored here, as in the reference's eval_leaves.py (it stores the flag and never reads it).
 The figures of `--display` (display_leaves.sh) come from `python -m rsis_amd.eval -dataset leaves ... --display`.
+Opening the reader, the loader and the models, the batch loop around `test()` (with a lone last image fed twice) and the `__main__` body
+are rsis_amd/eval_common.py, shared with eval.py and eval_cityscapes.py.
 """
 import os
-import sys
 
-import torch
-
-from .args import get_parser
-from .dataloader import eval_loader, open_reader
-from .eval import load_models
+from .eval_common import EvalDriver, run_main
 from .eval_post import write_leaves_result
-from .test import test
 
 
-class Evaluate(object):
+class Evaluate(EvalDriver):
     def __init__(self, args):
-        self.args, self.split, self.T = args, args.eval_split, args.maxseqlen
-        self.dataset = open_reader(args, self.split, dataset="leaves")                                               # :36
-        self.loader = eval_loader(args, self.dataset)                                                                # :38-41
+        super().__init__(args)
+        self.open_dataset("leaves")                                                                                  # :36-41
         self.sample_list = self.dataset.get_sample_list()
-        self.encoder, self.decoder = load_models(args)
 
     def create_figures(self):
         args = self.args
-        results_dir = os.path.join(args.models_root, args.model_name, args.model_name + "_results", "A1")
+        results_dir = self.out_path(args.model_name + "_results", "A1")
         os.makedirs(results_dir, exist_ok=True)
         print("Creating annotations for leaves validation...")
-        acc, written = 0, []
-        for x, _y_mask, _y_class, _sw_mask, _sw_class in self.loader:
-            if x.size(0) == 1:                 # the reference's test() needs B >= 2 (model.py:169 squeeze); a lone tail image is doubled
-                out_masks, _scores, stop_probs = test(args, self.encoder, self.decoder, torch.cat([x, x]))
-                out_masks, stop_probs = out_masks[:1], stop_probs[:1]
-            else:
-                out_masks, _scores, stop_probs = test(args, self.encoder, self.decoder, x)      # eval_leaves.py:96
+        written = []
+        for first, (x, *_targets), out_masks, _scores, stop_probs in self.batches(True):       # :96; a lone tail image is doubled
             Hm, Wm = x.size(-2), x.size(-1)
             for s in range(out_masks.shape[0]):
-                path = self.sample_list[s + acc]
-                h, w = self.dataset.raw_size(s + acc)                                           # :100-103 original size
-                sample_idx = os.path.basename(path).split(".")[0]
+                h, w = self.dataset.raw_size(first + s)                                         # :100-103 original size
+                sample_idx = os.path.basename(self.sample_list[first + s]).split(".")[0]
                 written.append(write_leaves_result(args, sample_idx, out_masks[s].view(self.T, Hm, Wm), stop_probs[s], h, w, results_dir))
-            acc += out_masks.shape[0]
         print("%d label images -> %s" % (len(written), results_dir))
         return written
 
@@ -67,16 +54,15 @@ class Evaluate(object):
             return None
         numbers, scores = cvppp_eval.evaluate_files(written, self.dataset.gt_files)
         cvppp_eval.print_summary(scores)
-        out = os.path.join(self.args.models_root, self.args.model_name, self.args.model_name + "_results")
+        out = self.out_path(self.args.model_name + "_results")
         print("%d images -> %s" % (len(numbers), cvppp_eval.write_result_table(out, self.args.model_name, numbers, scores)))
         return numbers, scores
 
 
-if __name__ == "__main__":
-    a = get_parser().parse_args()
-    torch.manual_seed(a.seed)
-    if not a.use_gpu or not torch.cuda.is_available():
-        raise SystemExit("rsis_amd.eval_leaves needs the GPU: the HIP library is the only compute path")
-    ev = Evaluate(a)
+def _main(args):
+    ev = Evaluate(args)
     ev.score(ev.create_figures())
-    sys.exit(0)
+
+
+if __name__ == "__main__":
+    run_main("rsis_amd.eval_leaves", _main)

@@ -155,6 +155,13 @@ def write_cityscapes_results(args, sample_idx, out_masks, class_scores, stop_pro
     return lines
 
 
+def cityscapes_result_columns(lines, n_masks):
+    """the lines `write_cityscapes_results` returned for an image with `n_masks` collected masks -> (rows, labels, scores), one entry per
+    line: the index of the line's mask among the collected ones, its class id and its score, as cityscapes_eval.score_image_sets takes them"""
+    per_mask = len(lines) // n_masks
+    return ([q // per_mask for q in range(len(lines))], [int(l.split()[1]) for l in lines], [float(l.split()[2]) for l in lines])
+
+
 def leaves_label_image(args, out_masks, stop_probs, height, width):
     """reference src/eval_leaves.py:105-120 for one image: every timestep whose stop probability exceeds -class_th paints its mask --
     the probability map stretched to 0..255 (bytescale inside imresize: min -> 0, max -> 255 PER MASK), resized, thresholded at

@@ -255,7 +255,7 @@ def test_eval_cityscapes_scores_the_ground_truth_of_real_files_as_perfect(city_t
                 present.add(v // 1000)
         return out.cuda(), cls.cuda(), torch.ones((B, T, 1)).cuda()
 
-    monkeypatch.setattr("rsis_amd.eval_cityscapes.test", fake)
+    monkeypatch.setattr("rsis_amd.eval_common.test", fake)
     n_lines = ev.create_figures()
     assert seen == [(2, 3, 64, 128)] * 2 and n_lines == 4 * 10 * 8   # un-cropped, un-resized, in sample order
     res = ev.score()
@@ -271,3 +271,113 @@ def test_eval_cityscapes_scores_the_ground_truth_of_real_files_as_perfect(city_t
     assert sorted(f for f in os.listdir(results) if f.endswith(".txt")) == sorted(s + ".txt" for s in ev.sample_list)
     assert not os.path.exists(os.path.join(a.models_root, "city_eval", "city_eval_gt"))
     assert _listing(city_tree) == before                       # nothing is written into the dataset directory
+
+
+@pytest.fixture(scope="module")
+def odd_tree(tmp_path_factory):
+    """three images per split: at batch 2 the last batch is one image"""
+    from rsis_amd.dataloader.cityscapes import synthesize_cityscapes_dir
+    return synthesize_cityscapes_dir(str(tmp_path_factory.mktemp("cs3") / "CityScapes"), n=3, sizes=((64, 128),))
+
+
+def _recording_network(seen, twins, num_classes):
+    """stand-in for test() that records the shape of every batch it is given (`seen`) and whether its last two images are equal
+    (`twins`).  Every mask is one rectangle, every stop probability 1 and the score of class 1 is (k + 1) / 8 for the k-th image it has
+    been given (exact in float32), so that an output can be traced to its input."""
+    def fake(args, encoder, decoder, x, return_logits=False):
+        k0, B, T = sum(s[0] for s in seen), x.shape[0], args.maxseqlen
+        seen.append(tuple(x.shape))
+        twins.append(B >= 2 and bool((x[-1] == x[-2]).all()))
+        out = torch.zeros((B, T) + tuple(x.shape[-2:]))
+        out[:, :, 8:40, 16:56] = 1.0
+        cls = torch.zeros((B, T, num_classes))
+        cls[:, :, 1] = (torch.arange(B) + k0 + 1).view(B, 1) / 8.0
+        return out.cuda(), cls.cuda(), torch.ones((B, T, 1)).cuda()
+    return fake
+
+
+def _odd_args(odd_tree, tmp_path, name, *extra):
+    from rsis_amd.args import get_parser
+    a = get_parser().parse_args(["-cityscapes_dir", odd_tree, "-eval_split", "val", "-batch_size", "2", "-imsize", "64", "-maxseqlen", "3",
+                                 "-num_classes", "9", "-hidden_size", "32", "-model_name", name, "-num_workers", "2"] + list(extra))
+    a.models_root = str(tmp_path / "models")
+    return a
+
+
+@pytest.mark.gpu
+def test_eval_cityscapes_passes_a_lone_tail_image_as_it_is(odd_tree, tmp_path, monkeypatch):
+    """eval_cityscapes over 3 images at batch 2: the last batch reaches test() as ONE image (this driver does not double it), and the
+    three result files hold the outputs of their own images, in sample order"""
+    from rsis_amd import eval_cityscapes
+    a = _odd_args(odd_tree, tmp_path, "city_tail")
+    torch.manual_seed(0)
+    ev = eval_cityscapes.Evaluate(a)
+    seen, twins = [], []
+    monkeypatch.setattr("rsis_amd.eval_common.test", _recording_network(seen, twins, 9))
+    assert ev.create_figures() == 3 * 3 * 8
+    assert seen == [(2, 3, 64, 128), (1, 3, 64, 128)] and twins == [False, False]
+    results = os.path.join(a.models_root, "city_tail", "city_tail_results")
+    assert len(ev.sample_list) == 3
+    assert sorted(f for f in os.listdir(results) if f.endswith(".txt")) == sorted(s + ".txt" for s in ev.sample_list)
+    for k, sample in enumerate(ev.sample_list):
+        lines = open(os.path.join(results, sample + ".txt")).read().splitlines()
+        assert len(lines) == 3 * 8 and all(l.startswith("city_tail_masks/%s_" % sample) for l in lines)
+        assert lines[0].split()[1] == "24" and float(lines[0].split()[2]) == (k + 1) / 8.0
+    assert len(ev.records) == 3
+
+
+@pytest.mark.gpu
+def test_eval_cityscapes_on_files_unscored_reads_no_ground_truth(odd_tree, tmp_path, monkeypatch):
+    """eval_cityscapes on files under --no_run_coco_eval: the result files are written, nothing is scored, no ground-truth PNG is read
+    for scoring, no `_gt` folder appears and nothing is created under the dataset tree"""
+    from rsis_amd import cityscapes_eval as E, eval_cityscapes
+    before = _listing(odd_tree)
+    a = _odd_args(odd_tree, tmp_path, "city_unscored", "--no_run_coco_eval")
+    torch.manual_seed(0)
+    ev = eval_cityscapes.Evaluate(a)
+    monkeypatch.setattr("rsis_amd.eval_common.test", _recording_network([], [], 9))
+
+    def no_read(path):
+        raise AssertionError("ground truth read under --no_run_coco_eval: %s" % path)
+
+    monkeypatch.setattr(E, "read_gt_png", no_read)
+    assert ev.create_figures() == 3 * 3 * 8
+    assert ev.records == [] and ev.gt_dir is None and ev.score() is None
+    out = os.path.join(a.models_root, "city_unscored")
+    assert sorted(os.listdir(out)) == ["city_unscored_results"]
+    assert _listing(odd_tree) == before
+
+
+@pytest.mark.gpu
+def test_eval_py_doubles_a_lone_tail_image_of_cityscapes_only(odd_tree, tmp_path, monkeypatch):
+    """rsis_amd.eval -dataset cityscapes over 3 images at batch 2: the lone last image reaches test() twice and its copy's outputs are
+    dropped -- records for exactly the 3 images, each with its own scores.  With --synthetic every batch goes in as the loader made it."""
+    from rsis_amd.args import get_parser
+    from rsis_amd.eval import Evaluate
+    a = _odd_args(odd_tree, tmp_path, "city_json", "-dataset", "cityscapes", "-stop_th", "0", "-class_th", "0", "-min_size", "0")
+    torch.manual_seed(0)
+    ev = Evaluate(a)
+    seen, twins = [], []
+    monkeypatch.setattr("rsis_amd.eval_common.test", _recording_network(seen, twins, 9))
+    preds = ev.run_eval()
+    assert seen == [(2, 3, 64, 128), (2, 3, 64, 128)] and twins == [False, True]
+    assert len(ev.sample_list) == 3 and sorted(set(p["image_id"] for p in preds)) == sorted(ev.sample_list)
+    assert len(preds) == 3 * 3 * 8
+    for k, sample in enumerate(ev.sample_list):
+        assert {p["score"] for p in preds if p["image_id"] == sample and p["category_id"] == 1} == {(k + 1) / 8.0}
+    b = get_parser().parse_args(["--synthetic", "-model_name", "syn_json", "-batch_size", "2", "-maxseqlen", "3", "-hidden_size", "32",
+                                 "-synthetic_batches", "8", "-num_classes", "5", "-imsize", "64", "-stop_th", "0", "-class_th", "0",
+                                 "-min_size", "0", "-models_root", str(tmp_path / "models")])
+    ev = Evaluate(b)
+    given = []
+    inner = _recording_network(seen, twins, 5)
+
+    def fake(args, encoder, decoder, x, return_logits=False):
+        given.append(x.data_ptr())
+        return inner(args, encoder, decoder, x)
+
+    del seen[:], twins[:]
+    monkeypatch.setattr("rsis_amd.eval_common.test", fake)
+    assert len(ev.run_eval()) == 4 * 3 * 4
+    assert seen == [(2, 3, 64, 64)] * 2 and twins == [False, False]
+    assert given == [batch[0].data_ptr() for batch in ev.loader]          # the loader's own tensors, not copies

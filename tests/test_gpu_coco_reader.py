@@ -387,7 +387,7 @@ def test_eval_py_writes_a_coco_results_file_that_the_command_line_scores_the_sam
                 cls[s, t, int(seg[ins == k][0])] = 1.0
         return out.cuda(), cls.cuda(), torch.ones((B, T, 1)).cuda()
 
-    monkeypatch.setattr("rsis_amd.eval.test", fake)
+    monkeypatch.setattr("rsis_amd.eval_common.test", fake)
     preds = ev.run_eval()
     assert seen == [2, 2] and len(preds) > 0
     figs = os.path.join(a.models_root, "coco_eval", "coco_eval_figs_val")       # --display: the images come through image_path

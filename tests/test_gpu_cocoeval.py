@@ -181,7 +181,7 @@ def _args(tmp_path, *extra):
 
 
 def _stand_in_network(ev, mode):
-    """replaces inference (rsis_amd.eval.test) by masks made from the loader's targets, so that the evaluation has a known answer:
+    """replaces inference (rsis_amd.eval_common.test) by masks made from the loader's targets, so that the evaluation has a known answer:
     'exact' = the ground truth with score 1 for its class, 'off' = the region no ground truth covers, 'noisy' = the ground truth
     shifted by a few pixels with spread-out class scores"""
     table = {b[0].data_ptr(): b for b in ev.loader.batches}
@@ -209,7 +209,7 @@ def _run(tmp_path, *extra, mode=None, monkeypatch=None):
     torch.manual_seed(0)
     ev = Evaluate(_args(tmp_path, *extra))
     if mode is not None:
-        monkeypatch.setattr("rsis_amd.eval.test", _stand_in_network(ev, mode))
+        monkeypatch.setattr("rsis_amd.eval_common.test", _stand_in_network(ev, mode))
     preds = ev.run_eval()
     path = os.path.join(str(tmp_path), "cocotest", "cocotest_test_cocoeval.json")
     return ev, preds, (json.load(open(path)) if os.path.exists(path) else None)

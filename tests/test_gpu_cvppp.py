@@ -244,3 +244,41 @@ def test_evaluate_score_after_create_figures(tmp_path):
     # a split without ground truth has nothing to score
     ev.dataset.gt_files, ev.split = [], "test"
     assert ev.score(written) is None
+
+
+def test_evaluate_doubles_a_lone_tail_image(tmp_path, monkeypatch):
+    """eval_leaves over a val split of 3 images at batch 2 with a stand-in for test() that records what it is given: the lone last image
+    arrives twice, the copy's outputs are dropped -- one label image per sample, each from its own masks (image k's mask covers the top
+    8 * (k + 1) of 32 rows)"""
+    from PIL import Image
+    from rsis_amd.args import get_parser
+    from rsis_amd.dataloader.leaves import synthesize_leaves_dir
+    from rsis_amd import eval_leaves
+    d = synthesize_leaves_dir(str(tmp_path / "A1"), n=99, size=(40, 48), seed=5)
+    a = get_parser().parse_args(["-model_name", "lv", "-dataset", "leaves", "-leaves_dir", d, "-leaves_test_dir", d, "-eval_split", "val",
+                                 "-batch_size", "2", "-maxseqlen", "3", "-gt_maxseqlen", "6", "-num_classes", "2", "-imsize", "32",
+                                 "--resize", "-hidden_size", "32", "-num_workers", "2", "-class_th", "0.0",
+                                 "-models_root", str(tmp_path / "models")])
+    torch.manual_seed(3)
+    ev = eval_leaves.Evaluate(a)
+    assert len(ev.sample_list) == 3 and len(ev.loader) == 2
+    seen, twins = [], []
+
+    def fake(args, encoder, decoder, x, return_logits=False):
+        k0, B, T = sum(s[0] for s in seen), x.shape[0], args.maxseqlen
+        seen.append(tuple(x.shape))
+        twins.append(bool((x[0] == x[1]).all()))
+        out = torch.zeros((B, T, 32, 32))
+        for s in range(B):
+            out[s, :, :8 * (k0 + s + 1)] = 1.0
+        return out.cuda(), torch.full((B, T, 2), 0.5).cuda(), torch.ones((B, T, 1)).cuda()
+
+    monkeypatch.setattr("rsis_amd.eval_common.test", fake)
+    written = ev.create_figures()
+    assert seen == [(2, 3, 32, 32), (2, 3, 32, 32)] and twins == [False, True]
+    assert len(written) == len(ev.sample_list) == 3
+    assert [os.path.basename(p) for p in written] == ["plant%03d_label.png" % i for i in (96, 97, 98)]
+    labels = [np.array(Image.open(p)) for p in written]
+    assert all(l.shape == (40, 48) for l in labels)
+    rows = [int((l > 0).any(axis=1).sum()) for l in labels]
+    assert all(abs(r - 10 * (k + 1)) <= 1 for k, r in enumerate(rows)), rows

@@ -316,7 +316,7 @@ def test_eval_py_scores_the_ground_truth_of_pascal_as_perfect(tmp_path, monkeypa
             cls[0, t, int(seg[ins == i].min())] = 1.0
         return out.cuda(), cls.cuda(), torch.ones((1, T, 1)).cuda()
 
-    monkeypatch.setattr("rsis_amd.eval.test", fake)
+    monkeypatch.setattr("rsis_amd.eval_common.test", fake)
     preds = ev.run_eval()
     assert seen == [(1, 3, 64, 80)] * 2                        # un-cropped, un-resized, in sample order
     assert preds and all(p["segmentation"]["size"] == [64, 80] for p in preds)
