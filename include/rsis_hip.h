@@ -450,6 +450,15 @@ int rsis_idmap_rle_encode(const unsigned char* idmap, int h, int w, const int* i
 int rsis_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, void* stream);
 int rsis_softiou_bwd(const float* logits, const float* y, const long long* perm, int perm_ld, const float* ca, const float* cb,
                      float* dlogits, int B, int T, int G, long N, void* stream);
+/* The same two with an IGNORE REGION: ignore[B][N], one byte per pixel, 0 = the pixel counts, non-zero = ignored (COCO crowds,
+ *   Cityscapes groups); with k = (ignore == 0):  S[t][g] = sum_n k p y,  S[t][G] = sum_n k p,  S[T][g] = sum_n k y  (y is masked by the
+ *   kernel, not by a promise of the caller), and dlogits is +0.0 at every ignored pixel.  An image ignored everywhere has S = 0: cost 1
+ *   for every pair, zero gradient.  Same layout, limits, early returns and deterministic-mode launch plan as the plain entry points;
+ *   ignore must be 4-byte aligned (RSIS_ERR_ARG otherwise); ignore == NULL IS the plain entry point (same kernel object, same bits). */
+int rsis_softiou_sums_ignore(const float* logits, const float* y, const unsigned char* ignore, float* S, int B, int T, int G, long N,
+                             void* stream);
+int rsis_softiou_bwd_ignore(const float* logits, const float* y, const unsigned char* ignore, const long long* perm, int perm_ld,
+                            const float* ca, const float* cb, float* dlogits, int B, int T, int G, long N, void* stream);
 
 /* ---- class / stop heads of one decoder timestep (model.py:169-182): side = channel concat (by pointer) of nside <= 5 vectors
  * side[i][B][Cside[i]] (the global max-pools of the hidden states); class_probs[B][ncls] = softmax(Wc side + bc) with
@@ -585,6 +594,15 @@ int rsis_poly_to_bits(const double* xy, long nverts, const long long* parts, lon
 int rsis_paint_instance_maps(const unsigned long long* bits, long bits_len, const unsigned int* area, long nrec, const long long* recs,
                              const long long* imgs, int B, int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, int* ins, int* seg,
                              void* stream);
+/* rsis_paint_ignore_map: the ignore map of the same batch (--ignore_regions).  bits[bits_len]: the bit rows of the batch's CROWD records
+ * (rsis_rle_to_bits / rsis_poly_to_bits), crecs[r] = {first word, words, native h, native w, 0, 0, 0, 0} (int64, 8 entries, nrec records),
+ * imgs[b] = {first crowd record, crowd records}, src_y / src_x the tables of rsis_paint_instance_maps, ins[B][Ho][Wo] the instance map it
+ * painted.  ignore[B][Ho][Wo] uint8, EVERY element written: 1 where any crowd record covers (src_x, src_y) and ins is 0 there (an
+ * outlined instance inside a crowd still counts), else 0.  A record that does not fit bits_len covers nothing; an image entry that does
+ * not fit nrec or has more than max_recs records counts as 0 records.  No allocation, no sync, no atomics; integer compares only.
+ * Same refusals as rsis_paint_instance_maps (ins == ignore or an output that is also an input: RSIS_ERR_ARG). */
+int rsis_paint_ignore_map(const unsigned long long* bits, long bits_len, long nrec, const long long* crecs, const long long* imgs, int B,
+                          int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, const int* ins, unsigned char* ignore, void* stream);
 long rsis_mask_intersect_blocks(long D, long G, long stride);
 int rsis_mask_intersect_batch(const unsigned long long* bits, long bits_len, const long long* jobs, int njobs, int total_blocks,
                               unsigned int* inter, long inter_len, void* stream);

@@ -181,6 +181,8 @@ SIGNATURES = {
     "rsis_loss_tail": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsis_softiou_sums": (_i, [_vp, _vp, _vp, _i, _i, _i, _l, _vp]),
     "rsis_softiou_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _l, _vp]),
+    "rsis_softiou_sums_ignore": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _vp]),
+    "rsis_softiou_bwd_ignore": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _l, _vp]),
     "rsis_mask_resize_threshold": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
     "rsis_rle_encode": (_i, [_vp, _i, _l, _vp, _i, _vp, _vp]),
     "rsis_largest_component": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -194,6 +196,7 @@ SIGNATURES = {
     "rsis_coco_iou_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_poly_to_bits": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _l, _vp, _vp]),
     "rsis_paint_instance_maps": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "rsis_paint_ignore_map": (_i, [_vp, _l, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "rsis_coco_match_batch": (_i, [_vp, _i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _i, _vp, _i, _vp, _vp, _l, _vp, _l, _vp]),
     "rsis_rle_from_string": (_i, [ctypes.c_char_p, _vp, _i]),
     "rsis_label_contingency_blocks": (_l, [_l]),

@@ -110,13 +110,16 @@ _FLAGS = [
     ("-coco_dir", dict(dest="coco_dir", default="/data/coco/")),
     ("-coco_train_set", dict(dest="coco_train_set", default="train2017")),
     ("-coco_val_set", dict(dest="coco_val_set", default="val2017")),
+    # regions that say "objects here, not outlined one by one" (COCO iscrowd records, Cityscapes group ids of trained classes) are left
+    # out of the mask loss: the loaders yield a sixth tensor, the (B, N) uint8 ignore map (include/rsis_hip.h: rsis_softiou_sums_ignore)
+    ("--ignore_regions", dict(dest="ignore_regions", action="store_true")),
 ]
 
 _DEFAULTS = dict(resume=False, crop=False, smooth_curves=False, update_encoder=False, transfer=False,
                  curriculum_learning=False, use_class_loss=False, use_stop_loss=False, log_term=False, visdom=False,
                  augment=False, use_gpu=True, resize=False, display=False, display_route=False, use_cats=True,
                  all_classes=False, no_display_text=False, use_gt_cats=False, use_gt_masks=False, use_gt_stop=False,
-                 synthetic=False, graph=False, enc_lr_quirk=False)
+                 synthetic=False, graph=False, enc_lr_quirk=False, ignore_regions=False)
 
 
 def get_parser():

@@ -830,6 +830,24 @@ int rsis_softiou_bwd(const float* logits, const float* y, const long long* perm,
   return rsis_l_softiou_bwd(logits, y, perm, perm_ld, ca, cb, dlogits, B, T, G, N, (hipStream_t)stream);
 }
 
+// ignore null: the plain entry points, argument checks included.  The kernels read a lane's four bytes as one word: 4-byte alignment.
+int rsis_softiou_sums_ignore(const float* logits, const float* y, const unsigned char* ignore, float* S, int B, int T, int G, long N,
+                             void* stream) {
+  if (!ignore) return rsis_softiou_sums(logits, y, S, B, T, G, N, stream);
+  if (!logits || !y || !S || B < 1 || T < 1 || G < 1 || T > 128 || G > 128 || N < 8 || N % 8 != 0 || ((size_t)ignore & 3) != 0)
+    return RSIS_ERR_ARG;
+  return rsis_l_softiou_sums_ignore(logits, y, ignore, S, B, T, G, N, (hipStream_t)stream);
+}
+
+int rsis_softiou_bwd_ignore(const float* logits, const float* y, const unsigned char* ignore, const long long* perm, int perm_ld,
+                            const float* ca, const float* cb, float* dlogits, int B, int T, int G, long N, void* stream) {
+  if (!ignore) return rsis_softiou_bwd(logits, y, perm, perm_ld, ca, cb, dlogits, B, T, G, N, stream);
+  if (!logits || !y || !perm || !ca || !cb || !dlogits || B < 1 || T < 1 || G < 1 || perm_ld < T || N < 4 || N % 4 != 0 ||
+      ((size_t)ignore & 3) != 0)
+    return RSIS_ERR_ARG;
+  return rsis_l_softiou_bwd_ignore(logits, y, ignore, perm, perm_ld, ca, cb, dlogits, B, T, G, N, (hipStream_t)stream);
+}
+
 int rsis_mask_resize_threshold(const float* prob, int n, int Hm, int Wm, const unsigned char* ignore, float th, unsigned char* seg,
                                unsigned char* raw, unsigned int* area, int h, int w, void* stream) {
   if (!prob || !seg || !area || n < 1 || Hm < 1 || Wm < 1 || h < 1 || w < 1) return RSIS_ERR_ARG;
@@ -875,6 +893,18 @@ int rsis_paint_instance_maps(const unsigned long long* bits, long bits_len, cons
     if (in[i] == (const void*)ins || in[i] == (const void*)seg) return RSIS_ERR_ARG;
   if ((long)Ho * Wo >= (1L << 31) || B > 65535 || max_recs > 255) return RSIS_ERR_UNSUPPORTED;
   return rsis_l_paint_instance_maps(bits, bits_len, area, nrec, recs, imgs, B, max_recs, src_y, src_x, Ho, Wo, ins, seg, (hipStream_t)stream);
+}
+
+int rsis_paint_ignore_map(const unsigned long long* bits, long bits_len, long nrec, const long long* crecs, const long long* imgs, int B,
+                          int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, const int* ins, unsigned char* ignore, void* stream) {
+  if (!imgs || !src_y || !src_x || !ins || !ignore || (const void*)ins == (const void*)ignore || nrec < 0 || bits_len < 0 ||
+      (nrec > 0 && (!bits || !crecs)) || B < 1 || max_recs < 0 || Ho < 1 || Wo < 1)
+    return RSIS_ERR_ARG;
+  const void* in[5] = {bits, crecs, imgs, src_y, src_x};
+  for (int i = 0; i < 5; ++i)
+    if (in[i] == (const void*)ignore) return RSIS_ERR_ARG;
+  if ((long)Ho * Wo >= (1L << 31) || B > 65535 || max_recs > 255) return RSIS_ERR_UNSUPPORTED;
+  return rsis_l_paint_ignore_map(bits, bits_len, nrec, crecs, imgs, B, max_recs, src_y, src_x, Ho, Wo, ins, ignore, (hipStream_t)stream);
 }
 
 long rsis_mask_intersect_blocks(long D, long G, long stride) {

@@ -124,3 +124,44 @@ int rsis_l_paint_instance_maps(const u64* bits, long bits_len, const unsigned in
                      recs, imgs, max_recs, src_y, src_x, Ho, Wo, tiles_x, ins, seg, vec);
   return rsis_check_launch();
 }
+
+// ---- the ignore map of a batch (--ignore_regions): crowd records, as bit rows, resampled through the same src_y / src_x tables ----
+// ign[b][i][j] = 1 where ANY crowd record of sample b covers native pixel (src_y[i], src_x[j]) and the painted instance map holds no
+// instance there (an outlined instance inside a crowd still counts), else 0.  One thread per output pixel, at most max_recs (<= 255,
+// the loader keeps 16) records per sample read straight from the tables; integer compares only.  Every element of ign is written.
+// crecs[r] = {first word, words, h, w, 0, 0, 0, 0}; imgs[b] = {first record, records}
+__global__ __launch_bounds__(CM_T) void paint_ignore_kernel(const u64* __restrict__ bits, long bits_len, long nrec, const long long* __restrict__ crecs,
+                                                            const long long* __restrict__ imgs, int max_recs, const int* __restrict__ src_y,
+                                                            const int* __restrict__ src_x, int Ho, int Wo, const int* __restrict__ ins,
+                                                            unsigned char* __restrict__ ign) {
+  const int b = blockIdx.y;
+  const long o = (long)blockIdx.x * CM_T + threadIdx.x;
+  if (o >= (long)Ho * Wo) return;
+  const int i = (int)(o / Wo), j = (int)(o - (long)i * Wo);
+  const long long first = imgs[2 * (long)b];
+  long long cnt = imgs[2 * (long)b + 1];
+  if (first < 0 || cnt < 0 || cnt > max_recs || cnt > CM_MAXREC || first > nrec || cnt > nrec - first) cnt = 0;
+  const int sy = src_y[(long)b * Ho + i], sx = src_x[(long)b * Wo + j];
+  const long out = (long)b * Ho * Wo + o;
+  unsigned char v = 0;
+  if (sy >= 0 && sx >= 0 && ins[out] == 0) {
+    for (int r = 0; r < (int)cnt && !v; ++r) {
+      const long long* R = crecs + 8 * (first + r);
+      const long long fw = R[0], words = R[1], h = R[2], w = R[3];
+      const bool ok = fw >= 0 && words >= 0 && h >= 1 && w >= 1 && h < (1LL << 31) && w < (1LL << 31) && h * w < (1LL << 31) &&
+                      words >= (h * w + 63) / 64 && fw <= bits_len && words <= bits_len - fw;
+      if (!ok || sy >= h || sx >= w) continue;                   // (a record that does not fit the buffers covers nothing)
+      const long e = (long)sx * h + sy;
+      v = (unsigned char)((bits[fw + (e >> 6)] >> (e & 63)) & 1ull);
+    }
+  }
+  ign[out] = v;
+}
+
+int rsis_l_paint_ignore_map(const u64* bits, long bits_len, long nrec, const long long* crecs, const long long* imgs, int B, int max_recs,
+                            const int* src_y, const int* src_x, int Ho, int Wo, const int* ins, unsigned char* ign, hipStream_t st) {
+  const long blocks = ((long)Ho * Wo + CM_T - 1) / CM_T;
+  hipLaunchKernelGGL(paint_ignore_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(CM_T), 0, st, bits, bits_len, nrec, crecs, imgs, max_recs,
+                     src_y, src_x, Ho, Wo, ins, ign);
+  return rsis_check_launch();
+}

@@ -97,6 +97,10 @@ int rsis_l_dropout_heads_mask_bwd(const float* dc, const float* ds, const float*
 int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, hipStream_t st);
 int rsis_l_softiou_bwd(const float* logits, const float* y, const long long* perm, int perm_ld, const float* ca, const float* cb, float* dlogits, int B, int T,
                        int G, long N, hipStream_t st);
+// (ignore null = the plain launches above)
+int rsis_l_softiou_sums_ignore(const float* logits, const float* y, const unsigned char* ignore, float* S, int B, int T, int G, long N, hipStream_t st);
+int rsis_l_softiou_bwd_ignore(const float* logits, const float* y, const unsigned char* ignore, const long long* perm, int perm_ld, const float* ca,
+                              const float* cb, float* dlogits, int B, int T, int G, long N, hipStream_t st);
 int rsis_l_heads_fwd(const float* const* side, const int* C, int n, int B, const float* Wc, const float* bc, int ncls, const float* Ws, const float* bs,
                      float* probs, float* stop, hipStream_t st, const unsigned long long* const* keys = nullptr, float* const* side_out = nullptr,
                      int* const* arg_out = nullptr);
@@ -134,6 +138,8 @@ int rsis_l_rle_to_bits(const unsigned int* counts, long counts_len, const long l
                        unsigned int* area, hipStream_t st);
 int rsis_l_poly_to_bits(const double* xy, long nverts, const long long* parts, long nparts, const long long* recs, int n, unsigned long long* scratch,
                         unsigned long long* bits, long bits_len, unsigned int* area, hipStream_t st);
+int rsis_l_paint_ignore_map(const unsigned long long* bits, long bits_len, long nrec, const long long* crecs, const long long* imgs, int B, int max_recs,
+                            const int* src_y, const int* src_x, int Ho, int Wo, const int* ins, unsigned char* ign, hipStream_t st);
 int rsis_l_paint_instance_maps(const unsigned long long* bits, long bits_len, const unsigned int* area, long nrec, const long long* recs,
                                const long long* imgs, int B, int max_recs, const int* src_y, const int* src_x, int Ho, int Wo, int* ins, int* seg,
                                hipStream_t st);

@@ -15,11 +15,23 @@
 
 typedef const f32x4 __attribute__((address_space(1)))* gcf4_t;
 typedef f32x4 __attribute__((address_space(1)))* gf4_t;
+typedef const unsigned int __attribute__((address_space(1)))* gcu_t;
+
+// IGNORE REGIONS (rsis_softiou_sums_ignore / rsis_softiou_bwd_ignore): ignore[B][N], one byte per pixel, non-zero = the pixel counts for
+// nothing (a COCO crowd, a Cityscapes group).  With k = (ignore == 0):  I = sum k p y,  P = sum k p,  Y = sum k y,  and the gradient is
+// zero where k is.  The kernels below carry it as a bool template parameter: a lane's four pixels are ONE aligned 4-byte load (every lane
+// of a half-wave at the same address: one request), issued unconditionally in the same four-steps-ahead batch as the float4 loads, and k
+// is applied as a SELECT (kept ? v : 0) -- the exact multiplication by 0 / 1, except that an ignored pixel gives +0 whatever the sign or
+// finiteness of what it hides.  IGN = false is the code of before, token for token (NOTES (98) has the resource lines of both).
+__device__ __forceinline__ bool siou_kept(unsigned int w, int e) { return ((w >> (8 * e)) & 0xffu) == 0u; }
 
 // grid = (nsplit, B), 256 threads = 4 waves; wave w of split s walks the pixels [k0, k1) in steps of 8 (N % 8 == 0):
 // lanes 0-31 take pixels +0..3, lanes 32-63 pixels +4..7 of each step (the MFMA K index is only a summation index).
+// IGN: the A-side "ones" row becomes the k row, and the prediction rows are selected by k: S[t][g], S[t][G] and S[T][g] are then all masked.
+template <bool IGN>
 __global__ __launch_bounds__(256) void softiou_sums_kernel(const float* __restrict__ logits, const float* __restrict__ y,
-                                                           float* __restrict__ S, int T, int G, long N, long per_wave) {
+                                                           float* __restrict__ S, int T, int G, long N, long per_wave,
+                                                           const unsigned char* __restrict__ ignore) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -29,17 +41,19 @@ __global__ __launch_bounds__(256) void softiou_sums_kernel(const float* __restri
   const bool brow = l31 < G, bone = l31 == G;
   const float* pa = logits + ((size_t)b * T + (arow ? l31 : 0)) * N + 4 * hi;
   const float* pb = y + ((size_t)b * G + (brow ? l31 : 0)) * N + 4 * hi;
+  const unsigned char* pi = IGN ? ignore + (size_t)b * N + 4 * hi : nullptr;
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   // Loads are UNCONDITIONAL (rows beyond T / G read row 0 and are selected away) and four steps are requested before the first is used:
   // `if (arow) v = load` compiled to branch + load + vmcnt(0) twice per 8-pixel step -- two dependent round trips per step, 120 us for a
   // pass whose bytes need 50 (NOTES (32a)).
-  auto step = [&](const f32x4 va, const f32x4 vb) {
+  auto step = [&](const f32x4 va, const f32x4 vb, const unsigned int vi) {
     f32x4 a, bv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       a[e] = arow ? rsis_sigmoid(va[e]) : (aone ? 1.f : 0.f);
+      if (IGN) a[e] = siou_kept(vi, e) ? a[e] : 0.f;
       bv[e] = brow ? vb[e] : (bone ? 1.f : 0.f);
     }
 #pragma unroll
@@ -48,12 +62,16 @@ __global__ __launch_bounds__(256) void softiou_sums_kernel(const float* __restri
   long k = k0;
   for (; k + 32 <= k1; k += 32) {
     f32x4 va[4], vb[4];
+    unsigned int vi[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { va[u] = *(gcf4_t)(pa + k + 8 * u); vb[u] = *(gcf4_t)(pb + k + 8 * u); }
+    for (int u = 0; u < 4; ++u) {
+      va[u] = *(gcf4_t)(pa + k + 8 * u); vb[u] = *(gcf4_t)(pb + k + 8 * u);
+      if (IGN) vi[u] = *(gcu_t)(pi + k + 8 * u);
+    }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) step(va[u], vb[u]);
+    for (int u = 0; u < 4; ++u) step(va[u], vb[u], vi[u]);
   }
-  for (; k < k1; k += 8) step(*(gcf4_t)(pa + k), *(gcf4_t)(pb + k));
+  for (; k < k1; k += 8) step(*(gcf4_t)(pa + k), *(gcf4_t)(pb + k), IGN ? *(gcu_t)(pi + k) : 0u);
   float* Sb = S + (size_t)b * (T + 1) * (G + 1);
   if (l31 <= G) {
 #pragma unroll
@@ -75,9 +93,14 @@ __global__ __launch_bounds__(256) void softiou_sums_kernel(const float* __restri
 // extra tile row of MFMAs: each lane adds up the four values of its row it feeds to the MFMAs anyway (pairwise, then one chain
 // per lane), and one cross-half add per row at the end gives sum p and (from the wave of T tile 0) sum y.
 // Same load discipline as above: unconditional loads, rows beyond T / G read row 0 and are selected away, four steps in flight.
-template <int NG>
-__global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __restrict__ logits, const float* __restrict__ y,
-                                                                 float* __restrict__ S, int T, int G, long N, long per_wave, int tshift) {
+// IGN: both the probabilities and the GT values are selected by k before they are summed (ps, ys) and fed to the MFMAs.
+// (the map is the LAST kernel argument of all three kernels: the IGN = false instantiations then read their arguments at the offsets of
+//  before and compile to the instruction streams of before.  NG = 4 with the map needs 131 + 128 registers, three more than two waves per
+//  SIMD leave each: the second launch bound asks for two, and the allocator then keeps the accumulators in the unified file, 195 VGPRs.)
+template <int NG, bool IGN>
+__global__ __launch_bounds__(256, (NG == 4 && IGN) ? 2 : 1) void softiou_sums_tiled_kernel(const float* __restrict__ logits, const float* __restrict__ y,
+                                                                 float* __restrict__ S, int T, int G, long N, long per_wave, int tshift,
+                                                                 const unsigned char* __restrict__ ignore) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5, wave = threadIdx.x >> 6;
   const int tw = wave & ((1 << tshift) - 1);                          // T tile of this wave
@@ -87,6 +110,7 @@ __global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __
   const int trow = tw * 32 + l31;
   const bool arow = trow < T;
   const float* pa = logits + ((size_t)b * T + (arow ? trow : 0)) * N + 4 * hi;
+  const unsigned char* pi = IGN ? ignore + (size_t)b * N + 4 * hi : nullptr;
   const float* pb[NG];
   bool brow[NG];
   f32x16 acc[NG];
@@ -99,15 +123,21 @@ __global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[gt][r] = 0.f;
   }
-  auto step = [&](const f32x4 va, const f32x4* vb) {
+  auto step = [&](const f32x4 va, const f32x4* vb, const unsigned int vi) {
     f32x4 a, bv[NG];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = arow ? rsis_sigmoid(va[e]) : 0.f;
+    for (int e = 0; e < 4; ++e) {
+      a[e] = arow ? rsis_sigmoid(va[e]) : 0.f;
+      if (IGN) a[e] = siou_kept(vi, e) ? a[e] : 0.f;
+    }
     ps += (a[0] + a[1]) + (a[2] + a[3]);
 #pragma unroll
     for (int gt = 0; gt < NG; ++gt) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bv[gt][e] = brow[gt] ? vb[gt][e] : 0.f;
+      for (int e = 0; e < 4; ++e) {
+        bv[gt][e] = brow[gt] ? vb[gt][e] : 0.f;
+        if (IGN) bv[gt][e] = siou_kept(vi, e) ? bv[gt][e] : 0.f;
+      }
       ys[gt] += (bv[gt][0] + bv[gt][1]) + (bv[gt][2] + bv[gt][3]);
     }
 #pragma unroll
@@ -118,20 +148,22 @@ __global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __
   long k = k0;
   for (; k + 32 <= k1; k += 32) {
     f32x4 va[4], vb[4][NG];
+    unsigned int vi[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       va[u] = *(gcf4_t)(pa + k + 8 * u);
+      if (IGN) vi[u] = *(gcu_t)(pi + k + 8 * u);
 #pragma unroll
       for (int gt = 0; gt < NG; ++gt) vb[u][gt] = *(gcf4_t)(pb[gt] + k + 8 * u);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) step(va[u], vb[u]);
+    for (int u = 0; u < 4; ++u) step(va[u], vb[u], vi[u]);
   }
   for (; k < k1; k += 8) {
     f32x4 vb[NG];
 #pragma unroll
     for (int gt = 0; gt < NG; ++gt) vb[gt] = *(gcf4_t)(pb[gt] + k);
-    step(*(gcf4_t)(pa + k), vb);
+    step(*(gcf4_t)(pa + k), vb, IGN ? *(gcu_t)(pi + k) : 0u);
   }
   float* Sb = S + (size_t)b * (T + 1) * (G + 1);
 #pragma unroll
@@ -151,28 +183,35 @@ __global__ __launch_bounds__(256) void softiou_sums_tiled_kernel(const float* __
 }
 
 // dlogits[b][t][n] = (ca[b][t] * y + cb[b][t] * (1 - y)) * p (1 - p),  y = Y[b][perm[b][t]][n],  p = sigmoid(logits[b][t][n])
+// IGN: +0.0 at every ignored pixel (a select: 0 * a negative value would leave -0.0)
+template <bool IGN>
 __global__ __launch_bounds__(256) void softiou_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ y,
                                                           const long long* __restrict__ perm, int perm_ld,
                                                           const float* __restrict__ ca, const float* __restrict__ cb,
-                                                          float* __restrict__ dlogits, int T, int G, long N4, long total) {
+                                                          float* __restrict__ dlogits, int T, int G, long N4, long total,
+                                                          const unsigned char* __restrict__ ignore) {
   for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long bt = e / N4, n4 = e - bt * N4;
     const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
     const int g = (int)perm[(size_t)b * perm_ld + t];
     const f32x4 v = *(gcf4_t)(logits + (size_t)e * 4);
     const f32x4 yy = *(gcf4_t)(y + (((size_t)b * G + g) * N4 + n4) * 4);
+    const unsigned int vi = IGN ? *(gcu_t)(ignore + ((size_t)b * N4 + n4) * 4) : 0u;
     const float a = ca[bt], c = cb[bt];
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float p = rsis_sigmoid(v[k]);
       o[k] = (a * yy[k] + c * (1.f - yy[k])) * p * (1.f - p);
+      if (IGN) o[k] = siou_kept(vi, k) ? o[k] : 0.f;
     }
     *(gf4_t)(dlogits + (size_t)e * 4) = o;
   }
 }
 
-int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, hipStream_t st) {
+// ONE launch plan for the plain and the ignore entry points: `ignore` null picks the IGN = false instantiations, the kernels of before
+static int softiou_sums_launch(const float* logits, const float* y, const unsigned char* ignore, float* S, int B, int T, int G, long N,
+                               hipStream_t st) {
   if (B < 0 || T < 0 || G < 0 || N < 0) return RSIS_ERR_ARG;
   if (B == 0) return RSIS_OK;
   if (rsis_zero_async(S, sizeof(float) * (size_t)B * (T + 1) * (G + 1), st) != RSIS_OK) return RSIS_ERR_LAUNCH;
@@ -191,8 +230,9 @@ int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, in
     if (rsis_deterministic()) per = (N + 7) / 8 * 8;          // one group per image: a single contributor per sum
     nblk = (N + per * groups - 1) / (per * groups);
     const dim3 grid((unsigned)nblk, B);
-#define RSIS_SIOU_TILED(NG_) \
-    hipLaunchKernelGGL(softiou_sums_tiled_kernel<NG_>, grid, dim3(256), 0, st, logits, y, S, T, G, N, per, tshift)
+#define RSIS_SIOU_TILED(NG_)                                                                                                          \
+    if (ignore) hipLaunchKernelGGL((softiou_sums_tiled_kernel<NG_, true>), grid, dim3(256), 0, st, logits, y, S, T, G, N, per, tshift, ignore); \
+    else hipLaunchKernelGGL((softiou_sums_tiled_kernel<NG_, false>), grid, dim3(256), 0, st, logits, y, S, T, G, N, per, tshift, ignore)
     switch (nG) {
       case 1: RSIS_SIOU_TILED(1); break;
       case 2: RSIS_SIOU_TILED(2); break;
@@ -209,18 +249,41 @@ int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, in
   if (per_wave < 64) per_wave = 64;
   if (rsis_deterministic()) per_wave = (N + 7) / 8 * 8;      // one wave per image walks every pixel: a single contributor per sum
   nsplit = (int)((N + per_wave * 4 - 1) / (per_wave * 4));
-  hipLaunchKernelGGL(softiou_sums_kernel, dim3(nsplit, B), dim3(256), 0, st, logits, y, S, T, G, N, per_wave);
+  if (ignore) hipLaunchKernelGGL(softiou_sums_kernel<true>, dim3(nsplit, B), dim3(256), 0, st, logits, y, S, T, G, N, per_wave, ignore);
+  else hipLaunchKernelGGL(softiou_sums_kernel<false>, dim3(nsplit, B), dim3(256), 0, st, logits, y, S, T, G, N, per_wave, ignore);
+  return rsis_check_launch();
+}
+
+int rsis_l_softiou_sums(const float* logits, const float* y, float* S, int B, int T, int G, long N, hipStream_t st) {
+  return softiou_sums_launch(logits, y, nullptr, S, B, T, G, N, st);
+}
+
+int rsis_l_softiou_sums_ignore(const float* logits, const float* y, const unsigned char* ignore, float* S, int B, int T, int G, long N,
+                               hipStream_t st) {
+  return softiou_sums_launch(logits, y, ignore, S, B, T, G, N, st);
+}
+
+// ONE launch for the plain and the ignore entry points, as for the sums
+static int softiou_bwd_launch(const float* logits, const float* y, const unsigned char* ignore, const long long* perm, int perm_ld,
+                              const float* ca, const float* cb, float* dlogits, int B, int T, int G, long N, hipStream_t st) {
+  const long total = (long)B * T * (N / 4);
+  long grid = (total + 255) / 256;
+  if (grid > 256L * 32) grid = 256L * 32;
+  if (ignore) hipLaunchKernelGGL(softiou_bwd_kernel<true>, dim3((unsigned)grid), dim3(256), 0, st, logits, y, perm, perm_ld, ca, cb, dlogits,
+                                 T, G, N / 4, total, ignore);
+  else hipLaunchKernelGGL(softiou_bwd_kernel<false>, dim3((unsigned)grid), dim3(256), 0, st, logits, y, perm, perm_ld, ca, cb, dlogits, T, G,
+                          N / 4, total, ignore);
   return rsis_check_launch();
 }
 
 int rsis_l_softiou_bwd(const float* logits, const float* y, const long long* perm, int perm_ld, const float* ca, const float* cb,
                        float* dlogits, int B, int T, int G, long N, hipStream_t st) {
-  const long total = (long)B * T * (N / 4);
-  long grid = (total + 255) / 256;
-  if (grid > 256L * 32) grid = 256L * 32;
-  hipLaunchKernelGGL(softiou_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, st, logits, y, perm, perm_ld, ca, cb, dlogits, T, G,
-                     N / 4, total);
-  return rsis_check_launch();
+  return softiou_bwd_launch(logits, y, nullptr, perm, perm_ld, ca, cb, dlogits, B, T, G, N, st);
+}
+
+int rsis_l_softiou_bwd_ignore(const float* logits, const float* y, const unsigned char* ignore, const long long* perm, int perm_ld,
+                              const float* ca, const float* cb, float* dlogits, int B, int T, int G, long N, hipStream_t st) {
+  return softiou_bwd_launch(logits, y, ignore, perm, perm_ld, ca, cb, dlogits, B, T, G, N, st);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -56,10 +56,21 @@ def maps_from_ids(ids, table=None):
     return ins, seg
 
 
+def ignore_from_ids(ids, table=None):
+    """(B, H, W) integer tensor of (warped) raw `instanceIds` values -> bool (B, H, W): the GROUP regions of trained classes, a bare
+    labelId below 1000 whose class is not 0 ("person group" = 24, "car group" = 26).  Void labels, groups of untrained labels (caravan
+    29, trailer 30) and the warp's zero fill stay counted as background.  A torch expression: once per batch, not hot."""
+    tab = _table(ids.device) if table is None else table.to(device=ids.device, dtype=torch.int32)
+    raw = ids.long()
+    small = (raw >= 0) & (raw < tab.numel())                 # (tab has 34 entries: every index below 1000 that has a class)
+    return small & (tab[raw.clamp(0, tab.numel() - 1)] > 0)
+
+
 class CityScapes(Reader):
     """reference CityScapes(MyDataset): same constructor arguments, `classes`, `get_classes`, `get_sample_list`, `__len__`,
     `get_raw_sample`; `host_item` returns (image, RAW ids) and the loader calls `maps_from_ids` after the warp"""
     same_size = True            # every image of the dataset has one size (1024 x 2048): un-cropped samples can be batched
+    has_ignore_source = True    # group regions: --ignore_regions
 
     def __init__(self, args, transform=None, target_transform=None, augment=False, split="train", resize=False, imsize=256):
         self._setup(args, transform, target_transform, augment, split, resize, imsize, crop=bool(args.crop),   # cityscapes.py:36-49
@@ -76,6 +87,10 @@ class CityScapes(Reader):
     def label_maps(self, maps):
         ids, = maps
         return self.maps_from_ids(ids)
+
+    def ignore_map(self, maps):
+        ids, = maps
+        return ignore_from_ids(ids) if self.ignore_regions else None
 
     def raw_ids(self, index):
         """the `*_gtFine_instanceIds.png` of a sample as an int32 array"""

@@ -15,7 +15,14 @@ The label images never exist on the host, nor at native size anywhere.
 Parsing rules (also INTEGRATION.md):
   classes   : ["<eos>"] + the category names in ascending category-id order; class index = 1 + rank of the category id.  A
               -num_classes other than len(classes) raises and names the right value.
-  crowd     : `iscrowd` records are not painted: their pixels stay background (this model's loss has no ignore region).
+  crowd     : `iscrowd` records are never painted as instances.  Without --ignore_regions their pixels stay background.  With it they
+              make the batch's IGNORE MAP (the loader's sixth tensor, left out of the mask loss): records stored as uncompressed run
+              counts or as polygons go to bit rows with the launches cocoeval uses (rsis_rle_to_bits / rsis_poly_to_bits), and one
+              rsis_paint_ignore_map launch writes the uint8 map at the output size through the same src_y / src_x tables: 1 where any
+              crowd record covers the pixel and no instance was painted there (an outlined instance inside a crowd still counts).  The
+              map is warped with the image and the label maps (fill outside the frame: 0 = counted).  At most MAX_CROWDS = 16 crowd
+              records per image: beyond that the 16 largest by the file's `area` are kept, with one warning per run.  A crowd record in
+              another form (compressed RLE text, counts that do not add up to the image) is skipped and counted in that warning.
   kind      : a record whose segmentation is not polygons (cocoeval.segmentation_kind: RLE of a non-crowd record, a bare box, a broken
               part) is skipped; one warning per run says how many.
   images    : an image with no paintable record is left out of the sample list; the count is printed once.
@@ -39,6 +46,7 @@ import torch
 from .reader import Reader, flip_crop, scale_image
 
 MAX_RECORDS = 255          # instance ids of rsis_targets_from_maps: 0..255
+MAX_CROWDS = 16            # crowd records of one image that make its ignore map (--ignore_regions); COCO images carry one or two
 
 
 def zoom_index(n, m):
@@ -115,6 +123,7 @@ class COCO(Reader):
     `__len__`, `get_raw_sample`, `image_path`, `raw_size`; `host_item` returns (image, record) and the loader paints both maps on the
     device (`stage_tables` on its staging thread, `device_maps` on its copy stream)"""
     num_maps = 0
+    has_ignore_source = True    # iscrowd records: --ignore_regions
 
     def __init__(self, args, transform=None, target_transform=None, augment=False, split="train", resize=False, imsize=256):
         if split not in ("train", "val"):
@@ -142,9 +151,16 @@ class COCO(Reader):
         images = d["images"]
         pos = {im["id"]: k for k, im in enumerate(images)}
         per_image = [[] for _ in images]                                    # paintable records of every image, in file order
-        skipped = 0
+        crowd_of = [[] for _ in images]                                     # --ignore_regions: (area, kind, data) of its crowd records
+        skipped = crowd_skipped = crowd_capped = 0
         for ann in d["annotations"]:
             if ann.get("iscrowd", 0):
+                if self.ignore_regions and ann["image_id"] in pos:
+                    rec = self._crowd_record(ann, images[pos[ann["image_id"]]], segmentation_kind)
+                    if rec is None:
+                        crowd_skipped += 1
+                    else:
+                        crowd_of[pos[ann["image_id"]]].append(rec)
                 continue
             try:
                 kind = segmentation_kind(ann.get("segmentation"))
@@ -158,9 +174,15 @@ class COCO(Reader):
             print("warning: %s: %d records without a polygon segmentation (or of an unknown image / category) are skipped"
                   % (self.ann_file, skipped), file=sys.stderr)
         ids, files, sizes, rec_off, part_off, vert_off, xy, cls = [], [], [], [0], [0], [0], [], []
-        for im, anns in zip(images, per_image):
-            if not anns:
+        self.crowds = []                                                    # sample -> [(kind, data)], at most MAX_CROWDS
+        for im, anns, crowds in zip(images, per_image, crowd_of):
+            if not anns:                                                    # (an image whose only records are crowds stays left out)
                 continue
+            if len(crowds) > MAX_CROWDS:                                    # the largest by `area` (stable: ties in file order)
+                order = np.argsort(-np.asarray([c[0] for c in crowds], np.float64), kind="stable")[:MAX_CROWDS]
+                crowds = [crowds[k] for k in sorted(order.tolist())]
+                crowd_capped += 1
+            self.crowds.append([c[1:] for c in crowds])
             if len(anns) > MAX_RECORDS:                                     # the 255 largest by `area` (stable: ties in file order)
                 order = np.argsort(-np.asarray([float(a.get("area", 0.0)) for a in anns], np.float64), kind="stable")[:MAX_RECORDS]
                 anns = [anns[k] for k in sorted(order.tolist())]
@@ -175,6 +197,10 @@ class COCO(Reader):
                 part_off.append(len(vert_off) - 1)
                 cls.append(class_of[ann["category_id"]])
             rec_off.append(len(cls))
+        if crowd_skipped or crowd_capped:
+            print("warning: %s: --ignore_regions: %d crowd records in a form other than run counts or polygons are skipped; %d images "
+                  "have more than %d crowd records (the largest by area are kept)" % (self.ann_file, crowd_skipped, crowd_capped, MAX_CROWDS),
+                  file=sys.stderr)
         left_out = len(images) - len(ids)
         if left_out:
             print("%s: %d of %d images have no paintable record and are left out" % (self.ann_file, left_out, len(images)))
@@ -186,6 +212,26 @@ class COCO(Reader):
         self.vert_off = np.asarray(vert_off, np.int64)                      # part -> its vertices
         self.xy = np.concatenate(xy) if xy else np.zeros((0,), np.float64)  # (x, y) pairs of every kept part
         self.rec_class = np.asarray(cls, np.int32)
+
+    @staticmethod
+    def _crowd_record(ann, im, segmentation_kind):
+        """(area, kind, data) of a crowd record that can make an ignore region, or None: 'counts' -> uint32 run counts that add up to
+        the image, 'polygons' -> list of float64 parts"""
+        seg = ann.get("segmentation")
+        try:
+            kind = segmentation_kind(seg)
+        except ValueError:
+            return None
+        area = float(ann.get("area", 0.0))
+        if kind == "polygons":
+            return area, kind, [np.asarray(p, dtype=np.float64) for p in seg]
+        if kind == "counts":
+            h, w = int(im["height"]), int(im["width"])
+            c = np.asarray(seg["counts"], dtype=np.int64)
+            if [int(v) for v in seg["size"]] != [h, w] or (c < 0).any() or int(c.sum()) != h * w or len(c) == 0:
+                return None
+            return area, kind, c.astype(np.uint32)
+        return None
 
     def raw_size(self, index):
         """(height, width) of the original image, as the annotation file states it"""
@@ -254,16 +300,92 @@ class COCO(Reader):
             src[b * Ho:(b + 1) * Ho] = sy
             src[B * Ho + b * Wo:B * Ho + (b + 1) * Wo] = sx
         secs = [xy.view(np.int64), ptab.reshape(-1), poly.reshape(-1), paint.reshape(-1), imgs.reshape(-1), src.view(np.int64)]
+        crowd = None
+        if self.ignore_regions:
+            csecs, crowd = self._stage_crowds(records)
+            secs += csecs
         off = np.concatenate([[0], np.cumsum([len(s) for s in secs])])
         layout = dict(off=[int(v) for v in off], nverts=int(nverts.sum()), nparts=len(part), n=n, B=B, Ho=int(Ho), Wo=int(Wo),
-                      words=int(words.sum()), max_recs=int(cnt.max()))
+                      words=int(words.sum()), max_recs=int(cnt.max()), crowd=crowd)
         return np.concatenate(secs), layout
+
+    def _stage_crowds(self, records):
+        """the crowd records of the batch -> (seven more int64 sections, their layout): polygon xy | parts[np][2] | poly recs[npoly][8] |
+        run counts (uint32 pairs) | rle desc[nrle][4] | crowd recs[nc][8] (first word, words, h, w) | imgs[B][2].  The bit rows of the
+        run-count records come first in the crowd bit buffer, those of the polygon records after them."""
+        from ..cocoeval import words_of
+        xy, ptab, prec, counts, desc, crec, imgs = [], [], [], [], [], [], []
+        nv = ncount = 0
+        rle_words = sum(words_of(int(self.native_size[r[0], 0] * self.native_size[r[0], 1]))
+                        for r in records for kind, _d in self.crowds[r[0]] if kind == "counts")
+        rle_at, poly_at = 0, 0
+        for index, _resized, _flip, _crop in records:
+            h, w = int(self.native_size[index, 0]), int(self.native_size[index, 1])
+            nw = words_of(h * w)
+            imgs.append((len(crec), len(self.crowds[index])))
+            for kind, data in self.crowds[index]:
+                if kind == "counts":
+                    desc.append((ncount, len(data), rle_at, nw))
+                    counts.append(data)
+                    ncount += len(data)
+                    crec.append((rle_at, nw, h, w, 0, 0, 0, 0))
+                    rle_at += nw
+                else:
+                    prec.append((len(ptab), len(data), h, w, poly_at, nw, 0, 0))
+                    for part in data:
+                        ptab.append((nv, len(part) // 2))
+                        xy.append(part)
+                        nv += len(part) // 2
+                    crec.append((rle_words + poly_at, nw, h, w, 0, 0, 0, 0))
+                    poly_at += nw
+        allc = np.concatenate(counts + [np.zeros((1 + (ncount + 1) % 2,), np.uint32)]).astype(np.uint32)     # (never empty, an even length)
+        i64 = lambda rows, k: np.asarray(rows, np.int64).reshape(-1, k).reshape(-1)      # noqa: E731
+        secs = [(np.concatenate(xy) if xy else np.zeros((0,), np.float64)).view(np.int64), i64(ptab, 2), i64(prec, 8), allc.view(np.int64),
+                i64(desc, 4), i64(crec, 8), i64(imgs, 2)]
+        lay = dict(nverts=nv, nparts=len(ptab), npoly=len(prec), ncounts=int(len(allc)), nrle=len(desc), n=len(crec),
+                   rle_words=int(rle_words), poly_words=int(poly_at), max_recs=max([c for _f, c in imgs] + [0]))
+        return secs, lay
 
     def stage_batch(self, items, S):
         return self.stage_tables([it[1] for it in items], S)
 
     def maps_to_warp(self, maps, table, layout):
-        return list(self.device_maps(table, layout))
+        ins, seg = self.device_maps(table, layout)
+        if not self.ignore_regions:
+            return [ins, seg]
+        return [ins, seg, self.device_ignore_map(table, layout, ins).to(torch.int32)]       # the map is warped as one more map
+
+    def label_maps(self, maps):
+        return maps[0], maps[1]
+
+    def ignore_map(self, maps):
+        return maps[2] if self.ignore_regions else None
+
+    @staticmethod
+    def device_ignore_map(table, layout, ins):
+        """table / layout of stage_tables under --ignore_regions, ins: the painted instance map -> (B, Ho, Wo) uint8 ignore map: at most
+        three launches on the current stream (run counts -> bits, polygons -> bits, the paint), no sync"""
+        from .._lib import check, lib, ptr, stream
+        L, o, c, dev = lib(), layout["off"], layout["crowd"], table.device
+        B, Ho, Wo = layout["B"], layout["Ho"], layout["Wo"]
+        ign = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev)       # every element is written by the kernel
+        xy, ptab, prec, counts, desc, crec, imgs = (table[o[k]:o[k + 1]] for k in range(6, 13))
+        nw = c["rle_words"] + c["poly_words"]
+        bits = torch.empty((max(nw, 1),), dtype=torch.int64, device=dev)
+        if c["nrle"]:
+            cd = counts.view(torch.int32)
+            ends, area = torch.empty_like(cd), torch.empty((c["nrle"],), dtype=torch.int32, device=dev)
+            check(L.rsis_rle_to_bits(ptr(cd), cd.numel(), ptr(desc), c["nrle"], ptr(ends), ptr(bits), c["rle_words"], ptr(area), stream()),
+                  "rsis_rle_to_bits")
+        if c["npoly"]:
+            scratch = torch.empty((c["poly_words"],), dtype=torch.int64, device=dev)
+            area = torch.empty((c["npoly"],), dtype=torch.int32, device=dev)
+            check(L.rsis_poly_to_bits(ptr(xy), c["nverts"], ptr(ptab), c["nparts"], ptr(prec), c["npoly"], ptr(scratch),
+                                      ptr(bits) + 8 * c["rle_words"], c["poly_words"], ptr(area), stream()), "rsis_poly_to_bits")
+        src = table[o[5]:o[6]].view(torch.int32)
+        check(L.rsis_paint_ignore_map(ptr(bits) if c["n"] else None, nw, c["n"], ptr(crec) if c["n"] else None, ptr(imgs), B, c["max_recs"],
+                                      ptr(src), ptr(src) + 4 * B * Ho, Ho, Wo, ptr(ins), ptr(ign), stream()), "rsis_paint_ignore_map")
+        return ign
 
     @staticmethod
     def device_maps(table, layout):

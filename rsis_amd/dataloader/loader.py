@@ -9,7 +9,7 @@ Split of the work:
            (rsis_affine_nearest, bit-equal to the reference's th_affine2d(mode='nearest')), the reader's `label_maps`, and the target
            tensors runIter reads (targets_from_maps == sequence_from_masks + batch_to_var).
 The loader asks its dataset only what reader.Reader states: `num_maps`, `same_size`, `crop`, `max_seq_len`, `augmentation_transform`,
-`host_item`, the three hooks, and `_cache` (to keep cache hits off the pool)."""
+`host_item`, the four hooks, and `_cache` (to keep cache hits off the pool)."""
 import random
 import threading
 from collections import namedtuple
@@ -64,7 +64,8 @@ Staged = namedtuple("Staged", "image maps table layout mats pins")
 
 
 class DeviceLoader(object):
-    """yields DEVICE batches (x, y_mask, y_class, sw_mask, sw_class).  The next batch is decoded into pinned memory by `num_workers`
+    """yields DEVICE batches (x, y_mask, y_class, sw_mask, sw_class), and a sixth tensor, the (B, N) uint8 ignore map, when the reader's
+    `ignore_map` hook answers (--ignore_regions on coco / cityscapes).  The next batch is decoded into pinned memory by `num_workers`
     threads and copied on a side stream while the current one trains.
 
     One process per GPU (rank / world): `batch_size` is the PER-RANK batch; every rank shuffles the whole dataset with the SAME
@@ -161,6 +162,9 @@ class DeviceLoader(object):
             ins_d, seg_d = self.ds.label_maps(warped)
             y_mask, y_class, sw_mask, sw_class = targets_from_maps(ins_d, seg_d, self.ds.max_seq_len, device=self.device)
             out = (x.contiguous(), y_mask, y_class, sw_mask, sw_class)
+            ign = self.ds.ignore_map(warped)                                    # --ignore_regions: a sixth tensor, (B, N) uint8
+            if ign is not None:
+                out = out + ((ign != 0).reshape(ign.size(0), -1).to(torch.uint8).contiguous(),)
         cur.wait_stream(st)
         for t in out:                       # allocated on the copy stream, consumed on the caller's: keep the caching allocator from handing
             t.record_stream(cur)            # the blocks to the next batch's side-stream work while the step still reads them

@@ -9,8 +9,12 @@ The contract with DeviceLoader (loader.py): every reader answers the same questi
   stage_batch    per batch, on the staging thread: host items -> (int64 table, layout) for ONE more host-to-device copy, or
                  (None, None) (the default);
   maps_to_warp   on the copy stream, before the warp: the copied maps (and table) -> the list of integer maps to warp (the maps);
-  label_maps     on the copy stream, after the warp: the warped integer maps -> (instance map, class map) (the two maps as they are)."""
+  label_maps     on the copy stream, after the warp: the warped integer maps -> (instance map, class map) (the two maps as they are);
+  ignore_map     on the copy stream, after the warp: the warped integer maps -> the (B, H, W) ignore region of the batch (non-zero / True =
+                 the pixel is left out of the mask loss), or None (the default: no such region, the loader yields 5-tuples).  A reader
+                 with a source for it answers only under `--ignore_regions`; the warp's zero fill outside the frame counts."""
 import os
+import sys
 
 import numpy as np
 
@@ -46,11 +50,22 @@ def flip_crop(a, flip, crop, S):
     return a
 
 
+_WARNED = set()
+
+
+def warn_once(msg):
+    """one line on stderr, once per process"""
+    if msg not in _WARNED:
+        _WARNED.add(msg)
+        print(msg, file=sys.stderr, flush=True)
+
+
 class Reader(object):
     """reference MyDataset: `classes`, `get_classes`, `get_sample_list`, `__len__`, `get_raw_sample`; plus `image_path`, `raw_size`,
     `host_item` and the loader contract of the module docstring"""
     num_maps = 1
     same_size = False
+    has_ignore_source = False       # the dataset marks regions "objects here, not outlined" (coco, cityscapes)
 
     def _setup(self, args, transform, target_transform, augment, split, resize, imsize, crop, zoom_range):
         """the constructor state every reader has; `crop` and `zoom_range` are what differs between the datasets"""
@@ -65,6 +80,10 @@ class Reader(object):
         if augment:
             self.augmentation_transform = RandomAffine(rotation_range=args.rotation, translation_range=args.translation,
                                                        shear_range=args.shear, zoom_range=zoom_range, interp="nearest")
+        self.ignore_regions = bool(getattr(args, "ignore_regions", False))
+        if self.ignore_regions and not self.has_ignore_source:
+            warn_once("--ignore_regions: %s has no source for an ignore region (no crowd / group records): no map is produced"
+                      % type(self).__name__)
         self._cache, self._cache_bytes = {}, 0
         self._cache_limit = int(float(os.environ.get("RSIS_LOADER_CACHE_MB", "1024")) * (1 << 20))
 
@@ -131,3 +150,6 @@ class Reader(object):
     def label_maps(self, maps):
         ins, seg = maps
         return ins, seg
+
+    def ignore_map(self, maps):
+        return None

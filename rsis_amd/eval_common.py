@@ -42,6 +42,11 @@ class EvalDriver(object):
     def __init__(self, args):
         self.args, self.split, self.T = args, args.eval_split, args.maxseqlen
         self.dataset = None
+        if getattr(args, "ignore_regions", False):
+            # the drivers share train.py's parser.  The ignore map belongs to the training loss; the measures have their own crowd / group
+            # rules.  The readers and the synthetic loader of a driver are opened without it, so every driver sees 5-tuples.
+            print("--ignore_regions is a training option: the evaluation drivers do not use it", file=sys.stderr)
+            args.ignore_regions = False
 
     def open_dataset(self, name):
         """eval.py:191-218, the part every dataset shares: the reader of -eval_split with its class names, the models, the loader (file

@@ -879,15 +879,31 @@ def softiou_supported(out_masks, y_mask):
             1 <= out_masks.size(1) <= 128 and 1 <= y_mask.size(1) <= 128 and out_masks.size(2) >= 8 and out_masks.size(2) % 8 == 0)
 
 
-def softiou_sums(out_masks, y_mask):
+def _ignore_map(ignore, B, N, device):
+    """the (B, N) uint8 ignore map as the soft-IoU kernels read it: contiguous, on the device, 4-byte aligned (a lane's four pixels are
+    one word); None stays None"""
+    if ignore is None:
+        return None
+    if ignore.dtype != torch.uint8 or ignore.device != device or tuple(ignore.shape) != (B, N):
+        raise ValueError("ignore map: uint8 (%d, %d) on %s expected, got %s %s on %s" % (B, N, device, ignore.dtype, tuple(ignore.shape), ignore.device))
+    ignore = _contig(ignore)
+    return ignore.clone() if ignore.data_ptr() % 4 else ignore
+
+
+def softiou_sums(out_masks, y_mask, ignore=None):
     """S (B, T+1, G+1): intersections sigmoid(out_masks[b,t]) . y_mask[b,g], plus the row / column of plain sums
-    (include/rsis_hip.h: rsis_softiou_sums).  No gradient."""
+    (include/rsis_hip.h: rsis_softiou_sums).  ignore: (B, N) uint8, non-zero = the pixel is left out of every sum
+    (rsis_softiou_sums_ignore); None = the plain entry point.  No gradient."""
     out_masks, y_mask = _contig(out_masks.detach()), _contig(y_mask)
     require_cuda_f32(out_masks, y_mask)
     B, T, N = out_masks.shape
     G = y_mask.shape[1]
     S = torch.empty((B, T + 1, G + 1), dtype=torch.float32, device=out_masks.device)
-    check(lib().rsis_softiou_sums(ptr(out_masks), ptr(y_mask), ptr(S), B, T, G, N, stream()), "rsis_softiou_sums")
+    if ignore is None:
+        check(lib().rsis_softiou_sums(ptr(out_masks), ptr(y_mask), ptr(S), B, T, G, N, stream()), "rsis_softiou_sums")
+    else:
+        ignore = _ignore_map(ignore, B, N, out_masks.device)
+        check(lib().rsis_softiou_sums_ignore(ptr(out_masks), ptr(y_mask), ptr(ignore), ptr(S), B, T, G, N, stream()), "rsis_softiou_sums_ignore")
     return S
 
 
@@ -903,33 +919,42 @@ class _SoftIoUMatchedFn(torch.autograd.Function):
     the backward is one elementwise kernel over the logits."""
 
     @staticmethod
-    def forward(ctx, out_masks, y_mask, perm, S, e):
+    def forward(ctx, out_masks, y_mask, perm, S, e, ignore=None):
         B, T, N = out_masks.shape
         idx = perm[:, :T]
         inter = torch.gather(S[:, :T, :-1], 2, idx.unsqueeze(-1)).squeeze(-1)          # (B, T)
         ysum = torch.gather(S[:, -1, :-1], 1, idx)
         den = S[:, :T, -1] + ysum - inter + e
-        ctx.save_for_backward(out_masks, y_mask, perm, inter, den)
+        ctx.has_ignore = ignore is not None
+        ctx.save_for_backward(*((out_masks, y_mask, perm, inter, den) + ((ignore,) if ignore is not None else ())))
         return 1 - inter / den
 
     @staticmethod
     def backward(ctx, g):
-        out_masks, y_mask, perm, inter, den = ctx.saved_tensors
+        out_masks, y_mask, perm, inter, den = ctx.saved_tensors[:5]
         B, T, N = out_masks.shape
         g = g.contiguous().float()
         ca = (-g / den).contiguous()
         cb = (g * inter / (den * den)).contiguous()
         logits = _contig(out_masks.detach())
         d = torch.empty_like(logits)
-        check(lib().rsis_softiou_bwd(ptr(logits), ptr(y_mask), ptr(perm), perm.shape[1], ptr(ca), ptr(cb), ptr(d), B, T,
-                                     y_mask.shape[1], N, stream()), "rsis_softiou_bwd")
-        return d, None, None, None, None
+        if ctx.has_ignore:
+            check(lib().rsis_softiou_bwd_ignore(ptr(logits), ptr(y_mask), ptr(ctx.saved_tensors[5]), ptr(perm), perm.shape[1], ptr(ca), ptr(cb),
+                                                ptr(d), B, T, y_mask.shape[1], N, stream()), "rsis_softiou_bwd_ignore")
+        else:
+            check(lib().rsis_softiou_bwd(ptr(logits), ptr(y_mask), ptr(perm), perm.shape[1], ptr(ca), ptr(cb), ptr(d), B, T,
+                                         y_mask.shape[1], N, stream()), "rsis_softiou_bwd")
+        return d, None, None, None, None, None
 
 
-def softiou_matched(out_masks, y_mask, perm, S, e=1e-6):
-    """(B, T) soft-IoU cost of every prediction against its matched ground-truth mask; differentiable w.r.t. out_masks."""
+def softiou_matched(out_masks, y_mask, perm, S, e=1e-6, ignore=None):
+    """(B, T) soft-IoU cost of every prediction against its matched ground-truth mask; differentiable w.r.t. out_masks.
+    ignore: the map S was computed with (softiou_sums): the gradient is zero at its pixels."""
     y_mask, perm = _contig(y_mask), _contig(perm)
-    return _SoftIoUMatchedFn.apply(out_masks, y_mask, perm, S, float(e))
+    if ignore is None:
+        return _SoftIoUMatchedFn.apply(out_masks, y_mask, perm, S, float(e))
+    ignore = _ignore_map(ignore, out_masks.shape[0], out_masks.shape[2], out_masks.device)
+    return _SoftIoUMatchedFn.apply(out_masks, y_mask, perm, S, float(e), ignore)
 
 
 # ---- THE rule that picks the heads kernels (csrc/losses.hip), asked by _HeadsFn and by decoder_seq's forward heads and

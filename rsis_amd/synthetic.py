@@ -30,10 +30,31 @@ def synthetic_targets(seed, B, H, W, gt_maxseqlen=20, n_inst=12, num_classes=21)
     return torch.from_numpy(y_mask), torch.from_numpy(y_class), torch.from_numpy(sw_mask), torch.from_numpy(sw_class)
 
 
-def synthetic_batch(seed, B, H, W, gt_maxseqlen=20, n_inst=12, num_classes=21, device="cuda"):
+def synthetic_ignore(seed, B, H, W):
+    """(B, H*W) uint8: one seeded rectangle per image (5-25 % of the area), 1 inside -- the stand-in for a crowd / group region"""
+    r = np.random.default_rng([int(seed), 555])
+    ign = np.zeros((B, H, W), np.uint8)
+    for b in range(B):
+        area = r.uniform(0.05, 0.25) * H * W
+        ar = r.uniform(0.5, 2.0)
+        h = int(np.clip(round(np.sqrt(area * ar)), 1, H))
+        w = int(np.clip(round(area / max(h, 1)), 1, W))
+        y0 = int(r.integers(0, H - h + 1))
+        x0 = int(r.integers(0, W - w + 1))
+        ign[b, y0:y0 + h, x0:x0 + w] = 1
+    return torch.from_numpy(ign.reshape(B, H * W))
+
+
+def synthetic_batch(seed, B, H, W, gt_maxseqlen=20, n_inst=12, num_classes=21, device="cuda", ignore_regions=False):
+    """ignore_regions (--ignore_regions): a 6-tuple, the sixth the ignore map of synthetic_ignore, with y_mask zero inside it (as a loader
+    paints it: a crowd pixel belongs to no outlined instance)"""
     g = np.random.default_rng([int(seed), 123])
     x = torch.from_numpy(g.standard_normal((B, 3, H, W), dtype=np.float32))
     y_mask, y_class, sw_mask, sw_class = synthetic_targets(seed, B, H, W, gt_maxseqlen, n_inst, num_classes)
+    if ignore_regions:
+        ign = synthetic_ignore(seed, B, H, W)
+        y_mask = y_mask * (ign == 0).to(y_mask.dtype).unsqueeze(1)
+        return tuple(t.to(device) for t in (x, y_mask, y_class, sw_mask, sw_class, ign))
     return tuple(t.to(device) for t in (x, y_mask, y_class, sw_mask, sw_class))
 
 
@@ -43,7 +64,8 @@ class SyntheticLoader(object):
     def __init__(self, args, n_batches, seed, device="cuda", distinct=2, rank=0, batch_size=None):
         H = W = args.imsize
         self.batches = [synthetic_batch(seed + 1000 * rank + i, batch_size or args.batch_size, H, W, args.gt_maxseqlen,
-                                        getattr(args, "synthetic_instances", 12), args.num_classes, device)
+                                        getattr(args, "synthetic_instances", 12), args.num_classes, device,
+                                        ignore_regions=bool(getattr(args, "ignore_regions", False)))
                         for i in range(distinct)]
         self.n = n_batches
         self._t_run = {}

@@ -89,7 +89,7 @@ def apply_update(args, optims, gscale=1.0):
 
 
 def runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits, optims, mode="train", reducer=None,
-            sync_losses=True, t_run=None, want_outs=True, do_update=True, between=None):
+            sync_losses=True, t_run=None, want_outs=True, do_update=True, between=None, ignore=None):
     """Runs forward, computes loss and (if train mode) updates parameters for the provided batch (train.py:54-197).
     Returns (losses [total, iou, stop, class], outs [sigmoid(masks), class probs], perms [y_mask_perm, y_class_perm, assignment]).
     want_outs=False (training loops that only log the losses, as the reference's trainIters does: train.py:344-356): the
@@ -172,11 +172,12 @@ def runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits
     with torch.no_grad():
         scores = torch.ones(y_mask.size(0), args.gt_maxseqlen, args.maxseqlen, device=x.device)
         if fused_iou:
-            iou_sums = ops.softiou_sums(out_masks, y_mask)
+            iou_sums = ops.softiou_sums(out_masks, y_mask, ignore=ignore)          # (ignore None: the plain entry point)
             scores[:, :, :t] = args.iou_weight * ops.softiou_cost_matrix(iou_sums)
         else:
             log_once("softiou-bmm", "soft-IoU scores through torch.bmm (ops.softiou_supported is False for these shapes / dtypes)")
-            scores[:, :, :t] = args.iou_weight * softIoU_matrix(y_mask, out_masks)
+            keep = (ignore == 0).to(out_masks.dtype) if ignore is not None else None       # (B, N): the same definition in torch
+            scores[:, :, :t] = args.iou_weight * softIoU_matrix(y_mask, out_masks, keep=keep)
         valid = (sw_mask.unsqueeze(-1) * sw_mask[:, 0:args.maxseqlen].unsqueeze(1) > 0).float()   # :127-130
         scores = scores * valid + (1 - valid) * 10                                                 # :131
         if scores.is_cuda and scores.size(1) <= 128 and scores.size(1) >= scores.size(2):
@@ -197,9 +198,10 @@ def runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits
     with torch.set_grad_enabled(train):
         N, C = out_masks.size(-1), out_classes.size(-1)
         if fused_iou:
-            siou = ops.softiou_matched(out_masks, y_mask, perm, iou_sums)                          # same sums, no second pass
+            siou = ops.softiou_matched(out_masks, y_mask, perm, iou_sums, ignore=ignore)           # same sums, no second pass
         else:
-            siou = softIoU(y_mask_perm.reshape(-1, N), out_masks.reshape(-1, N))
+            siou = softIoU(y_mask_perm.reshape(-1, N), out_masks.reshape(-1, N),
+                           keep=None if keep is None else keep.unsqueeze(1).expand(-1, t, -1).reshape(-1, N))
         cls_w, bw = getattr(class_crit, "balance_weight", None), getattr(stop_xentropy, "balance_weight", None)
         if out_classes.is_cuda and out_classes.dtype == torch.float32:
             # the three masked means and their weighted sum (:159-176) in one launch each way
@@ -448,9 +450,10 @@ class GraphedStep(object):
         return self.graphs[1] if self.graphs and len(self.graphs) > 1 else None
 
     def _run(self, batch, t_run, do_update=True, between=None):
-        return runIter(self.args, self.encoder, self.decoder, *batch, self.crits, self.optims, mode="train",
+        # (a batch with an ignore map is a 6-tuple: the map is one more static input, copied per replay like the other five)
+        return runIter(self.args, self.encoder, self.decoder, *batch[:5], self.crits, self.optims, mode="train",
                        reducer=None if self.split else self.reducer, sync_losses=False, t_run=t_run, want_outs=False, do_update=do_update,
-                       between=between)
+                       between=between, ignore=batch[5] if len(batch) > 5 else None)
 
     def _groups(self):
         return [o.group for o in self.optims if isinstance(o, FlatOptimizer)]
@@ -673,7 +676,7 @@ def trainIters(args):
         # modules read `dtype` (which MFMA kernels they run) from the namespace they are constructed with, and the namespace that
         # is re-saved next to the checkpoint must say what actually ran
         for k in ("synthetic", "synthetic_batches", "synthetic_instances", "models_root", "max_epoch", "log_term", "graph", "dtype",
-                  "enc_lr_quirk"):
+                  "enc_lr_quirk", "ignore_regions"):
             setattr(load_args, k, getattr(args, k, None))
         encoder, decoder = FeatureExtractor(load_args), RSIS(load_args)
         encoder_dict, decoder_dict = check_parallel(encoder_dict, decoder_dict)
@@ -769,16 +772,19 @@ def trainIters(args):
                 best_val_loss, acc_patience, mt_val = 1000, 0, -1
         for split in ("train", "val"):                                    # :341
             n_img, t_split = 0, time.time()
-            for batch_idx, (x, y_mask, y_class, sw_mask, sw_class) in enumerate(loaders[split]):
+            for batch_idx, batch in enumerate(loaders[split]):
+                x, y_mask, y_class, sw_mask, sw_class = batch[:5]
+                ignore = batch[5] if len(batch) > 5 else None             # --ignore_regions: (B, N) uint8, both splits
                 t_run = loaders[split].steps_to_run(args, sw_mask) if hasattr(loaders[split], "steps_to_run") else None
                 if split == "train" and getattr(args, "graph", False) and t_run is not None:
                     # one captured hipGraph per (shapes, T, loss switches, encoder update, active parameter set)
-                    key = (tuple(x.shape), tuple(y_mask.shape), t_run, args.use_class_loss, args.use_stop_loss, args.update_encoder)
-                    if graphs.get("mode", key[3:]) != key[3:]:       # loss switches / encoder update changed: other launch set
+                    key = (tuple(x.shape), tuple(y_mask.shape), t_run, ignore is not None, args.use_class_loss, args.use_stop_loss,
+                           args.update_encoder)
+                    if graphs.get("mode", key[4:]) != key[4:]:       # loss switches / encoder update changed: other launch set
                         for gs in graphs.pop("cache", {}).values():
                             gs.release()
                         graphs.pop("key", None)
-                    graphs["mode"] = key[3:]
+                    graphs["mode"] = key[4:]
                     if graphs.get("key") != key:
                         # (a data set whose batches stop at different steps alternates between a few keys: keep the last few
                         #  captures instead of re-capturing on every change; a resident synthetic batch only ever has one)
@@ -800,14 +806,15 @@ def trainIters(args):
                         else:
                             cache[key] = cache.pop(key)            # most recently used goes last
                         graphs["key"], graphs["step"] = key, cache[key]
-                    losses, _outs, _perm = graphs["step"]((x, y_mask, y_class, sw_mask, sw_class), t_run)
+                    losses, _outs, _perm = graphs["step"](tuple(batch[:5]) + ((ignore,) if ignore is not None else ()), t_run)
                     if graphs["step"].failed is not None and not graphs.get("warned") and rank == 0:
                         print("[train] hipGraph capture failed (%s): this configuration runs eagerly" % graphs["step"].failed)
                         graphs["warned"] = True
                     losses = [v.clone() for v in losses]      # (static tensors of the graph: keep this step's values)
                 else:
                     losses, _outs, _perm = runIter(args, encoder, decoder, x, y_mask, y_class, sw_mask, sw_class, crits, optims,
-                                                   mode=split, reducer=reducer, sync_losses=False, t_run=t_run, want_outs=False)
+                                                   mode=split, reducer=reducer, sync_losses=False, t_run=t_run, want_outs=False,
+                                                   ignore=ignore)
                 for k, v in zip(("total", "iou", "stop", "class"), losses):
                     epoch_losses[split][k].append(v)
                 n_img += x.size(0) * world

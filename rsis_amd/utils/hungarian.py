@@ -29,9 +29,12 @@ def StableBalancedMaskedBCE(target, out, balance_weight=None):
     return losses.squeeze()
 
 
-def softIoU(target, out, e=1e-6):
-    """hungarian.py:62-89: cost = 1 - sum(p*y) / (sum(p + y - p*y) + e) per row, p = sigmoid(out)."""
+def softIoU(target, out, e=1e-6, keep=None):
+    """hungarian.py:62-89: cost = 1 - sum(p*y) / (sum(p + y - p*y) + e) per row, p = sigmoid(out).
+    keep (rows, N) in {0, 1}: the pixels that count (an ignore region is keep = 0); both p and y are multiplied by it."""
     out = torch.sigmoid(out)
+    if keep is not None:
+        out, target = out * keep, target * keep
     num = (out * target).sum(1, True)
     den = (out + target - out * target).sum(1, True) + e
     iou = num / den
@@ -39,11 +42,13 @@ def softIoU(target, out, e=1e-6):
     return cost.squeeze()
 
 
-def softIoU_matrix(y_mask, out_masks, e=1e-6):
+def softIoU_matrix(y_mask, out_masks, e=1e-6, keep=None):
     """All-pairs soft-IoU cost in one batched contraction: cost[b, g, t] = softIoU(y_mask[b, g], out_masks[b, t]).
     Equals the reference's per-timestep `repeat` + softIoU of train.py:102-109 (same sums, one GEMM instead of a
-    gt_T-fold copy of every prediction)."""
+    gt_T-fold copy of every prediction).  keep (B, N) in {0, 1}: the pixels that count, as in softIoU."""
     p = torch.sigmoid(out_masks)                                    # (B, T, N)
+    if keep is not None:
+        p, y_mask = p * keep.unsqueeze(1), y_mask * keep.unsqueeze(1)
     inter = torch.bmm(y_mask, p.transpose(1, 2))                    # (B, G, T)
     den = y_mask.sum(2, keepdim=True) + p.sum(2).unsqueeze(1) - inter + e
     return 1 - inter / den
